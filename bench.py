@@ -13,6 +13,12 @@ tiles to rank 0 over RCCL - total work is fixed, so scaling is "strong".
 `python bench.py --gpus N` starts its own N ranks (a child `python -m torch.distributed.run`, before this process touches
 the GPU); under an external launcher (WORLD_SIZE set) it is one of the ranks.
 
+A plain run does what the headline needs and nothing else: set-up, warm-up, the `--steps` timed steps, the outputs of the last
+timed step when `--dump-outputs DIR` is given, and the result line (its roofline comes from the timed steps' own events and the
+committed counter profiles).  `--full` adds every other leg of the record: the same steps without phase events, the empty-space
+skipping leg, the view x transfer-function matrix and the variants, the CPU baseline, the forced gather's check and, for the
+default command, the extra legs in child processes.
+
 Output (round 5): rank 0 prints ONE JSON line of < 4 KB on stdout - the contract's fields, the dominant kernel's `roofline`, `cpu_baseline`,
 a four-figure summary per variant and extra leg (`compact_record`) - and writes the full record (views, variants, per-kernel counters, per-rank
 tables, the device group, the extra legs) to `bench_detail.json` beside this script (`--detail-file`), to gpurun_out/ when that directory
@@ -252,6 +258,30 @@ def cpu_baseline(cfg, vol_host, colors, alphas, vr, cam, noise=None, budget_s=10
 
 
 COMPACT_LIMIT = 4096   # bytes of the ONE stdout line (the driver's record keeps a few KB of stdout; 20 KB of detail made it unparseable)
+DUMP_LIMIT = 64 * 10**6   # bytes of all --dump-outputs arrays together
+DUMP_SEED = 1             # the pixel sample of a frame above DUMP_LIMIT: the same pixels in every run
+DUMP_COUNTERS = ("samples", "shaded_samples", "shadow_samples", "rays", "active_pixels", "skipped_samples", "skipped_shadow_samples")
+
+
+def dump_outputs(path, layers, counters):
+    """--dump-outputs: `layers` = {name: (H, W, C) float32 array} of one frame, written whole while all of them fit DUMP_LIMIT, else the same
+    seeded sample of pixels from each (as (k, C) arrays, the flat pixel indices row-major from row 0 = bottom in pixel_index.npy); `counters` =
+    the step's sample counters (float64, exact below 2^53) in DUMP_COUNTERS order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    h, w = next(iter(layers.values())).shape[:2]
+    per_pixel = sum(a.shape[2] * 4 for a in layers.values())
+    out = {"counters": np.asarray(counters, dtype=np.float64)}
+    if h * w * per_pixel <= DUMP_LIMIT:
+        out.update({k: np.ascontiguousarray(a, dtype=np.float32) for k, a in layers.items()})
+    else:
+        k = (DUMP_LIMIT - 4096) // (per_pixel + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, size=k, replace=False))
+        out.update({name: np.ascontiguousarray(a.reshape(h * w, -1)[idx], dtype=np.float32) for name, a in layers.items()})
+        out["pixel_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 def _sig(x, digits=5):
@@ -370,7 +400,7 @@ def run_extra_leg(argv, timeout_s):
     import tempfile
     fd, detail = tempfile.mkstemp(prefix="ovr_bench_leg_", suffix=".json")
     os.close(fd)
-    cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-extras", "--no-cpu-baseline", "--no-views", "--no-skip-leg", "--detail-file", detail]
+    cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--no-extras", "--no-cpu-baseline", "--no-views", "--no-skip-leg", "--detail-file", detail]
     t0 = time.perf_counter()
     try:
         p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
@@ -456,6 +486,12 @@ def main():
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"), help="where rank 0 writes the full record (views, variants, per-kernel counters, per-rank tables, "
                     "extra legs); stdout carries one compact line of < 4 KB")
     ap.add_argument("--no-extras", action="store_true", help="do not run the extra legs of the default command (C4 and C5 on one GPU, rank 0's shard of 8, the device group)")
+    ap.add_argument("--full", action="store_true", help="besides the headline's timed steps, run what the record adds to it: the same steps without phase events, the "
+                    "empty-space-skipping leg, the view x TF matrix and the variants, the CPU baseline, the forced gather's check and the default command's extra "
+                    "legs (the --no-* switches above leave single parts out).  Off: set-up, warm-up, the timed steps, --dump-outputs and the result line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: rank 0's "
+                    "frame (rgba; grad, the gradient layer, where one process holds the whole frame) in float32 and that step's counters in float64; "
+                    f"at most {DUMP_LIMIT // 10**6} MB in all (larger frames: a seeded sample of pixels, their indices in pixel_index.npy)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -577,7 +613,7 @@ def worker(args, world):
     ren.commit()
     vinfo = ren.volume_info()
     vol_host = None
-    want_cpu = world == 1 and not multi and not args.no_cpu_baseline   # rank 0 at N = 1 only
+    want_cpu = args.full and world == 1 and not multi and not args.no_cpu_baseline   # rank 0 at N = 1 only
     if want_cpu:
         vol_host = vol.cpu().numpy() if cfg["dtype"] != "uint16" or hasattr(torch, "uint16") else vol.cpu().numpy().view(np.uint16)
     del vol
@@ -726,17 +762,29 @@ def worker(args, world):
     main_leg = timed_leg(args.steps, args.warmup)
     main_extra_warmup = timed_leg.extra_warmup
     dt, tot, kernel_ms, phase_ms, last_stats = main_leg["dt"], main_leg["tot"], main_leg["kernel_ms"], main_leg["phase_ms"], main_leg["last"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step, taken before any other leg renders into the same accumulated frame
+        if gatherer is not None:
+            layers = {"rgba": gatherer.frame.cpu().numpy()}
+        else:
+            fb = ovr.FrameBufferData()
+            ren.mapframe(fb)
+            layers = {"rgba": np.array(fb.rgba.data(), copy=True), "grad": np.array(fb.grad.data(), copy=True)}
+        dumped = dump_outputs(args.dump_outputs, layers, [getattr(last_stats, k) for k in DUMP_COUNTERS])
     # The same steps again without the two events between the frame's kernels (ovr_hip_set_phase_timing(0), ABI v9: what the plugin runs).  The
     # headline's timed region keeps them - its per-kernel durations ARE those events - and pays ~16 us per frame for it; this leg is never `value`.
-    ren.set_phase_timing(False)
-    timed_leg.phases = False
-    plain_leg = timed_leg(args.steps, 2)
-    timed_leg.phases = True
-    ren.set_phase_timing(True)
-    without_phase_events = {"ms_per_step": plain_leg["dt"] / args.steps * 1e3, "fps": args.steps / plain_leg["dt"],
-                            "msamples_per_s": plain_leg["tot"]["samples"] / plain_leg["dt"] / 1e6, "steps": args.steps,
-                            "note": "ovr_hip_set_phase_timing(0): no hipEventRecord between the frame's kernels - the plugin's setting; same frames (the headline's region takes them on every 4th step)"}
-    if multi and world == 1:
+    without_phase_events = None
+    if args.full:
+        ren.set_phase_timing(False)
+        timed_leg.phases = False
+        plain_leg = timed_leg(args.steps, 2)
+        timed_leg.phases = True
+        ren.set_phase_timing(True)
+        without_phase_events = {"ms_per_step": plain_leg["dt"] / args.steps * 1e3, "fps": args.steps / plain_leg["dt"],
+                                "msamples_per_s": plain_leg["tot"]["samples"] / plain_leg["dt"] / 1e6, "steps": args.steps,
+                                "note": "ovr_hip_set_phase_timing(0): no hipEventRecord between the frame's kernels - the plugin's setting; same frames (the headline's region takes them on every 4th step)"}
+    if args.full and multi and world == 1:
         # forced single-rank gather: the gathered frame must be the renderer's own frame
         fb = ovr.FrameBufferData()
         ren.mapframe(fb, device=True)
@@ -748,7 +796,7 @@ def worker(args, world):
     # extra leg (N = 1): the same frames with empty-space skipping over the reference's macrocell grids; reported
     # beside the headline, never as `value`.  Same number of accumulated frames after a reset, so the frames must be equal bit for bit
     skip_leg = None
-    if not multi and not args.skip_empty and not args.no_skip_leg:
+    if args.full and not multi and not args.skip_empty and not args.no_skip_leg:
         fb = ovr.FrameBufferData()
         set_cam()   # any camera commit resets the accumulation (device_impl.cpp:125-144)
         ren.commit()
@@ -793,7 +841,7 @@ def worker(args, world):
     # view x transfer-function matrix (N = 1; SURVEY 8d: "both cameras and both TFs reported"): the headline cell is the timed
     # region above, the other cells are short legs of the same renderer (3 warm-up + 10 timed frames each)
     views = None
-    if not multi and not args.no_views and not args.skip_empty:
+    if args.full and not multi and not args.no_views and not args.skip_empty:
         views = {}
         for vcam, vtf in itertools.product(("front", "oblique"), ("sparse", "dense")):
             if (vcam, vtf) == (cfg["cam"], cfg["tf"]):
@@ -974,6 +1022,10 @@ def worker(args, world):
                          "lds_staging": {"on": bool(args.lds_staging), "fallback_taps_per_frame": int(last_stats.lds_fallback_taps),
                                          "unstaged_workgroup_rounds_per_frame": int(last_stats.lds_unstaged_rounds), "workgroup_rounds_per_frame": int(last_stats.lds_rounds)}},
         }
+        if without_phase_events is None:
+            del out["without_phase_events"]
+        if dumped:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if group_devices:
             gn, gkind, gms = ren.group_info()
             members = [ren.member_stats(i) for i in range(gn)]
@@ -1019,7 +1071,7 @@ def worker(args, world):
         # ranks on one card), OVR_BENCH_EXTRA_DEVICES=0,0 replaces the N > 1 leg's device list (the box has one GPU)
         if os.environ.get("OVR_BENCH_FORCE_EXTRAS") == "1":
             default_cmd = True
-        if default_cmd and not args.no_extras:
+        if args.full and default_cmd and not args.no_extras:
             torch.cuda.empty_cache()
             extra = {}
             if world == 1:

@@ -126,10 +126,10 @@ print("HEALED")
 
 
 def test_the_default_bench_command_prints_one_compact_line():
-    """VERDICT r4 #1, on the GPU: `python bench.py --steps 2 --warmup 1` (every leg of the default command) - exactly one `{` line on stdout, below 4 KB,
+    """VERDICT r4 #1, on the GPU: `python bench.py --full --steps 2 --warmup 1` (every leg of the default command) - exactly one `{` line on stdout, below 4 KB,
     with the dominant kernel's roofline and the CPU baseline; the full record is in the detail file"""
     from helpers import run_bench
-    c, d, out = run_bench(["--steps", "2", "--warmup", "1"], timeout=1500)
+    c, d, out = run_bench(["--full", "--steps", "2", "--warmup", "1"], timeout=1500)
     assert c["steps"] == 2 and c["warmup"] == 1 and c["n_gpus"] == 1 and c["value"] > 0 and c["config"]["name"] == "c3"
     r = c["roofline"]
     assert r["bound"] in ("hbm", "ta", "valu", "l1") and r["kernel"].startswith("raymarch_kernel") and r["kernel_ms"] > 0 and r["algorithmic_bytes_per_launch"] > 1e9

@@ -26,7 +26,8 @@ for part in $parts; do
   default)
     # the DEFAULT command as the driver runs it (every leg), under rocprofv3 --kernel-trace --stats: the stdout line, the detail record and the per-kernel statistics
     mkdir -p gpurun_out/prof_r05_default_cmd
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r05_default_cmd/stats -- python3 bench.py --steps 20 --warmup 5 --detail-file gpurun_out/prof_r05_default_cmd/bench_detail.json > gpurun_out/prof_r05_default_cmd/bench_stdout.json 2> gpurun_out/prof_r05_default_cmd/stats.log
+    d=$_   # the directory made on the line above
+    rocprofv3 --kernel-trace --stats --output-format csv -d $d/stats -- python3 bench.py --full --steps 20 --warmup 5 --detail-file $d/bench_detail.json > $d/bench_stdout.json 2> $d/stats.log
     for f in $(find gpurun_out/prof_r05_default_cmd/stats -name "*kernel_stats.csv" | head -1); do cp $f gpurun_out/prof_r05_default_cmd/kernel_stats.csv; done
     rm -rf gpurun_out/prof_r05_default_cmd/stats
     wc -c gpurun_out/prof_r05_default_cmd/bench_stdout.json; head -5 gpurun_out/prof_r05_default_cmd/kernel_stats.csv | cut -c1-200 ;;

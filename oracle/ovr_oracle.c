@@ -412,6 +412,16 @@ int ovr_oracle_literals(double* out, int capacity)
   return n;
 }
 
+/* The light is a literal of the reference (params.h:79), not an input.  tests/test_oracle_vs_ref_march.py replaces it to prove that its
+ * comparison with the reference's frames notices a misread component; NULL restores the literal.  Process-wide, like the pow mode. */
+static float g_light[3] = { LIT_LIGHT_X, LIT_LIGHT_Y, LIT_LIGHT_Z };
+void ovr_oracle_set_light_for_selfcheck(const float v[3])
+{
+  g_light[0] = v ? v[0] : LIT_LIGHT_X;
+  g_light[1] = v ? v[1] : LIT_LIGHT_Y;
+  g_light[2] = v ? v[2] : LIT_LIGHT_Z;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* per-frame constants                                                                               */
 /* ------------------------------------------------------------------------------------------------ */
@@ -467,7 +477,7 @@ static void make_frame_consts(const ovr_oracle_scene* s, frame_consts* fc)
   fc->wtc_it[0] = m0.x; fc->wtc_it[1] = m0.y; fc->wtc_it[2] = m0.z; /* column vx of the normal matrix */
   fc->wtc_it[3] = m1.x; fc->wtc_it[4] = m1.y; fc->wtc_it[5] = m1.z; /* column vy */
   fc->wtc_it[6] = m2.x; fc->wtc_it[7] = m2.y; fc->wtc_it[8] = m2.z; /* column vz */
-  fc->light = v3_normalize(v3_make(LIT_LIGHT_X, LIT_LIGHT_Y, LIT_LIGHT_Z)); /* params.h:79 */
+  fc->light = v3_normalize(v3_make(g_light[0], g_light[1], g_light[2])); /* params.h:79 */
 }
 
 /* xfmVector(M, a) = madd(a.x, vx, madd(a.y, vy, a.z*vz))  LinearSpace.h:320 */

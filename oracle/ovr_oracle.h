@@ -109,6 +109,8 @@ typedef struct ovr_oracle_counters {
  * epsilon, the light, the shading terms, TEA's rounds / constants / scale, float_small / float_large), in the order of oracle.py::LITERAL_NAMES; returns how many.
  * Pinned against the reference's source text: tests/golden/ref_literals.json (extracted from the cited lines by tests/golden/make_ref_literals.py) */
 int ovr_oracle_literals(double* out, int capacity);
+/* replaces the light literal (a self-check of the comparison against the reference's frames uses it); NULL restores it */
+void ovr_oracle_set_light_for_selfcheck(const float v[3]);
 
 /* ovr/common/random/random.h:146-188 - two floats from 16 TEA rounds; state is updated in place */
 void ovr_oracle_tea_floats(uint32_t* v0, uint32_t* v1, float out[2]);

@@ -19,7 +19,10 @@ def _normalize(v):
 class Spec:
     """SURVEY.md Appendix A, cell-centred convention, spp = 1, no accumulation"""
 
-    def __init__(self, vol, colors, alphas, vr, cam, size, fovy, rate, shading, origin=(0, 0, 0), spacing=(1, 1, 1)):
+    def __init__(self, vol, colors, alphas, vr, cam, size, fovy, rate, shading, origin=(0, 0, 0), spacing=(1, 1, 1), basis=None):
+        """basis: the camera as the marcher is handed it - position, direction, horizontal, vertical, 12 float32 values the HOST computes and
+        stores in the launch parameters (device_impl.cpp:125-144).  They are input data of the shader this class specifies, not part of its
+        arithmetic; without them the basis is derived from `cam` in float64, which differs from the stored floats in their last bits."""
         self.vol = vol.astype(np.float64)
         if vol.dtype == np.uint8:
             self.vol /= 255.0
@@ -38,6 +41,9 @@ class Spec:
         self.Hh = t * aspect * _normalize(np.cross(self.D, up))
         self.Vv = np.cross(self.Hh, self.D) / aspect
         self.org = eye
+        if basis is not None:
+            b = np.asarray(basis, np.float32).astype(np.float64)
+            self.org, self.D, self.Hh, self.Vv = b[0:3], b[3:6], b[6:9], b[9:12]
         self.scale = np.array(spacing, np.float64) * self.dims
         self.origin = np.array(origin, np.float64)
         self.step = 1.0 / rate

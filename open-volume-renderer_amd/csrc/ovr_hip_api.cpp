@@ -519,8 +519,8 @@ void update_tfn_range(ovr_hip_renderer* r)
     P.tf_lower = integer_normalize(t.lo, dt);
   }
   // a degenerate range (upper == lower: a constant volume under the data-range fallback) gives the reference scale = inf and the
-  // coordinate clamp01((lower - lower) * inf) = clamp01(NaN) = 0 for every sample; scale = 0 yields the same 0 without the NaN, which
-  // the shadow march's transfer-function lookup (tf_alpha2: no clamp) relies on
+  // coordinate clamp01((lower - lower) * inf) = clamp01(NaN) = 0 for every sample; scale = 0 yields the same 0 without a NaN
+  // ever reaching a transfer-function lookup
   P.tf_scale = P.tf_upper == P.tf_lower ? 0.f : 1.f / (P.tf_upper - P.tf_lower);
 }
 

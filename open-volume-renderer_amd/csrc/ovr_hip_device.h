@@ -138,39 +138,23 @@ typedef unsigned char u8x2_u __attribute__((ext_vector_type(2), aligned(1)));
 typedef signed char i8x2_u __attribute__((ext_vector_type(2), aligned(1)));
 
 template <int VT> struct Vox;
-// f32 brick shape (experiment switches; the default is what the A/B runs of profiles/r02_notes.md keep)
-#ifndef OVR_F32_CX
-#define OVR_F32_CX 3
-#define OVR_F32_MBX 10
-#define OVR_F32_BY 2
-#define OVR_F32_BZ 1
-#endif
+// (the f32 brick shape is what the A/B runs of profiles/r02_notes.md keep)
 template <> struct Vox<VOX_F32> {
   typedef float T; typedef f32x2_u P;
-  static constexpr int cx = OVR_F32_CX, mbx = OVR_F32_MBX, by = OVR_F32_BY, bz = OVR_F32_BZ; // cells per brick in x, bricks per macro block in x, log2 brick y/z
+  static constexpr int cx = 3, mbx = 10, by = 2, bz = 1; // cells per brick in x, bricks per macro block in x, log2 brick y/z
   static constexpr bool kScale = false, kClamp = false;
   static constexpr bool kTransposed = false;
   static constexpr bool kQuad = false;
 };
-#ifndef OVR_U16_CX
-#define OVR_U16_CX 3
-#define OVR_U16_MBX 10
-#define OVR_U16_BY 2
-#define OVR_U16_BZ 2
-#endif
 template <> struct Vox<VOX_U16> {
   typedef unsigned short T; typedef u16x2_u P;
-  static constexpr int cx = OVR_U16_CX, mbx = OVR_U16_MBX, by = OVR_U16_BY, bz = OVR_U16_BZ;
+  static constexpr int cx = 3, mbx = 10, by = 2, bz = 2;
   static constexpr bool kScale = false, kClamp = false; // u16 is sampled as RAW float (array.cpp:335-338)
   static constexpr bool kTransposed = false;
   static constexpr bool kQuad = false;
 };
 // Thin replicas (view-dependent layout choice, see VoxelType in ovr_hip_kernels.h): 1 cell + apron along the pair axis, 4 x 4
 // (f32) or 4 x 8 (u16) voxels across.  *_TT is stored with x and y exchanged, so its pair axis is the volume's y.
-#ifndef OVR_U16T_BY
-#define OVR_U16T_BY 2
-#define OVR_U16T_BZ 3
-#endif
 template <> struct Vox<VOX_F32_T> {
   typedef float T; typedef f32x2_u P;
   static constexpr int cx = 1, mbx = 32, by = 2, bz = 2;
@@ -181,7 +165,7 @@ template <> struct Vox<VOX_F32_T> {
 template <> struct Vox<VOX_F32_TT> : Vox<VOX_F32_T> { static constexpr bool kTransposed = true; };
 template <> struct Vox<VOX_U16_T> {
   typedef unsigned short T; typedef u16x2_u P;
-  static constexpr int cx = 1, mbx = 32, by = OVR_U16T_BY, bz = OVR_U16T_BZ;
+  static constexpr int cx = 1, mbx = 32, by = 2, bz = 3;
   static constexpr bool kScale = false, kClamp = false;
   static constexpr bool kTransposed = false;
   static constexpr bool kQuad = false;
@@ -361,23 +345,21 @@ __device__ __forceinline__ unsigned int tap_cell(const VolConsts& vc, const Tap&
 // bytes or more: a 64-lane gather whose quads each stay inside one line costs 18 clocks as dwordx2 / dwordx4 and 66 - as if every lane had a
 // line of its own - as dword or ushort, whatever the alignment (tools/ubench_align.hip, profiles/r05_notes.md section 10; a dwordx2 at a 4-byte
 // boundary - the 32-bit bricks' odd pairs - costs the 18; dwords merge only when the quad's four are consecutive).  The 16-bit layouts' pairs are
-// 4 bytes: OVR_ROW_LOADS loads the ALIGNED 8 bytes around the pair (a brick row of the general layout, two rows of a thin replica) and shifts the
+// 4 bytes: the row loads (RowLoads) read the ALIGNED 8 bytes around the pair (a brick row of the general layout, two rows of a thin replica) and shift the
 // pair out of them - the same voxels, so the same frame.  C4: shade 3.21 -> 2.87 ms, frame 7.5 -> 7.2 ms; front view (thin replica) 3.57 -> 3.29;
 // a 512^3 u16 volume at 512^2 0.353 -> 0.335; the 8-bit layouts' 2-byte pairs likewise (a 1024^3 u8 volume at C3's settings 1.80 -> 1.70 ms, front view 1.085 ->
 // 0.97) - where the layout is large: C1 (256^3 u8) is bound by vector issue and the shifts cost it 3 % (0.183 -> 0.188 ms), see RowLoads.
-#ifndef OVR_ROW_LOADS
-#define OVR_ROW_LOADS 1
-#endif
 // Which launches take the row loads: the 16-bit and 8-bit volumes whose layout is too large for the caches to serve (addressing modes 1 and 2, and mode 4 = mode 0's
 // 32-bit byte offsets + row loads: launch_vs upgrades a 16-bit or 8-bit layout of more than 128 MB).  Small 16-bit volumes are bound by vector issue and keep the
 // 4-byte loads (a 256 x 256 x 226 u16 volume, all samples shaded in place: 0.88 -> 1.08 ms WITH the row loads; the 1024 x 1024 x 1080 one 34 -> 24 ms).
-template <int VT, int AM> struct RowLoads { static constexpr bool on = OVR_ROW_LOADS && sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad && (AM == 1 || AM == 2 || AM == 4); };
+template <int VT, int AM> struct RowLoads { static constexpr bool on = sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad && (AM == 1 || AM == 2 || AM == 4); };
 template <int VT, int AM, typename B>
 __device__ __forceinline__ typename Vox<VT>::P load_pair(const B* base, unsigned long long off) // off in units of B (bytes for char, else elements)
 {
   typedef typename Vox<VT>::T T;
   typedef typename Vox<VT>::P P;
   if constexpr (RowLoads<VT, AM>::on) {
+    static_assert(BrickMap<VT>::SX * sizeof(T) <= 8, "row loads: a pair must not cross its aligned 8 bytes, so a brick row is at most 8 bytes");
     constexpr unsigned per = 8u / (unsigned)sizeof(B);                 // units of B per 8 bytes
     const unsigned long long al = off & ~(unsigned long long)(per - 1u);
     const unsigned sh = ((unsigned)off & (per - 1u)) * (8u * (unsigned)sizeof(B));
@@ -473,9 +455,6 @@ __device__ __forceinline__ void tap_loads(const VolConsts& vc, Tap& t)
       p01 = load_pair<VT, AM>(cb, (unsigned long long)(oz1 + o0)); p11 = load_pair<VT, AM>(cb, (unsigned long long)(oz1 + o1));
     }
   }
-#ifdef OVR_EXP_HALF_LOADS /* timing experiment only (wrong pictures): what would half the gather instructions buy? */
-  p10 = p00; p11 = p01;
-#endif
   // p(b, c) = the pair along a at (b0 + b, z0 + c); the corners keep their volume-axis names, so the lerp order (x, then y,
   // then z) and with it every bit of the result is the same for every layout
   if (!TR) {
@@ -526,138 +505,9 @@ __device__ __forceinline__ float sample_volume(const VolConsts& vc, f3 p)
   return tap_finish<VT>(vc, t);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// Quad-cooperative taps (round 5).  The texture addresser works through a gather quad by quad - 4 consecutive lanes - and a quad costs by the
-// number of 128-byte lines its lanes touch: 1.1 clocks for one line, 2.8 for two, 4.4 for four (tools/ubench_align.hip, 8-byte loads).  In the
-// shade kernel a quad is 4 consecutive steps of one primary ray; when every lane loads the pairs of its OWN tap, one instruction reads pair j of
-// four taps that lie 1 voxel apart along the view direction - 2.7 bricks on the oblique view (3 x 4 x 2 cells a brick).  Transposed: instruction i
-// reads the FOUR pairs of request i's tap, lane j the pair j = (y0 + (j & 1), z0 + (j >> 1)) - one tap's pairs share a brick unless the tap
-// straddles a y or z face: 1.9 lines (1.6 for the 16-bit bricks).  The lerps follow the data: lane j lerps its pair along x, the even lanes along
-// y with their neighbour's value, lane 0 along z, and lane i takes the result of request i - the same fma of the same operands as tap_finish
-// (lerp(a, b, f) = fma(f, b - a, a), x then y then z), so frames stay bit-identical, with 6 instead of 7 x 2 lerp instructions per tap and lane.
-// All 4 lanes of a quad must be active around these calls (the callers enter per quad, with a per-lane `use` flag).
-// Not for the transposed and quad replicas (their pair axis / cell differs) and not without LDS tables (addressing mode 3): those keep tap_loads.
-// MEASURED (profiles/r05_notes.md section 11): bit-identical (211 parity tests with it on) and SLOWER - C3 shade 0.92 -> 1.08 ms, C4 2.85 -> 3.38, C5 2.80 ->
-// 3.53: the transposition is paid in vector instructions.  Per tap and lane the addresses take 12 v_mov_dpp + 12 v_lshl_add + 12 ds_read_b32 (each lane
-// looks up the table entries of FOUR taps) where the own tap took 3 + 3 + 6 adds, and the lerps 12 instructions per request (the weights' broadcasts are not
-// folded into v_fmac as DPP operands, the final select branches): 2339 instead of 1545 vector instructions in the kernel, and the shade kernel was at 0.58 of
-// vector issue before.  What the texture addresser saves the ALUs spend.  Off; a transposition through LDS (ds_write_b64 x 4 / ds_read_b128 x 2 per tap, no
-// vector instructions) is the untried alternative - it would put the LDS pipe at ~50-70 clocks per wave and tap beside the addresser's 100-150.
-// ------------------------------------------------------------------------------------------------------------------
-#ifndef OVR_COOP_TAPS
-#define OVR_COOP_TAPS 0
-#endif
-template <int VT, int AM> struct Coop { static constexpr bool ok = OVR_COOP_TAPS && !Vox<VT>::kQuad && !Vox<VT>::kTransposed && AM != 3; };
-template <int B> __device__ __forceinline__ int qb_i(int x) { return __builtin_amdgcn_update_dpp(0, x, B * 0x55, 0xf, 0xf, true); } // lane B of the quad
-template <int B> __device__ __forceinline__ float qb_f(float x) { return __int_as_float(qb_i<B>(__float_as_int(x))); }
-template <int CTRL> __device__ __forceinline__ float qperm_f(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true)); }
-
-// lane `sub` of the quad loads pair (sub & 1, sub >> 1) of the tap of the quad's lane I (its corner t.x0 / y0 / z0); use == 0: the tap is not
-// wanted - the four lanes read the volume's first bytes instead (one hot line)
-template <int VT, int AM, int I>
-__device__ __forceinline__ typename Vox<VT>::P coop_load(const VolConsts& vc, const Tap& t, int use, int sub)
-{
-  typedef typename Vox<VT>::T T;
-  const int xi = qb_i<I>(t.x0), yi = qb_i<I>(t.y0) + (sub & 1), zi = qb_i<I>(t.z0) + (sub >> 1);
-  const unsigned int m = (unsigned int)qb_i<I>(use);
-  const unsigned int oxy = vc.tab_x[xi] + vc.tab_y[yi];
-  if (AM == 2) {
-    const unsigned long long off = (vc.tab_z64[zi] + oxy) & (((unsigned long long)m << 32) | m);
-    return load_pair<VT, AM>(static_cast<const T*>(vc.data), off);
-  }
-  const unsigned int off = (vc.tab_z[zi] + oxy) & m;
-  if (AM == 1) return load_pair<VT, AM>(static_cast<const T*>(vc.data), (unsigned long long)off);
-  return load_pair<VT, AM>(static_cast<const char*>(vc.data), (unsigned long long)off);
-}
-// the value of request I's tap from the four lanes' pairs; returned in every lane of the quad (fx / fy / fz: the OWN tap's weights of each lane)
-template <int VT, int I>
-__device__ __forceinline__ float coop_lerp(const VolConsts& vc, typename Vox<VT>::P p, float fx, float fy, float fz)
-{
-  float lo = (float)p.x, hi = (float)p.y;
-#if OVR_PARITY_EXACT
-  if (Vox<VT>::kScale) { lo = Vox<VT>::kClamp ? fmaxf(lo / 127.f, -1.f) : lo / 255.f; hi = Vox<VT>::kClamp ? fmaxf(hi / 127.f, -1.f) : hi / 255.f; }
-#else
-  if (Vox<VT>::kClamp) { lo = fmaxf(lo, vc.vmin); hi = fmaxf(hi, vc.vmin); }
-#endif
-  const float cx = fmaf(qb_f<I>(fx), hi - lo, lo);                       // lane j: c(y_j, z_j) = lerp along x
-  const float cy = fmaf(qb_f<I>(fy), qperm_f<0xB1>(cx) - cx, cx);        // lanes 0, 2: lerp(c(y0, z), c(y1, z), fy)   (quad_perm 1,0,3,2)
-  float cz = fmaf(qb_f<I>(fz), qperm_f<0x4E>(cy) - cy, cy);              // lane 0: lerp(c(z0), c(z1), fz)               (quad_perm 2,3,0,1)
-  if (Vox<VT>::kScale && !OVR_PARITY_EXACT) cz *= vc.vscale;
-  return qb_f<0>(cz);
-}
-// one tap per lane of the quad, all four in flight: issue, then finish (own result per lane; garbage where use == 0)
-template <int VT, int AM>
-struct CoopTap {
-  typename Vox<VT>::P p[4];
-  float fx, fy, fz;
-  __device__ __forceinline__ void issue(const VolConsts& vc, const Tap& t, int use, int sub)
-  {
-    fx = t.fx; fy = t.fy; fz = t.fz;
-    p[0] = coop_load<VT, AM, 0>(vc, t, use, sub); p[1] = coop_load<VT, AM, 1>(vc, t, use, sub);
-    p[2] = coop_load<VT, AM, 2>(vc, t, use, sub); p[3] = coop_load<VT, AM, 3>(vc, t, use, sub);
-  }
-  __device__ __forceinline__ float finish(const VolConsts& vc, int sub) const
-  {
-    const float s0 = coop_lerp<VT, 0>(vc, p[0], fx, fy, fz), s1 = coop_lerp<VT, 1>(vc, p[1], fx, fy, fz);
-    const float s2 = coop_lerp<VT, 2>(vc, p[2], fx, fy, fz), s3 = coop_lerp<VT, 3>(vc, p[3], fx, fy, fz);
-    return sub == 0 ? s0 : sub == 1 ? s1 : sub == 2 ? s2 : s3;
-  }
-};
-
-// ------------------------------------------------------------------------------------------------------------------
-// packed FP32: two taps of ONE lane side by side in 64-bit register pairs (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: each half
-// is the IEEE operation of the scalar instruction, so results are bit-identical to the scalar form).  Measured issue cost relative
-// to v_fma_f32 (tools/ubench_valu.hip): v_pk_fma_f32 1.3 for two fmas, v_pk_add / v_pk_mul 1.1 for two.  Only what is naturally
-// a pair is packed: the loaded voxel pairs are (x, x+1) of one brick row - their x-lerp needs hi - lo of ONE register pair, which a
-// packed instruction cannot do without moves (the compiler's own SLP packing of those lerps costs 3 v_mov per 2 lerps: the
-// library is built with -fno-slp-vectorize) - so the x-lerps stay scalar and write their results side by side for the packed y / z lerps.
-// ------------------------------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 mk2(float a, float b) { f2 r; r.x = a; r.y = b; return r; }
-__device__ __forceinline__ f2 splat2(float a) { return mk2(a, a); }
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 lerp2(f2 a, f2 b, f2 f) { return fma2(f, b - a, a); }
-
-// axis_tap for two taps.  The clamp of p to [0, 1] (sample_volume_object_space) is applied to x instead: x = fma(p, cs, cb) is monotone
-// in p (cs > 0), p = 0 maps to cb and p = 1 to cs + cb (exact: n - 0.5 or n - 1), so clamping x to [cb, cs + cb] gives the value clamping p
-// first gives, for every p (NaN -> cb either way: clamp01(NaN) = 0 -> cb, and med3(NaN, cb, cs + cb) = cb)
-// a * sc.x + sc.y on both halves; sc = (scale, offset) lives in one register pair whose halves the instruction broadcasts (op_sel)
-__device__ __forceinline__ f2 fma2_sc(f2 a, f2 sc) { return fma2(a, __builtin_shufflevector(sc, sc, 0, 0), __builtin_shufflevector(sc, sc, 1, 1)); }
-__device__ __forceinline__ void axis_tap2(f2 po, f2 csb, int& ia, int& ib, float& fa, float& fb)
-{
-  const f2 x = fma2_sc(po, csb);
-  const float hi = csb.x + csb.y;
-  const float xa = clampf(x.x, csb.y, hi), xb = clampf(x.y, csb.y, hi);
-  fa = __builtin_amdgcn_fractf(xa); ia = floor_to_int(xa);
-  fb = __builtin_amdgcn_fractf(xb); ib = floor_to_int(xb);
-}
-__device__ __forceinline__ void tap_coords2(const VolConsts& vc, f2 px, f2 py, f2 pz, f2 cx, f2 cy, f2 cz, Tap& a, Tap& b)
-{
-  axis_tap2(px, cx, a.x0, b.x0, a.fx, b.fx);
-  axis_tap2(py, cy, a.y0, b.y0, a.fy, b.fy);
-  axis_tap2(pz, cz, a.z0, b.z0, a.fz, b.fz);
-}
-// tap_finish for two taps: 8 scalar x-lerps, then the y and z lerps of both taps packed (6 instructions instead of 12)
-template <int VT>
-__device__ __forceinline__ f2 tap_finish2(const VolConsts& vc, Tap a, Tap b)
-{
-#if OVR_PARITY_EXACT
-  return mk2(tap_finish<VT>(vc, a), tap_finish<VT>(vc, b));
-#endif
-  if (Vox<VT>::kClamp) {
-    a.c000 = fmaxf(a.c000, vc.vmin); a.c100 = fmaxf(a.c100, vc.vmin); a.c010 = fmaxf(a.c010, vc.vmin); a.c110 = fmaxf(a.c110, vc.vmin);
-    a.c001 = fmaxf(a.c001, vc.vmin); a.c101 = fmaxf(a.c101, vc.vmin); a.c011 = fmaxf(a.c011, vc.vmin); a.c111 = fmaxf(a.c111, vc.vmin);
-    b.c000 = fmaxf(b.c000, vc.vmin); b.c100 = fmaxf(b.c100, vc.vmin); b.c010 = fmaxf(b.c010, vc.vmin); b.c110 = fmaxf(b.c110, vc.vmin);
-    b.c001 = fmaxf(b.c001, vc.vmin); b.c101 = fmaxf(b.c101, vc.vmin); b.c011 = fmaxf(b.c011, vc.vmin); b.c111 = fmaxf(b.c111, vc.vmin);
-  }
-  const f2 c00 = mk2(lerpf(a.c000, a.c100, a.fx), lerpf(b.c000, b.c100, b.fx)), c10 = mk2(lerpf(a.c010, a.c110, a.fx), lerpf(b.c010, b.c110, b.fx));
-  const f2 c01 = mk2(lerpf(a.c001, a.c101, a.fx), lerpf(b.c001, b.c101, b.fx)), c11 = mk2(lerpf(a.c011, a.c111, a.fx), lerpf(b.c011, b.c111, b.fx));
-  const f2 fy = mk2(a.fy, b.fy), fz = mk2(a.fz, b.fz);
-  const f2 c0 = lerp2(c00, c10, fy), c1 = lerp2(c01, c11, fy);
-  f2 s = lerp2(c0, c1, fz);
-  if (Vox<VT>::kScale) s = s * splat2(vc.vscale);
-  return s;
-}
+// (Quad-cooperative taps - one instruction reading the four pairs of ONE tap, the lerps following the data through DPP - were measured bit-identical and
+// slower: C3 shade 0.92 -> 1.08 ms, the transposition is paid in vector instructions; profiles/r05_notes.md section 11.  Packed-FP32 lerps
+// (v_pk_fma_f32) likewise cost more issue slots than the scalar v_sub + v_fmac pairs; profiles/r03_notes.md.)
 
 // ------------------------------------------------------------------------------------------------------------------
 // transfer function in LDS (or global when it does not fit)
@@ -695,20 +545,6 @@ __device__ __forceinline__ f3 tf_color(const TfConsts& tf, float v)
   const float f = __builtin_amdgcn_fractf(x);
   const float4 a = tf.color[i0], b = tf.color[i0 + 1];
   return mk3(lerpf(a.x, b.x, f), lerpf(a.y, b.y, f), lerpf(a.z, b.z, f));
-}
-
-// opacity of two samples: tf_coord + tf_alpha packed.  Two of the scalar form's instructions per sample are dropped without changing a bit:
-//  * the clamp of the coordinate to [0, 1]: v = (clamp(s, lower, upper) - lower) * scale is never negative and exceeds 1 by at most a
-//    rounding step; such a v indexes the table's last entry with a small fraction, and the entry after the last is a copy of the
-//    last (stage_tf), so the lerp returns A[n - 1] exactly as v = 1 does (update_tfn_range keeps scale finite);
-//  * min(i0 + 1, n - 1): the same copy makes (i0, i0 + 1) clamp-to-edge, and the two entries arrive with one ds_read2_b32.
-__device__ __forceinline__ f2 tf_alpha2(const TfConsts& tf, f2 s)
-{
-  const f2 sc = mk2(fminf(fmaxf(s.x, tf.lower), tf.upper), fminf(fmaxf(s.y, tf.lower), tf.upper));
-  const f2 x = ((sc - splat2(tf.lower)) * splat2(tf.scale)) * splat2(tf.fna1);
-  const int ia = (int)x.x, ib = (int)x.y;
-  const float a0 = tf.alpha[ia], a1 = tf.alpha[ia + 1], b0 = tf.alpha[ib], b1 = tf.alpha[ib + 1];
-  return mk2(lerpf(a0, a1, __builtin_amdgcn_fractf(x.x)), lerpf(b0, b1, __builtin_amdgcn_fractf(x.y)));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -785,10 +621,9 @@ __device__ __forceinline__ bool pixel_ray_hits_box(const RayMarchParams& P, cons
 // (4^3 macrocells = 64 voxels per entry), FINE = true: one entry per macrocell (16 voxels); both are dilated by one macrocell.
 // Sample coordinates: x = p * cs + cb (tap_coords), macrocell = (floor(x) + 1) >> 4 (tap_cell), i.e. the regular 16-voxel
 // grid in w = x + 1.
-// Round 3 - any number of occupied intervals per ray: besides the hull [first, last] the fine walk of a primary ray marks, in a 64-bit mask,
-// which of 64 equal segments of the span [seg0, seg0 + 64 / seg_scale] it walked (the coarse hull) meet a set entry (one segment of
-// margin on either side).  A round of the march whose t range touches no marked segment lies in empty macrocells although it is inside the
-// hull - interior voids take the 45-instruction bulk path too (accel/dda.h walks such gaps cell by cell for the reference's path tracer).
+// Besides the hull [first, last] a span carries a 64-bit mask over 64 equal segments of [seg0, seg0 + 64 / seg_scale].  Nothing refines the mask any
+// more (the segment walker that did was measured 2-4 % slower on every bench configuration, profiles/r03_notes.md): it is all set or all clear.  Its
+// fields and tests stay because removing them changes the skipping kernels' code - that waits for a change that is measured.
 struct SkipSpan {
   float first, last;            // hull: every sample outside it lies in a macrocell with majorant 0
   float seg0, seg_scale;        // segment i covers t in [seg0 + i / seg_scale, seg0 + (i + 1) / seg_scale)
@@ -814,9 +649,8 @@ __device__ __forceinline__ bool skipspan_touches(const SkipSpan& s, float ta, fl
   return (m & range) != 0ull;
 }
 
-template <bool FINE, bool MARK = false>
-__device__ __forceinline__ void skip_walk(const VolConsts& vc, f3 oo, f3 od, float ta, float tb, float& first, float& last, float seg0 = 0.f, float seg_scale = 0.f,
-                                          unsigned long long* mask = nullptr)
+template <bool FINE>
+__device__ __forceinline__ void skip_walk(const VolConsts& vc, f3 oo, f3 od, float ta, float tb, float& first, float& last)
 {
   const float w0[3] = { fmaf(oo.x, vc.cs.x, vc.cb.x + 1.f), fmaf(oo.y, vc.cs.y, vc.cb.y + 1.f), fmaf(oo.z, vc.cs.z, vc.cb.z + 1.f) };
   const float dw[3] = { od.x * vc.cs.x, od.y * vc.cs.y, od.z * vc.cs.z };
@@ -840,13 +674,7 @@ __device__ __forceinline__ void skip_walk(const VolConsts& vc, f3 oo, f3 od, flo
     const bool occ = grid[(size_t)ci[0] + (size_t)(m1[0] + 1) * ((size_t)ci[1] + (size_t)(m1[1] + 1) * (size_t)ci[2])] != 0;
     const int ax = (tmax[0] <= tmax[1]) ? (tmax[0] <= tmax[2] ? 0 : 2) : (tmax[1] <= tmax[2] ? 1 : 2);
     const float tn = ax == 0 ? tmax[0] : ax == 1 ? tmax[1] : tmax[2];
-    if (occ) {
-      first = fminf(first, t); last = fmaxf(last, fminf(tn, tb));
-      if (MARK) {
-        const int lo = max((int)((t - seg0) * seg_scale) - 1, 0), hi = min((int)((fminf(tn, tb) - seg0) * seg_scale) + 1, 63);
-        if (hi >= lo) *mask |= (hi >= 63 ? ~0ull : ((2ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
-      }
-    }
+    if (occ) { first = fminf(first, t); last = fmaxf(last, fminf(tn, tb)); }
     t = fmaxf(t, tn);
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -856,7 +684,7 @@ __device__ __forceinline__ void skip_walk(const VolConsts& vc, f3 oo, f3 od, flo
         else { ci[k] = nxt; tmax[k] += tdel[k]; }
       }
   }
-  if (t < tb) { first = fminf(first, t); last = tb; if (MARK) *mask = ~0ull; } // safety limit hit (never expected): treat the rest as occupied
+  if (t < tb) { first = fminf(first, t); last = tb; } // safety limit hit (never expected): treat the rest as occupied
 }
 
 // raymarching_shadow, shaders_raymarching.cu:44-85 (+ :205-229): alpha-only march toward the light.
@@ -915,157 +743,12 @@ __device__ __forceinline__ float march_shadow(const VolConsts& vc, const TfConst
       // serialise the taps again (seen in the ISA); dead lanes just compute a value that is not used
       const float s = tap_finish<VT>(vc, taps[k]);
       float a = tf_alpha(tf, tf_coord(tf, s));
-#ifndef OVR_SHADOW_BF
-#define OVR_SHADOW_BF 0 /* branch-free opacity correction in the plain shadow march too (measurement switch) */
-#endif
-      a = opacity_correction<SKIP || OVR_SHADOW_BF>(a, mc.base * dts[k]);
+      a = opacity_correction<SKIP>(a, mc.base * dts[k]);
       if (SKIP) a = mj[k] > 0.f ? a : 0.f; // a macrocell whose majorant is 0 holds no sample with opacity > 0
       live = live && valid[k] && (alpha < 0.9999f);
       alpha = live ? fmaf(1.f - alpha, a, alpha) : alpha;
       n_shadow += (live && (!SKIP || mj[k] > 0.f)) ? 1u : 0u;
       if (SKIP) n_shadow_skipped += (live && !(mj[k] > 0.f)) ? 1u : 0u;
-    }
-  }
-  return alpha;
-}
-
-// The same march with quad-cooperative taps (CoopTap): entered by all 4 lanes of a quad with a request to shade in any of them (`want`: this
-// lane's own), left when none of the quad's rays is live any more; a lane whose ray has ended keeps loading its share of the others' taps.
-template <int VT, int AM, int KS, bool SKIP>
-__device__ __forceinline__ float march_shadow_coop(const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, f3 org, bool want, unsigned int& n_shadow,
-                                                   unsigned int& n_shadow_skipped)
-{
-  const int sub = (int)(threadIdx.x & 3u);
-  const unsigned int qshift = threadIdx.x & 60u; // first lane of the quad within the wave
-  const f3 oo = to_object(mc, org);
-  const f3 od = mk3(mc.light.x * mc.inv_scale.x, mc.light.y * mc.inv_scale.y, mc.light.z * mc.inv_scale.z);
-  float t0 = 0.f, t1 = FLT_MAX;
-  float alpha = 0.f;
-  bool live = intersect_unit_box(t0, t1, oo, od) && want;
-  float tx = t0, ty = fminf(t1, t0 + mc.shadow_stride);
-  float skip_first = FLT_MAX, skip_last = -FLT_MAX;
-  if (SKIP && live) skip_walk<false>(vc, oo, od, t0, t1, skip_first, skip_last);
-  for (;;) {
-    if (((unsigned int)(__ballot(live) >> qshift) & 0xfu) == 0u) break; // no live ray in this quad
-    Tap taps[KS];
-    float dts[KS], mj[KS];
-    bool valid[KS];
-    bool any_inside = false;
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      valid[k] = ty > tx;
-      dts[k] = ty - tx;
-      const float tm = 0.5f * (tx + ty);
-      const bool inside = live && (!SKIP || (tm >= skip_first && tm <= skip_last));
-      taps[k] = Tap{};
-      mj[k] = SKIP ? 0.f : 1.f;
-      if (inside || !SKIP) {
-        const f3 pos = mk3(fmaf(tm, mc.light.x, org.x), fmaf(tm, mc.light.y, org.y), fmaf(tm, mc.light.z, org.z));
-        tap_coords(vc, to_object(mc, pos), taps[k]);
-        if (SKIP) mj[k] = vc.majorant[tap_cell(vc, taps[k])]; // empty-space skipping: max TF opacity of the macrocell
-      }
-      any_inside = any_inside || (live && mj[k] > 0.f);
-      tx = ty;
-      ty = fminf(tx + mc.shadow_stride, t1);
-    }
-    if (SKIP && __ballot(any_inside) == 0ull) { // nothing to fetch for any lane of the wave: bookkeeping only
-#pragma unroll
-      for (int k = 0; k < KS; ++k) {
-        live = live && valid[k] && (alpha < 0.9999f);
-        n_shadow_skipped += live ? 1u : 0u;
-      }
-      continue;
-    }
-    CoopTap<VT, AM> ct[KS];
-#pragma unroll
-    for (int k = 0; k < KS; ++k) ct[k].issue(vc, taps[k], (live && mj[k] > 0.f) ? -1 : 0, sub);
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const float s = ct[k].finish(vc, sub);
-      float a = tf_alpha(tf, tf_coord(tf, s));
-      a = opacity_correction<true>(a, mc.base * dts[k]);
-      if (SKIP) a = mj[k] > 0.f ? a : 0.f; // a macrocell whose majorant is 0 holds no sample with opacity > 0
-      live = live && valid[k] && (alpha < 0.9999f);
-      alpha = live ? fmaf(1.f - alpha, a, alpha) : alpha;
-      n_shadow += (live && (!SKIP || mj[k] > 0.f)) ? 1u : 0u;
-      if (SKIP) n_shadow_skipped += (live && !(mj[k] > 0.f)) ? 1u : 0u;
-    }
-  }
-  return alpha;
-}
-
-// The same march with its taps in pairs (packed FP32, see f2 above): the all-shaded frames - most of the reference's shipped scenes, and
-// every frame at the scene files' sampling rate 4 - are bound by this loop's instruction stream (profiles/r03_notes.md: VALU ~100 % busy).
-// Per pair of steps: positions, object coordinates and cell coordinates as 9 v_pk_fma_f32 (18 v_fma_f32 in the scalar form), the y / z lerps,
-// the transfer-function coordinate and the opacity correction's multiplies packed; the redundant clamps dropped (axis_tap2, tf_alpha2).
-// Every value is computed by the same IEEE operations in the same order as in march_shadow: bit-identical results.
-#ifndef OVR_SHADOW_PACKED
-#define OVR_SHADOW_PACKED 0
-#endif
-#ifndef OVR_PACKED_LERP
-#define OVR_PACKED_LERP 0
-#endif
-template <int VT, int AM, int KS>
-__device__ __forceinline__ float march_shadow_packed(const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, f3 org, unsigned int& n_shadow)
-{
-  static_assert(KS % 2 == 0, "taps come in pairs");
-  constexpr int KP = KS / 2;
-  const f3 oo = to_object(mc, org);
-  const f3 od = mk3(mc.light.x * mc.inv_scale.x, mc.light.y * mc.inv_scale.y, mc.light.z * mc.inv_scale.z);
-  float t0 = 0.f, t1 = FLT_MAX;
-  float alpha = 0.f;
-  if (!intersect_unit_box(t0, t1, oo, od)) return alpha;
-  float tx = t0, ty = fminf(t1, t0 + mc.shadow_stride);
-  bool live = true;
-  const f2 lx = splat2(mc.light.x), ly = splat2(mc.light.y), lz = splat2(mc.light.z);
-  const f2 ox = splat2(org.x), oy = splat2(org.y), oz = splat2(org.z);
-  // (scale, offset) of the two affine maps per axis, each pair in ONE 64-bit scalar register: a packed fma may read one scalar operand
-  const f2 wx = mk2(mc.inv_scale.x, mc.wto_p.x), wy = mk2(mc.inv_scale.y, mc.wto_p.y), wz = mk2(mc.inv_scale.z, mc.wto_p.z);
-  const f2 cx = mk2(vc.cs.x, vc.cb.x), cy = mk2(vc.cs.y, vc.cb.y), cz = mk2(vc.cs.z, vc.cb.z);
-  while (live) {
-    Tap taps[KS];
-    f2 dts[KP];
-    bool valid[KS];
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-      const float txa = tx, tya = ty;
-      tx = ty; ty = fminf(tx + mc.shadow_stride, t1);
-      const float txb = tx, tyb = ty;
-      tx = ty; ty = fminf(tx + mc.shadow_stride, t1);
-      valid[2 * p] = tya > txa; valid[2 * p + 1] = tyb > txb;
-      const f2 vtx = mk2(txa, txb), vty = mk2(tya, tyb);
-      dts[p] = vty - vtx;
-      const f2 tm = (vtx + vty) * splat2(0.5f);
-      // pos = org + tm * light; to_object (its clamp to [0, 1] is subsumed, axis_tap2); cell coordinates
-      const f2 px = fma2(tm, lx, ox), py = fma2(tm, ly, oy), pz = fma2(tm, lz, oz);
-      const f2 qx = fma2_sc(px, wx), qy = fma2_sc(py, wy), qz = fma2_sc(pz, wz);
-      tap_coords2(vc, qx, qy, qz, cx, cy, cz, taps[2 * p], taps[2 * p + 1]);
-    }
-#pragma unroll
-    for (int k = 0; k < KS; ++k) tap_loads<VT, AM>(vc, taps[k]);
-#pragma unroll
-    for (int p = 0; p < KP; ++p) {
-#if OVR_PACKED_LERP
-      const f2 s = tap_finish2<VT>(vc, taps[2 * p], taps[2 * p + 1]);
-#else
-      // the 7 lerps of a tap stay scalar: v_sub + v_fmac cost 1.4 v_fma_f32 issue slots, the packed pair 2.45 for two - and the pairs would
-      // have to be assembled with moves first (tools/ubench_valu.hip, profiles/r03_notes.md)
-      const f2 s = mk2(tap_finish<VT>(vc, taps[2 * p]), tap_finish<VT>(vc, taps[2 * p + 1]));
-#endif
-      const f2 a = tf_alpha2(tf, s);
-      // opacity correction (shaders_raymarching.cu:118-122), branch-free: both transcendentals always run (the shadow stride is never
-      // 1 / base in practice), the select keeps a exactly where the reference's branch does
-      const f2 adj = splat2(mc.base) * dts[p];
-      const f2 lg = mk2(__builtin_amdgcn_logf(1.f - a.x), __builtin_amdgcn_logf(1.f - a.y));
-      const f2 pl = adj * lg;
-      const float ca = clamp01(1.f - __builtin_amdgcn_exp2f(pl.x)), cb = clamp01(1.f - __builtin_amdgcn_exp2f(pl.y));
-      const float aa = (fabsf(adj.x - 1.f) < 1e-7f) ? a.x : ca, ab = (fabsf(adj.y - 1.f) < 1e-7f) ? a.y : cb;
-      live = live && valid[2 * p] && (alpha < 0.9999f);
-      alpha = live ? fmaf(1.f - alpha, aa, alpha) : alpha;
-      n_shadow += live ? 1u : 0u;
-      live = live && valid[2 * p + 1] && (alpha < 0.9999f);
-      alpha = live ? fmaf(1.f - alpha, ab, alpha) : alpha;
-      n_shadow += live ? 1u : 0u;
     }
   }
   return alpha;
@@ -1096,25 +779,13 @@ __device__ __forceinline__ float march_shadow_packed(const VolConsts& vc, const 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
-#ifndef OVR_SHADOW_K
-#define OVR_SHADOW_K 4
-#endif
-constexpr int kShadowTaps = OVR_SHADOW_K; // shadow-march taps in flight per lane
+constexpr int kShadowTaps = 4; // shadow-march taps in flight per lane
 // chunks a tile reserves at a time: consecutive chunks of one tile are shaded by ONE workgroup, one chunk per wave
 // (L1/L2 reuse: measured 2.4 -> 1.5 ms for the shading kernel at C3; 8 / 16 / 32 are slower - imbalance)
 constexpr int kRun = 4;
-#ifndef OVR_RUN_MAX
-#define OVR_RUN_MAX 16
-#endif
-#ifndef OVR_TICKET_RUNS
-#define OVR_TICKET_RUNS 8
-#endif
-constexpr int kTicketRuns = OVR_TICKET_RUNS; // shade kernel: most runs a workgroup takes per ticket
-#ifndef OVR_TICKET_BLOCK
-#define OVR_TICKET_BLOCK 8
-#endif
-constexpr unsigned int kTicketBlock = OVR_TICKET_BLOCK; // shade kernel: consecutive tickets that stay in one sub-pool
-constexpr int kRunMax = OVR_RUN_MAX; // largest reservation (a multiple of kRun: the shade kernel takes kRun chunks per workgroup)
+constexpr int kTicketRuns = 8; // shade kernel: most runs a workgroup takes per ticket
+constexpr unsigned int kTicketBlock = 8; // shade kernel: consecutive tickets that stay in one sub-pool
+constexpr int kRunMax = 16; // largest reservation (a multiple of kRun: the shade kernel takes kRun chunks per workgroup)
 
 struct ShadeReq { // 32 bytes; after shading the same slot holds the result (cx,cy,cz,gx,gy,gz,a,next)
   float px, py, pz; // world-space sample position          | colour contribution  tr*clamp01(rgb*shade)
@@ -1259,38 +930,21 @@ __device__ __forceinline__ void write_pixel(const RayMarchParams& P, unsigned in
 // shade one request: gradient (shaders_common.h:195-215), normals, shadow march, Lambert-ish term
 // (shaders_raymarching.cu:124-158).  Writes the result over the request.
 template <int VT, int SHADE, int AM, bool SKIP>
-__device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r, bool want,
+__device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r,
                                               unsigned int& n_shadow, unsigned int& n_shadow_skipped)
 {
-  // (entered by whole quads: `want` says whether this lane's request is a real one - the others only help with the quad-cooperative taps and
-  // compute on whatever their slot holds; their result is not stored)
-  constexpr bool COOP = Coop<VT, AM>::ok;
-  if (!COOP && !want) return;
   const f3 pos = mk3(r.px, r.py, r.pz);
   const f3 po = to_object(mc, pos);
   // one-sided differences, flipped at the upper bound; the three taps are issued together
   const bool flx = (po.x + mc.gstep.x) > 1.f, fly = (po.y + mc.gstep.y) > 1.f, flz = (po.z + mc.gstep.z) > 1.f;
   const f3 pgx = mk3(po.x + (flx ? -mc.gstep.x : mc.gstep.x), po.y, po.z), pgy = mk3(po.x, po.y + (fly ? -mc.gstep.y : mc.gstep.y), po.z);
   const f3 pgz = mk3(po.x, po.y, po.z + (flz ? -mc.gstep.z : mc.gstep.z));
-  float sgx, sgy, sgz;
-  f3 rgb;
-  if constexpr (COOP) {
-    const int sub = (int)(threadIdx.x & 3u), use = want ? -1 : 0;
-    Tap tx_, ty_, tz_;
-    tap_coords(vc, pgx, tx_); tap_coords(vc, pgy, ty_); tap_coords(vc, pgz, tz_);
-    CoopTap<VT, AM> cgx, cgy, cgz;
-    cgx.issue(vc, tx_, use, sub); cgy.issue(vc, ty_, use, sub); cgz.issue(vc, tz_, use, sub);
-    rgb = tf_color(tf, want ? r.v : 0.f);
-    sgx = cgx.finish(vc, sub); sgy = cgy.finish(vc, sub); sgz = cgz.finish(vc, sub);
-  }
-  else {
-    Tap tgx, tgy, tgz;
-    tap_issue<VT, AM>(vc, pgx, tgx);
-    tap_issue<VT, AM>(vc, pgy, tgy);
-    tap_issue<VT, AM>(vc, pgz, tgz);
-    rgb = tf_color(tf, r.v);
-    sgx = tap_finish<VT>(vc, tgx); sgy = tap_finish<VT>(vc, tgy); sgz = tap_finish<VT>(vc, tgz);
-  }
+  Tap tgx, tgy, tgz;
+  tap_issue<VT, AM>(vc, pgx, tgx);
+  tap_issue<VT, AM>(vc, pgy, tgy);
+  tap_issue<VT, AM>(vc, pgz, tgz);
+  const f3 rgb = tf_color(tf, r.v);
+  const float sgx = tap_finish<VT>(vc, tgx), sgy = tap_finish<VT>(vc, tgy), sgz = tap_finish<VT>(vc, tgz);
   f3 g;
 #if OVR_PARITY_EXACT
   g.x = (sgx - r.s) / (flx ? -mc.gstep.x : mc.gstep.x); // (sample(c + stp) - v) / stp, shaders_common.h:195-215
@@ -1311,11 +965,7 @@ __device__ __forceinline__ void shade_request(const RayMarchParams& P, const Vol
                          fmaf(n_w.x, m[2], fmaf(n_w.y, m[5], n_w.z * m[8]))));
   }
   float shadow = 0.f;
-  if (SHADE == 2) {
-    if constexpr (COOP) shadow = march_shadow_coop<VT, AM, kShadowTaps, SKIP>(vc, tf, mc, pos, want, n_shadow, n_shadow_skipped);
-    else if (OVR_SHADOW_PACKED && !SKIP) shadow = march_shadow_packed<VT, AM, kShadowTaps>(vc, tf, mc, pos, n_shadow);
-    else shadow = march_shadow<VT, AM, kShadowTaps, SKIP>(vc, tf, mc, pos, n_shadow, n_shadow_skipped);
-  }
+  if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP>(vc, tf, mc, pos, n_shadow, n_shadow_skipped);
   const float cosNL = fabsf(dot3(mc.light, n_w));
   const float shade = 0.5f + 0.5f * cosNL * 2.f * (1.f - shadow); // shaders_raymarching.cu:156-157
   const float tr = r.tr;
@@ -1406,15 +1056,11 @@ __device__ __forceinline__ float quad_bcast(float x) // value of lane B of this 
 // a_sub for the lane's sub = lane & 3.  As nested conditionals the compiler builds this from compares and exec-mask branches (5 vector + 7
 // scalar instructions per select, 8 selects per round of the march); with the two lane masks m1 = -(sub & 1), m2 = -((sub >> 1) & 1) kept in
 // registers it is three v_bfi_b32 (bit-field insert: (m & b) | (~m & a)) - the same bits
-#ifndef OVR_SEL4_BFI
-#define OVR_SEL4_BFI 1
-#endif
 struct SubMask { unsigned int m1, m2; int sub; };
 __device__ __forceinline__ SubMask make_submask(int sub) { SubMask m; m.m1 = 0u - (unsigned int)(sub & 1); m.m2 = 0u - (unsigned int)((sub >> 1) & 1); m.sub = sub; return m; }
 __device__ __forceinline__ unsigned int bfi(unsigned int m, unsigned int b, unsigned int a) { return (m & b) | (~m & a); }
 __device__ __forceinline__ float sel4(float a0, float a1, float a2, float a3, const SubMask& m)
 {
-  if (!OVR_SEL4_BFI) return m.sub == 0 ? a0 : m.sub == 1 ? a1 : m.sub == 2 ? a2 : a3;
   const unsigned int lo = bfi(m.m1, __float_as_uint(a1), __float_as_uint(a0)), hi = bfi(m.m1, __float_as_uint(a3), __float_as_uint(a2));
   return __uint_as_float(bfi(m.m2, hi, lo));
 }
@@ -1462,9 +1108,6 @@ __device__ __forceinline__ bool assign_pixel_quad(const RayMarchParams& P, int l
 // coarse grid over the whole ray, then - only inside the coarse interval - the per-macrocell grid: a primary ray is long (its
 // coarse interval is up to 80 voxels too wide at either end, and a ray that only grazes the dilated coarse entries gets an
 // interval although it meets nothing), and every round inside the interval costs ~330 instead of ~45 instructions.
-#ifndef OVR_SKIP_FINE
-#define OVR_SKIP_FINE 1
-#endif
 template <bool FINE>
 __device__ __forceinline__ void skip_interval_level(const VolConsts& vc, f3 oo, f3 od, float t0, float t1, int sub, bool live, float& t_first, float& t_last)
 {
@@ -1477,60 +1120,25 @@ __device__ __forceinline__ void skip_interval_level(const VolConsts& vc, f3 oo, 
   t_first = fminf(fminf(quad_bcast<0>(first), quad_bcast<1>(first)), fminf(quad_bcast<2>(first), quad_bcast<3>(first)));
   t_last = fmaxf(fmaxf(quad_bcast<0>(last), quad_bcast<1>(last)), fmaxf(quad_bcast<2>(last), quad_bcast<3>(last)));
 }
-// Measured (profiles/r03_notes.md, r03_ab_segments.txt): bit-identical frames, the march with skipping 2-4 % SLOWER on every bench
-// configuration and on the shipped scenes' shapes (C3 0.452 -> 0.467 ms, C2 0.334 -> 0.348, C5 1.70 -> 1.72) - their occupied macrocells are
-// one blob per ray, the hull already is the interval, and the mask costs registers and a 64-bit test per round.  Data with real interior
-// voids (the datasets do not ship) is where it would pay; off by default, -DOVR_SKIP_SEGMENTS=1 builds it.
-#ifndef OVR_SKIP_SEGMENTS
-#define OVR_SKIP_SEGMENTS 0
-#endif
 __device__ __forceinline__ SkipSpan skip_interval(const VolConsts& vc, f3 oo, f3 od, float t0, float t1, int sub, bool live)
 {
   SkipSpan sp = skipspan_none();
   sp.mask_lo = sp.mask_hi = ~0u;
   skip_interval_level<false>(vc, oo, od, t0, t1, sub, live, sp.first, sp.last);
-  if (OVR_SKIP_FINE) {
-    const float c0 = sp.first, c1 = sp.last; // quad-uniform
-    if (__ballot(live && c0 <= c1) != 0ull) {
-      const bool walk = live && c0 <= c1;
-      if (!OVR_SKIP_SEGMENTS) skip_interval_level<true>(vc, oo, od, c0, c1, sub, walk, sp.first, sp.last);
-      else {
-        // the fine walk over the coarse hull [c0, c1], a quarter per lane: hull and segment mask in one pass
-        float first = FLT_MAX, last = -FLT_MAX;
-        unsigned long long m = 0ull;
-        const float len = c1 - c0;
-        const float scale = len > 0.f ? 64.f / len : 0.f;
-        if (walk) {
-          const float ta = fmaf((float)sub * 0.25f, len, c0), tb = sub == 3 ? c1 : fmaf((float)(sub + 1) * 0.25f, len, c0);
-          skip_walk<true, true>(vc, oo, od, ta, tb, first, last, c0, scale, &m);
-          if (!(len > 0.f)) m = ~0ull;
-        }
-        sp.first = fminf(fminf(quad_bcast<0>(first), quad_bcast<1>(first)), fminf(quad_bcast<2>(first), quad_bcast<3>(first)));
-        sp.last = fmaxf(fmaxf(quad_bcast<0>(last), quad_bcast<1>(last)), fmaxf(quad_bcast<2>(last), quad_bcast<3>(last)));
-        const float lo = __uint_as_float((unsigned int)m), hi = __uint_as_float((unsigned int)(m >> 32));
-        sp.mask_lo = __float_as_uint(quad_bcast<0>(lo)) | __float_as_uint(quad_bcast<1>(lo)) | __float_as_uint(quad_bcast<2>(lo)) | __float_as_uint(quad_bcast<3>(lo));
-        sp.mask_hi = __float_as_uint(quad_bcast<0>(hi)) | __float_as_uint(quad_bcast<1>(hi)) | __float_as_uint(quad_bcast<2>(hi)) | __float_as_uint(quad_bcast<3>(hi));
-        sp.seg0 = c0;
-        sp.seg_scale = scale;
-      }
-    }
-  }
+  const float c0 = sp.first, c1 = sp.last; // quad-uniform
+  const bool walk = live && c0 <= c1;
+  if (__ballot(walk) != 0ull) skip_interval_level<true>(vc, oo, od, c0, c1, sub, walk, sp.first, sp.last);
   return sp;
 }
 
 template <int SHADE, bool POOLED> struct QCfg {
-#ifndef OVR_POOLED_K
-#define OVR_POOLED_K 4
-#endif
-  static constexpr int K = POOLED ? OVR_POOLED_K : (SHADE == 0 ? 4 : 3);   // instructions (x4 steps) per round
+  static constexpr int K = POOLED ? 4 : (SHADE == 0 ? 4 : 3);   // instructions (x4 steps) per round
   static constexpr int QCAP = SHADE == 0 ? 0 : (POOLED ? 128 : 256);       // pooled: spills after every instruction
 };
 
 // Register budget: at most 3 waves per SIMD (up to 168 VGPRs).  Left alone the compiler squeezes the kernel into 128 VGPRs
 // for a 4th wave by serialising the K tap groups it is supposed to keep in flight - measured 1.98 instead of 1.53 ms on C3.
-#ifndef OVR_MARCH_WPE
-#define OVR_MARCH_WPE 3
-#endif
+constexpr int kMarchWavesPerEu = 3;
 // LDSB = true: the "LDS-staged bricks" variant (north_star; measured in profiles/r02_notes.md).  Once per round the workgroup
 // copies the bricks its 64 rays touch in the round's 16 steps - the brick-aligned bounding box of the block's four corner
 // rays over the round's t range - from HBM / L2 into LDS with whole-line 16-byte loads (8 lanes per 128-byte brick), and the
@@ -1544,12 +1152,10 @@ struct LdsRegion { int bx0, by0, bz0, ebx, eby, ebz, nbr, ok; };
 // transfer functions and on axis views), but a ray's chain of dependent rounds is the floor of an image SHARD's march, and there 6
 // wins: 8-way shard of C3 0.295 -> 0.250 ms, 4-way 0.451 -> 0.423 (profiles/r02_notes.md).  launch_vsbs picks it for small shards (use_deep_rounds).
 constexpr int kDeepK = 6;
-template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false>
-#ifndef OVR_PIN_AM
-#define OVR_PIN_AM 1 /* the 64-bit addressing modes would spill to scratch under the pin */
-#endif
 // (the skipping pooled march sits at the edge of the 3-waves budget: 169 VGPRs - one too many - cost it 15 %; it is pinned to 3)
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= OVR_PIN_AM) ? OVR_MARCH_WPE : 1, OVR_MARCH_WPE))) void raymarch_kernel(const RayMarchParams P)
+constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scratch under the pin
+template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
   static_assert(!LDSB || (SHADE == 0 && !POOLED && !SKIP && AM <= 1 && !Vox<VT>::kTransposed), "LDS-staged bricks: unshaded in-place march only");
   using Cfg = QCfg<SHADE, POOLED>;
@@ -1775,15 +1381,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
           r.px = r.py = r.pz = r.s = r.v = r.tr = r.a = 0.f; r.next = 0;
           if ((unsigned int)lane < n) {
             r = queue[(q_head + lane) & (QCAP - 1)];
-            const bool want = r.a > 0.f; // a == 0: null request
-            if (Coop<VT, AM>::ok) { // whole quads enter (n is a multiple of 4): quad-cooperative taps, CoopTap
-              if (((unsigned int)(__ballot(want) >> (lane & 60)) & 0xfu) != 0u) {
-                ShadeReq rr = r;
-                shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, rr, want, n_shadow, n_shadow_skipped);
-                if (want) r = rr;
-              }
-            }
-            else if (want) shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, true, n_shadow, n_shadow_skipped);
+            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
           }
           int opend = owner ? pend : 0;
           apply_batch(r, q_head, n, lane, opend, first, color, gradient);
@@ -1977,20 +1575,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
       for (int k = 0; k < K; ++k) {
         sa[k] = tap_finish<VT>(vc, taps[k]);
         va[k] = tf_coord(tf, sa[k]);
-#ifndef OVR_MARCH_TF_PAD
-#define OVR_MARCH_TF_PAD 0 /* 1: the pooled march takes the paired read too (measurements) */
-#endif
-        aa[k] = opacity_correction<false>(tf_alpha<!POOLED || OVR_MARCH_TF_PAD>(tf, va[k]), mc.base * dts[k]);
+        aa[k] = opacity_correction<false>(tf_alpha<!POOLED>(tf, va[k]), mc.base * dts[k]);
         if (SKIP) aa[k] = mj[k] > 0.f ? aa[k] : 0.f; // a macrocell whose majorant is 0 holds no sample with opacity > 0
       }
       // ---- (3b) transparent round (wave-uniform; ~9 of 10 rounds with a sparse transfer function): no live sample of any
       //      ray of the wave has opacity > 0, so every step adds exactly 0 to alpha and colour (fma(tr, 0, x) == x) and
       //      pushes nothing - only liveness and the counters move.  The validity bits are monotone (once ty == tx == t1 it
       //      stays), so step i is live iff the ray was live at the start of the round, alpha < 0.9999 and bit i is set.
-#ifndef OVR_FAST_SKIP
-#define OVR_FAST_SKIP 0 /* the skipping kernels have their own, earlier fast path; this one costs them 30 VGPRs */
-#endif
-      if (OVR_FAST_SKIP || !SKIP) {
+      //      (Not in the skipping kernels: they have their own, earlier fast path, and this one costs them 30 VGPRs.)
+      if (!SKIP) {
         bool opaque = false;
 #pragma unroll
         for (int k = 0; k < K; ++k) opaque = opaque || (aa[k] > 0.f);
@@ -2177,11 +1770,9 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     const unsigned int n = Q.chunk_n[c];
     if ((unsigned int)lane < n) {
       ShadeReq r = Q.reqs[(size_t)c * 64 + lane];
-      const bool want = r.a > 0.f; // a == 0: null request (a step of the quad that needs no shading)
-      // whole quads enter (a chunk holds whole quads): the taps are quad-cooperative where the layout allows (CoopTap)
-      if (Coop<VT, AM>::ok ? (((unsigned int)(__ballot(want) >> (lane & 60)) & 0xfu) != 0u) : want) {
-        shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, want, n_shadow, n_shadow_skipped);
-        if (want) Q.reqs[(size_t)c * 64 + lane] = r;
+      if (r.a > 0.f) { // a == 0: null request (a step of the quad that needs no shading)
+        shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
+        Q.reqs[(size_t)c * 64 + lane] = r;
       }
     }
   };
@@ -2236,10 +1827,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     seen = run0 + batch;
     const unsigned int run1 = min(run0 + batch, n_runs);
     for (unsigned int ticket = run0; ticket < run1; ++ticket) {
-#ifndef OVR_TICKET_LOCKSTEP
-#define OVR_TICKET_LOCKSTEP 1
-#endif
-      if (OVR_TICKET_LOCKSTEP && ticket != run0) __syncthreads(); // the 4 waves stay on ONE run: its chunks share their bricks in L1
+      if (ticket != run0) __syncthreads(); // the 4 waves stay on ONE run: its chunks share their bricks in L1
       const unsigned int grp = ticket / kTicketBlock, sub = grp & (unsigned int)(kPoolSubs - 1);
       const unsigned int run = (grp / (unsigned int)kPoolSubs) * kTicketBlock + ticket % kTicketBlock;
       if (run >= s_runs[sub]) continue; // idle ticket (workgroup-uniform)
@@ -2297,19 +1885,17 @@ inline int shade_grid_blocks(const RayMarchParams& p)
 // (profiles/r02_ab/r02b_deep.txt, march ms plain -> deep): C3 4-way 0.443 -> 0.422, 8-way 0.288 -> 0.254, 2-way (16 200 blocks) equal;
 // but C5 (4K: 16 200 blocks even 8-way, throughput-bound) 0.508 -> 0.607 and C4 8-way (64-bit addressing) 0.604 -> 0.632: so only
 // shards of at most 10 000 blocks with 32-bit addressing take it.  OVR_HIP_DEEP=0|1 overrides the choice (measurements).
-#ifndef OVR_DEEP_MAX_BLOCKS
-#define OVR_DEEP_MAX_BLOCKS 10000
-#endif
+constexpr unsigned int kDeepMaxBlocks = 10000;
 inline bool use_deep_rounds(const RayMarchParams& p)
 {
   static const int forced = getenv("OVR_HIP_DEEP") ? atoi(getenv("OVR_HIP_DEEP")) : -1;
   if (forced >= 0) return forced != 0;
   // sparse (foveated) frames: the kept rays are few and concentrated where the rays are long - the same floor (round 3: march 1.12 ->
   // 1.01 ms at the app's default focus); the host passes the previous frame's pixel count, the list's length is only known on the device
-  if (p.sparse_xy) return p.world == 1 && p.sparse_hint_pixels > 0 && p.sparse_hint_pixels <= 64ull * OVR_DEEP_MAX_BLOCKS;
+  if (p.sparse_xy) return p.world == 1 && p.sparse_hint_pixels > 0 && p.sparse_hint_pixels <= 64ull * kDeepMaxBlocks;
   // (the threshold was measured on the number of blocks a shard OWNS, launched or not: n_blocks_owned - n_schedule may be smaller since
   // round 4, when blocks none of whose rays hits the box are no longer launched)
-  return p.world > 1 && p.n_blocks_owned <= (unsigned int)OVR_DEEP_MAX_BLOCKS;
+  return p.world > 1 && p.n_blocks_owned <= kDeepMaxBlocks;
 }
 
 template <int VT, int SHADE, int AM, bool SKIP>
@@ -2419,7 +2005,7 @@ inline hipError_t launch_vs(const RayMarchParams& p, hipStream_t stream, const h
   int am = addressing_mode(p.vol, p.n_color, p.n_alpha);
   if (const char* f = getenv("OVR_HIP_ADDRESSING")) am = std::max(am, atoi(f)); // diagnostic: a more general mode than needed (tests)
   if (am < 3 && (!p.vol.axis_ab || !p.vol.axis_z)) return hipErrorInvalidValue; // the layout's offset tables (launch_axis_tables)
-  if constexpr (sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad && OVR_ROW_LOADS) {
+  if constexpr (sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad) {
     // mode 4 = mode 0 with the 16-bit pairs read as aligned 8-byte rows (RowLoads): layouts the caches do not serve; OVR_HIP_ROW_LOADS=0|1, read when a renderer is created, forces (tests, measurements)
     const int forced = p.row_loads - 1; // RayMarchParams::row_loads: 0 = by size, 1 = never, 2 = always
     if (am == 0 && (forced >= 0 ? forced != 0 : p.vol.bytes > (128ull << 20))) return launch_vsb<VT, SHADE, 4>(p, stream, ev);

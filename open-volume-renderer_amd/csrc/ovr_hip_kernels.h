@@ -76,10 +76,7 @@ struct float3_ { float x, y, z; };
 // their first sample, and half of it with a dense transfer function.  4 sub-pools remove that (march 1.00 -> 0.59 ms, dense TF);
 // more bring little (8: 0.57) and slow the shade kernel down - its requests lose their creation order - by 1.7 % (8), 2 % (16),
 // 11 % (64) on the sparse-TF headline; profiles/r02_notes.md, profiles/r02_ab/r02_ab_ps*.txt.
-#ifndef OVR_POOL_SUBS
-#define OVR_POOL_SUBS 4
-#endif
-constexpr int kPoolSubs = OVR_POOL_SUBS; // a power of two, at most 64
+constexpr int kPoolSubs = 4; // a power of two, at most 64
 constexpr int kPoolCtrlWords = 32 * (kPoolSubs + 2);
 // ctrl words: [0] shade ticket cursor, [1] overflow flag of this generation (a sub-pool ran out), [32 * (s + 1)] chunks reserved
 // from sub-pool s (all of these zeroed per generation), [32 * (kPoolSubs + 1)] the most any sub-pool was asked for in any

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OVR_HIP_ABI_VERSION 10
+#define OVR_HIP_ABI_VERSION 11
 
 /* error codes */
 #define OVR_HIP_OK 0
@@ -219,6 +219,46 @@ int ovr_hip_get_macrocells(ovr_hip_renderer* r, int32_t dims[3], float* minmax_h
 /* extension (multi-GPU): this renderer draws only the image tiles owned by `rank` of `world`;
  * owner(tile_x, tile_y) = (tile_x + tile_y) % world.  world = 1 restores the single-GPU behaviour. */
 int ovr_hip_set_image_shard(ovr_hip_renderer* r, int32_t rank, int32_t world, int32_t tile_w, int32_t tile_h);
+
+/* ABI v11 - convergence estimate and adaptive refinement.  The renderer interface has a convergence number -
+ * MainRenderer::unsafe_get_variance(), ovr/renderer.h:124-127: the title bar of the interactive app, the stop criterion of the batch app's
+ * progressive loop, apps/main_batch.cpp:211-215 - that the reference's OptiX device leaves at 0 (device_impl.cpp:266).  Defined while frames
+ * accumulate and sparse sampling is off, from the second accumulated frame on.  Beside the accumulation buffer A the renderer keeps H, the sum of the
+ * even-numbered frames; after an even frame n, per pixel (IEEE float, in this order)
+ *     m = A / n, h = H / (n / 2) per channel;  d = ((|m_r - h_r| + |m_g - h_g|) + |m_b - h_b|) + |m_a - h_a|;  s = ((m_r + m_g) + m_b) + m_a;
+ *     e = s > 0 ? d / sqrtf(s) : 0
+ * and per 8x8-pixel block E_b = T(e) / P: T the balanced pairwise tree over the 64 pixels in the order 8 * (y & 7) + (x & 7), P the pixels of the block
+ * that lie inside the image and belong to this renderer (pixels that do not contribute 0).  The frame error is the largest E_b.  It has the shape of
+ * OSPRay's tile error (the whole accumulation against half of it, normalised by the root of the brightness) and is NOT claimed to equal its value.
+ * open-volume-renderer_amd/convergence.py is the same arithmetic in numpy.
+ *   OFF       today's behaviour: no buffer, no launch
+ *   ESTIMATE  every frame is bit-identical to OFF; one more read-modify-write of 32 B per pixel and the estimate's kernels on even frames
+ *   ADAPTIVE  + after an even frame n every active block with E_b <= threshold is RETIRED: it is no longer marched, keeps n_b = n, and in every later frame
+ *             its pixels are written as A / n_b - and its gradient pixels as frame n_b left them - into the framebuffer set that frame renders into; it
+ *             stays retired until the accumulation is reset.  ovr_hip_stats then counts what was marched.  When every block is retired a frame is that
+ *             one small kernel.  A retired block keeps its E_b: frame error <= threshold exactly when every block is retired.
+ * Queued like every setter, applied at commit; every call resets the accumulation.  EINVAL: unknown mode, a negative or non-finite threshold.
+ * ovr_hip_render_async in these modes, as always, resolves the previous frame (reads its estimate and active count) before it launches the next. */
+#define OVR_HIP_CONVERGENCE_OFF 0
+#define OVR_HIP_CONVERGENCE_ESTIMATE 1
+#define OVR_HIP_CONVERGENCE_ADAPTIVE 2
+int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold);
+
+typedef struct ovr_hip_convergence {
+  float error;            /* frame error; +inf while valid == 0 */
+  float threshold;
+  int32_t mode, valid;    /* valid: 0 before the second accumulated frame, without accumulation, with sparse sampling, with the mode OFF */
+  int32_t frames;         /* the even frame the estimate belongs to (on an odd frame: the one before it) */
+  int32_t blocks, active_blocks, retired_blocks; /* owned 8x8 blocks that a ray can meet (the others are never marched and have E_b = 0); a device
+                                                     group: summed over its members, error = the largest member's */
+} ovr_hip_convergence;
+int ovr_hip_get_convergence(const ovr_hip_renderer* r, ovr_hip_convergence* out);
+/* for known-answer tests, like ovr_hip_get_macrocells.  dims = blocks per axis (ceil(W / 8), ceil(H / 8)); error_host[bx + by * dims[0]] = E_b,
+ * frames_host = n_b, negated when the block is retired; blocks this renderer does not own or that no ray meets read error 0, frames 0.
+ * member: as ovr_hip_get_member_stats (0 for an ordinary renderer).  Either output may be NULL. */
+int ovr_hip_get_convergence_blocks(ovr_hip_renderer* r, int32_t member, int32_t dims[2], float* error_host, int32_t* frames_host, size_t capacity_blocks);
+/* the accumulation buffers, W*H*4 floats: which = 0: A, 1: H (ESTATE while the mode is OFF) */
+int ovr_hip_get_accumulation(ovr_hip_renderer* r, int32_t member, int32_t which, float* host, size_t capacity_floats);
 
 /* replaces DeviceOptix7::Impl::commit (device_impl.cpp:113-197): applies every queued setter; any change resets
  * the accumulation (frame_index restarts at 1 on the next render). */

@@ -19,9 +19,10 @@ SHADE_NONE, SHADE_GRADIENT, SHADE_FULL = 0, 1, 2
 GRID_CELL_CENTRED, GRID_VERTEX_CENTRED = 0, 1
 PIPELINE_AUTO, PIPELINE_IN_PLACE, PIPELINE_POOLED = 0, 1, 2
 JITTER_TEA, JITTER_BLUE_NOISE = 0, 1
+CONVERGENCE_OFF, CONVERGENCE_ESTIMATE, CONVERGENCE_ADAPTIVE = 0, 1, 2
 LAYOUT_AUTO, LAYOUT_GENERAL, LAYOUT_THIN, LAYOUT_THIN_T, LAYOUT_QUAD = -1, 0, 1, 2, 3
 # the ABI these ctypes structures describe: load() refuses a library of another version (ovr_hip_get_stats would write past them)
-EXPECTED_ABI = 10
+EXPECTED_ABI = 11
 
 
 class Stats(C.Structure):
@@ -61,6 +62,19 @@ class VolumeInfo(C.Structure):
         ("data_upper", C.c_float),
         ("tf_lower", C.c_float),
         ("tf_upper", C.c_float),
+    ]
+
+
+class Convergence(C.Structure):
+    _fields_ = [
+        ("error", C.c_float),
+        ("threshold", C.c_float),
+        ("mode", C.c_int32),
+        ("valid", C.c_int32),
+        ("frames", C.c_int32),
+        ("blocks", C.c_int32),
+        ("active_blocks", C.c_int32),
+        ("retired_blocks", C.c_int32),
     ]
 
 
@@ -120,6 +134,10 @@ SYMBOLS = {
     "ovr_hip_set_layout_choice": (C.c_int, [_H, C.c_int32]),
     "ovr_hip_get_volume_info": (C.c_int, [_H, C.POINTER(VolumeInfo)]),
     "ovr_hip_mapframe_rgba16f": (C.c_int, [_H, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "ovr_hip_set_convergence": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "ovr_hip_get_convergence": (C.c_int, [_H, C.POINTER(Convergence)]),
+    "ovr_hip_get_convergence_blocks": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), _F3, C.POINTER(C.c_int32), C.c_size_t]),
+    "ovr_hip_get_accumulation": (C.c_int, [_H, C.c_int32, C.c_int32, _F3, C.c_size_t]),
 }
 
 _lib = None

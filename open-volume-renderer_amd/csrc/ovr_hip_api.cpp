@@ -95,6 +95,7 @@ struct FocusP { float cx = 0.5f, cy = 0.5f, scale = 0.2f, base_noise = 0.1f; }; 
 struct TfnP { std::vector<float> colors, alphas; float lo = 1, hi = -1; };
 struct ShardP { int rank = 0, world = 1, tw = 64, th = 64; };
 struct Size2 { int w = 0, h = 0; };
+struct ConvP { int mode = OVR_HIP_CONVERGENCE_OFF; float threshold = 0.f; };
 
 } // namespace
 
@@ -213,6 +214,23 @@ struct ovr_hip_renderer {
   int h_rgba_rect[2][4] = {}, h_grad_rect[2][4] = {};
   int d_rect[2][4] = {}; // per framebuffer set: the rectangle of the camera its last frame was rendered with (empty: never rendered, all zeros)
   float* d_accum = nullptr;
+  // ---- convergence estimate and adaptive refinement (ovr_hip_set_convergence).  Everything below exists only while the mode is not OFF.
+  Queued<ConvP> convergence;
+  float* d_accum_half = nullptr;        // H: the sum of the even-numbered frames (W*H*4)
+  float* d_grad_keep = nullptr;         // adaptive: the gradient pixels of the retired blocks (W*H*3)
+  float* d_conv_error = nullptr;        // per block of the image (bx + by * ceil(W / 8)): E_b
+  int* d_conv_frames = nullptr;         // per block: the even frame of its estimate, negated when retired, 0 = none
+  unsigned int* d_conv_words = nullptr; // ConvergenceParams::words
+  unsigned int* d_conv_lists = nullptr; // adaptive: [active: conv_list_cap][retired: conv_list_cap][counts]
+  unsigned int* h_conv = nullptr;       // pinned: ConvergenceParams::publish
+  size_t conv_blocks = 0, conv_list_cap = 0;
+  const unsigned int* conv_sorted = nullptr; // the frame's launch list before anything was retired from it
+  bool conv_frame = false;              // the frame in flight is followed by an estimate
+  bool conv_resolve_only = false;       // the frame in flight marches nothing: every block is retired
+  bool conv_valid = false;
+  float conv_error = 0.f;
+  int conv_frames = 0;
+  unsigned int conv_active = 0, conv_retired = 0; // entries of the launch list that are marched / resolved (conv_active + conv_retired == n_work while adaptive)
   uint32_t* d_rgba8 = nullptr; // mapframe_rgba8: device and pinned host copy of the 8-bit frame
   uint32_t* h_rgba8 = nullptr;
   uint16_t* d_rgba16f = nullptr; // mapframe_rgba16f: the half frame of the EXR writer
@@ -319,6 +337,61 @@ namespace {
 
 int set_device(ovr_hip_renderer* r) { HIP_TRY(hipSetDevice(r->device)); return 0; }
 
+// the convergence estimate's buffers: gone with the mode, the framebuffer size or the renderer (ensure_convergence brings them back)
+int free_convergence(ovr_hip_renderer* r)
+{
+  if (r->d_accum_half) HIP_TRY(hipFree(r->d_accum_half));
+  if (r->d_grad_keep) HIP_TRY(hipFree(r->d_grad_keep));
+  if (r->d_conv_error) HIP_TRY(hipFree(r->d_conv_error));
+  if (r->d_conv_frames) HIP_TRY(hipFree(r->d_conv_frames));
+  if (r->d_conv_words) HIP_TRY(hipFree(r->d_conv_words));
+  if (r->d_conv_lists) HIP_TRY(hipFree(r->d_conv_lists));
+  r->d_accum_half = r->d_grad_keep = r->d_conv_error = nullptr;
+  r->d_conv_frames = nullptr; r->d_conv_words = r->d_conv_lists = nullptr;
+  r->conv_blocks = r->conv_list_cap = 0;
+  r->conv_valid = false;
+  r->conv_active = r->conv_retired = 0;
+  return 0;
+}
+
+int ensure_convergence(ovr_hip_renderer* r, bool lists)
+{
+  const int W = r->fbsize.current.w, H = r->fbsize.current.h;
+  const size_t n = r->fb_pixels, blocks = (size_t)((W + 7) / 8) * (size_t)((H + 7) / 8);
+  const bool adaptive = r->convergence.current.mode == OVR_HIP_CONVERGENCE_ADAPTIVE;
+  if (!r->d_accum_half) {
+    HIP_TRY(hipMalloc((void**)&r->d_accum_half, std::max<size_t>(n, 1) * 4 * sizeof(float)));
+    HIP_TRY(hipMemset(r->d_accum_half, 0, std::max<size_t>(n, 1) * 4 * sizeof(float))); // pixels no frame writes (other ranks' tiles) read 0
+  }
+  if (!r->d_conv_error || r->conv_blocks != blocks) {
+    if (r->d_conv_error) HIP_TRY(hipFree(r->d_conv_error));
+    if (r->d_conv_frames) HIP_TRY(hipFree(r->d_conv_frames));
+    r->d_conv_error = nullptr; r->d_conv_frames = nullptr;
+    HIP_TRY(hipMalloc((void**)&r->d_conv_error, std::max<size_t>(blocks, 1) * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&r->d_conv_frames, std::max<size_t>(blocks, 1) * sizeof(int)));
+    r->conv_blocks = blocks;
+  }
+  if (!r->d_conv_words) {
+    HIP_TRY(hipMalloc((void**)&r->d_conv_words, 4 * sizeof(unsigned int)));
+    HIP_TRY(hipMemset(r->d_conv_words, 0, 4 * sizeof(unsigned int)));
+  }
+  if (!r->h_conv) {
+    HIP_TRY(hipHostMalloc((void**)&r->h_conv, 4 * sizeof(unsigned int), hipHostMallocDefault));
+    std::memset(r->h_conv, 0, 4 * sizeof(unsigned int));
+  }
+  if (adaptive && lists) { // (sized by the launch list: asked for once the frame has built it)
+    if (!r->d_grad_keep) HIP_TRY(hipMalloc((void**)&r->d_grad_keep, std::max<size_t>(n, 1) * 3 * sizeof(float)));
+    if (!r->d_conv_lists || r->conv_list_cap < r->n_sched) {
+      if (r->d_conv_lists) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(r->d_conv_lists)); }
+      r->d_conv_lists = nullptr;
+      const size_t cap = std::max<size_t>(r->n_sched, 1);
+      HIP_TRY(hipMalloc((void**)&r->d_conv_lists, (2 * cap + (cap + 1023) / 1024) * sizeof(unsigned int)));
+      r->conv_list_cap = cap;
+    }
+  }
+  return 0;
+}
+
 int free_framebuffers(ovr_hip_renderer* r)
 {
   for (int i = 0; i < 2; ++i) {
@@ -330,6 +403,7 @@ int free_framebuffers(ovr_hip_renderer* r)
   }
   if (r->d_accum) HIP_TRY(hipFree(r->d_accum));
   r->d_accum = nullptr;
+  if (int e = free_convergence(r)) return e;
   if (r->d_rgba8) HIP_TRY(hipFree(r->d_rgba8));
   if (r->h_rgba8) HIP_TRY(hipHostFree(r->h_rgba8));
   r->d_rgba8 = nullptr; r->h_rgba8 = nullptr;
@@ -1023,6 +1097,14 @@ int enqueue_frame(ovr_hip_renderer* r)
   P.n_blocks_owned = 0;
   r->frame_empty_pixels = 0;
   r->frame_empty_rays = 0;
+  // ---- convergence estimate / adaptive refinement: defined while frames accumulate and every pixel is sampled
+  const bool conv_on = r->convergence.current.mode != OVR_HIP_CONVERGENCE_OFF && accumulate && !sparse;
+  P.accum_half = nullptr; // (before launch_clear_blocks: H is cleared with A)
+  P.conv_asked = nullptr;
+  if (conv_on) {
+    if (int e = ensure_convergence(r, false)) return e;
+    P.accum_half = r->d_accum_half;
+  }
   if (!sparse) {
     if (r->sched_list_dirty)
       if (int e = build_schedule_list(r)) return e;
@@ -1056,6 +1138,38 @@ int enqueue_frame(ovr_hip_renderer* r)
       if (r->set_clear_gen[r->cur] != r->clear_gen || first_accumulated) {
         HIP_TRY(launch_clear_blocks(P, r->d_sched + r->n_work, r->n_sched - r->n_work, first_accumulated ? 1 : 0, st));
         r->set_clear_gen[r->cur] = r->clear_gen;
+      }
+    }
+  }
+  r->conv_frame = r->conv_resolve_only = false;
+  if (!conv_on) r->conv_valid = false;
+  else {
+    const bool adaptive = r->convergence.current.mode == OVR_HIP_CONVERGENCE_ADAPTIVE;
+    if (int e = ensure_convergence(r, true)) return e;
+    if (r->frame_index == 1) { // a new accumulation: no estimate yet, every block is active again (d_sched still holds them all, sorted)
+      HIP_TRY(hipMemsetAsync(r->d_conv_error, 0, std::max<size_t>(r->conv_blocks, 1) * sizeof(float), st));
+      HIP_TRY(hipMemsetAsync(r->d_conv_frames, 0, std::max<size_t>(r->conv_blocks, 1) * sizeof(int), st));
+      HIP_TRY(hipMemsetAsync(r->d_conv_words, 0, 4 * sizeof(unsigned int), st));
+      // an image shard writes its own tiles only: what an earlier shard or an unsharded accumulation left in the others is not H
+      if (r->shard.current.world > 1) HIP_TRY(hipMemsetAsync(r->d_accum_half, 0, std::max<size_t>(n, 1) * 4 * sizeof(float), st));
+      r->conv_valid = false;
+      r->conv_error = 0.f;
+      r->conv_frames = 0;
+      r->conv_active = r->n_work;
+      r->conv_retired = 0;
+    }
+    P.conv_asked = r->d_conv_words + 2;
+    r->conv_sorted = P.schedule;
+    r->conv_frame = (r->frame_index & 1) == 0;
+    if (adaptive && r->conv_retired > 0) {
+      P.schedule = r->d_conv_lists; // the active entries, still longest rays first
+      P.n_schedule = r->conv_active;
+      if (r->conv_active == 0) { // every block is retired: the frame is the resolve alone
+        r->conv_resolve_only = true;
+        r->conv_frame = false;
+        r->tune_frame = -1;      // nothing the layout / pipeline tuner could time
+        P.pool = PoolDesc{};
+        return launch_frame(r);
       }
     }
   }
@@ -1101,6 +1215,19 @@ int enqueue_frame(ovr_hip_renderer* r)
 int launch_frame(ovr_hip_renderer* r)
 {
   hipStream_t st = r->stream();
+  const bool resolve = r->P.accum_half && r->convergence.current.mode == OVR_HIP_CONVERGENCE_ADAPTIVE && r->conv_retired > 0;
+  const int blocks_x = (r->fbsize.current.w + 7) / 8;
+  if (r->conv_resolve_only) { // (no march, no counters: the host's copy of them reads 0)
+    HIP_TRY(hipEventRecord(r->ev[0], st));
+    HIP_TRY(launch_resolve_blocks(r->P, r->d_conv_lists + r->conv_list_cap, r->conv_retired, r->d_conv_frames, r->d_grad_keep, blocks_x, st));
+    HIP_TRY(hipEventRecord(r->ev[3], st));
+    std::memset(r->h_counters, 0, 8 * sizeof(unsigned long long));
+    r->frame_phase_timed = false;
+    r->async_pending = true;
+    return 0;
+  }
+  // retired blocks get their pixels from the resolve (disjoint from what the march writes), in whichever set this frame renders into
+  if (resolve) HIP_TRY(launch_resolve_blocks(r->P, r->d_conv_lists + r->conv_list_cap, r->conv_retired, r->d_conv_frames, r->d_grad_keep, blocks_x, st));
   // the frame's last reduction kernel writes the counters and the pool's control words into h_counters / h_ctrl itself and zeroes them on the
   // device for the next frame (RayMarchParams::publish): a frame is its kernels, nothing in front of them and nothing behind
   r->P.publish = r->h_counters;
@@ -1116,6 +1243,24 @@ int launch_frame(ovr_hip_renderer* r)
   r->frame_phase_timed = phases;
   HIP_TRY(launch_raymarch(r->P, st, evs));
   r->frame_words_dirty = false;
+  if (r->conv_frame) { // behind the frame's last kernel and its last event: kernel_ms stays the frame's own time
+    ConvergenceParams c{};
+    c.accum = r->d_accum; c.accum_half = r->d_accum_half; c.grad = r->P.grad; c.grad_keep = r->d_grad_keep;
+    c.width = r->P.width; c.height = r->P.height; c.frame_index = r->P.frame_index;
+    c.rank = r->P.rank; c.world = r->P.world; c.tile_w = r->P.tile_w; c.tile_h = r->P.tile_h;
+    c.blocks_x = blocks_x;
+    c.adaptive = r->convergence.current.mode == OVR_HIP_CONVERGENCE_ADAPTIVE ? 1 : 0;
+    c.threshold = r->convergence.current.threshold;
+    c.sorted = r->conv_sorted; c.n_work = r->n_work;
+    c.active = r->P.schedule; c.n_active = r->P.n_schedule;
+    c.active_out = r->d_conv_lists; c.retired_out = r->d_conv_lists ? r->d_conv_lists + r->conv_list_cap : nullptr;
+    c.counts = r->d_conv_lists ? r->d_conv_lists + 2 * r->conv_list_cap : nullptr;
+    c.block_error = r->d_conv_error; c.block_frames = r->d_conv_frames; c.words = r->d_conv_words;
+    c.sub_capacity = r->P.pool.reqs ? r->P.pool.sub_capacity : 0xffffffffu;
+    c.publish = r->h_conv;
+    r->h_conv[3] = 0u; // (finish_frame_one expects this frame's number here)
+    HIP_TRY(launch_convergence(c, st));
+  }
   r->async_pending = true;
   return 0;
 }
@@ -1288,6 +1433,18 @@ int finish_frame_one(ovr_hip_renderer* r)
       r->skip_backoff = std::min(r->skip_backoff * 2, 256);
     }
     else r->skip_backoff = 32;
+  }
+  if (r->conv_frame) { // the estimate behind this (even) frame, published by its last kernel
+    if (r->h_conv[3] != (unsigned int)r->frame_index) return fail(OVR_HIP_EDEVICE, "[hip] the convergence estimate of the frame was not published");
+    std::memcpy(&r->conv_error, &r->h_conv[0], sizeof(float));
+    r->conv_frames = r->frame_index;
+    r->conv_valid = true;
+    if (r->convergence.current.mode == OVR_HIP_CONVERGENCE_ADAPTIVE) {
+      // the tuner compares kernel times of consecutive frames: candidates timed on different amounts of work are not comparable - it starts over
+      if (r->h_conv[1] != r->conv_active && r->tune_on && r->tune_state == 1) r->tune_state = 0;
+      r->conv_active = r->h_conv[1];
+      r->conv_retired = r->h_conv[2];
+    }
   }
   if (r->d_trace) {
     if (const char* path = getenv("OVR_HIP_TRACE_FILE")) {
@@ -1915,6 +2072,7 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_sparse_count) (void)hipFree(r->d_sparse_count);
   if (r->d_data_range) (void)hipFree(r->d_data_range);
   if (r->h_counters) (void)hipHostFree(r->h_counters);
+  if (r->h_conv) (void)hipHostFree(r->h_conv);
   for (int i = 0; i < 4; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   if (r->pool.reqs) (void)hipFree(r->pool.reqs);
   if (r->pool.chunk_next) (void)hipFree(r->pool.chunk_next);
@@ -2264,6 +2422,18 @@ OVR_SIMPLE_SETTER(ovr_hip_set_layout_choice, layout_choice, int32_t, v >= -1 && 
 OVR_SIMPLE_SETTER(ovr_hip_set_lds_staging, lds_staging, int32_t, v == 0 || v == 1, "[hip] unknown LDS-staging mode")
 OVR_SIMPLE_SETTER(ovr_hip_set_pixel_jitter, jitter, int32_t, v == 0 || v == 1, "[hip] unknown pixel-jitter mode")
 
+int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (mode != OVR_HIP_CONVERGENCE_OFF && mode != OVR_HIP_CONVERGENCE_ESTIMATE && mode != OVR_HIP_CONVERGENCE_ADAPTIVE)
+    return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_convergence: unknown mode");
+  if (!std::isfinite(threshold) || threshold < 0.f) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_convergence: the threshold must be finite and not negative");
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); ConvP c; c.mode = mode; c.threshold = threshold; r->convergence.set(c); }
+  GROUP_FORWARD(r, ovr_hip_set_convergence(m, mode, threshold));
+  return 0;
+}
+
 int ovr_hip_set_focus(ovr_hip_renderer* r, float cx, float cy, float scale, float base_noise)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -2328,7 +2498,8 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
          && a->rate.current == b->rate.current && a->jitter.current == b->jitter.current && a->grid_convention.current == b->grid_convention.current
          && a->tfn.current.lo == b->tfn.current.lo && a->tfn.current.hi == b->tfn.current.hi && a->tfn.current.colors == b->tfn.current.colors && a->tfn.current.alphas == b->tfn.current.alphas
          && std::memcmp(&a->focus.current, &b->focus.current, sizeof(FocusP)) == 0 && a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw
-         && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn;
+         && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn && a->convergence.current.mode == b->convergence.current.mode
+         && a->convergence.current.threshold == b->convergence.current.threshold;
 }
 } // namespace
 extern "C" {
@@ -2405,6 +2576,16 @@ int commit_one(ovr_hip_renderer* r)
   if (r->rate.update()) r->fb_reset = true;       // :190-196
   if (r->shading.update()) r->fb_reset = true;
   if (r->jitter.update()) { r->fb_reset = true; r->sched_dirty = true; }
+  {
+    const int before = r->convergence.current.mode;
+    if (r->convergence.update()) { // any call resets the accumulation: retired blocks come back, the estimate starts over
+      r->fb_reset = true;
+      if (r->convergence.current.mode != before) { // OFF keeps no buffer; the other two allocate what they need with their next frame
+        HIP_TRY(hipDeviceSynchronize());
+        if (int e = free_convergence(r)) return e;
+      }
+    }
+  }
   (void)r->lds_staging.update(); // same frame either way
   // every layout and both pipelines give the same frame: no accumulation reset - but what was measured under the old setting is void
   // (a probe must not override a layout forced meanwhile; forced -> automatic has to measure again)
@@ -2426,6 +2607,7 @@ int commit_one(ovr_hip_renderer* r)
   }
   if (tune_void) { r->tune_state = 0; r->tune_recheck = 0; }
   r->fb_reset = other_changed || only_camera_so_far || reset_pending;
+  if (r->fb_reset) { r->conv_valid = false; r->conv_retired = 0; r->conv_active = r->n_work; }
   return 0;
 }
 } // namespace
@@ -2606,6 +2788,83 @@ int ovr_hip_get_stats(const ovr_hip_renderer* r, ovr_hip_stats* out)
   if (r->async_pending) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_stats: a frame is still in flight (call ovr_hip_sync)");
   *out = r->stats;
   return 0;
+}
+
+namespace {
+void convergence_of(const ovr_hip_renderer* m, ovr_hip_convergence* out)
+{
+  const ConvP& c = m->convergence.current;
+  out->threshold = c.threshold;
+  out->mode = c.mode;
+  out->valid = m->conv_valid ? 1 : 0;
+  out->error = m->conv_valid ? m->conv_error : INFINITY;
+  out->frames = m->conv_valid ? m->conv_frames : 0;
+  const bool adaptive = c.mode == OVR_HIP_CONVERGENCE_ADAPTIVE;
+  out->blocks = c.mode != OVR_HIP_CONVERGENCE_OFF ? (int32_t)m->n_work : 0;
+  out->retired_blocks = adaptive ? (int32_t)m->conv_retired : 0;
+  out->active_blocks = out->blocks - out->retired_blocks;
+}
+// the renderer a diagnostic download addresses: member k of a device group, the renderer itself otherwise
+ovr_hip_renderer* member_of(ovr_hip_renderer* r, int32_t member)
+{
+  const int n = r->members.size() > 1 ? (int)r->members.size() : 1;
+  if (member < 0 || member >= n) return nullptr;
+  return n > 1 ? r->members[(size_t)member] : r;
+}
+} // namespace
+
+int ovr_hip_get_convergence(const ovr_hip_renderer* r, ovr_hip_convergence* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_convergence: null argument");
+  if (r->async_pending) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_convergence: a frame is still in flight (call ovr_hip_sync)");
+  convergence_of(r, out);
+  for (size_t i = 1; i < r->members.size(); ++i) { // a device group: the largest error, the blocks of all members
+    ovr_hip_convergence a;
+    convergence_of(r->members[i], &a);
+    out->valid = out->valid && a.valid;
+    out->error = std::max(out->error, a.error);
+    out->blocks += a.blocks; out->active_blocks += a.active_blocks; out->retired_blocks += a.retired_blocks;
+  }
+  if (!out->valid) { out->error = INFINITY; out->frames = 0; }
+  return 0;
+}
+
+int ovr_hip_get_convergence_blocks(ovr_hip_renderer* r, int32_t member, int32_t dims[2], float* error_host, int32_t* frames_host, size_t capacity_blocks)
+{
+  if (!r || !dims) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_convergence_blocks: null argument");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  ovr_hip_renderer* m = member_of(r, member);
+  if (!m) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_convergence_blocks: no such member");
+  dims[0] = (m->fbsize.current.w + 7) / 8; dims[1] = (m->fbsize.current.h + 7) / 8;
+  const size_t blocks = (size_t)dims[0] * (size_t)dims[1];
+  if (!error_host && !frames_host) return 0;
+  if (capacity_blocks < blocks) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_convergence_blocks: output too small");
+  if (!m->d_conv_error || m->conv_blocks != blocks) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_convergence_blocks: no frame was rendered with the convergence estimate on");
+  if (blocks == 0) return 0;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream()));
+  if (error_host) HIP_TRY(hipMemcpy(error_host, m->d_conv_error, blocks * sizeof(float), hipMemcpyDeviceToHost));
+  if (frames_host) HIP_TRY(hipMemcpy(frames_host, m->d_conv_frames, blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return set_device(r);
+}
+
+int ovr_hip_get_accumulation(ovr_hip_renderer* r, int32_t member, int32_t which, float* host, size_t capacity_floats)
+{
+  if (!r || !host || (which != 0 && which != 1)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_accumulation: bad argument");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  ovr_hip_renderer* m = member_of(r, member);
+  if (!m) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_accumulation: no such member");
+  const size_t floats = m->fb_pixels * 4;
+  if (capacity_floats < floats) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_accumulation: output too small");
+  const float* src = which == 0 ? m->d_accum : m->d_accum_half;
+  if (!src) return fail(OVR_HIP_ESTATE, which == 0 ? "[hip] ovr_hip_get_accumulation: no framebuffer" : "[hip] ovr_hip_get_accumulation: no frame was rendered with the convergence estimate on");
+  if (floats == 0) return 0;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream()));
+  HIP_TRY(hipMemcpy(host, src, floats * sizeof(float), hipMemcpyDeviceToHost));
+  return set_device(r);
 }
 
 int ovr_hip_get_macrocells(ovr_hip_renderer* r, int32_t dims[3], float* minmax_host, float* majorant_host, size_t capacity_cells)

@@ -909,6 +909,17 @@ __device__ __forceinline__ void write_pixel(const RayMarchParams& P, unsigned in
   float4* fb = reinterpret_cast<float4*>(P.rgba) + pixel_index;
   if (P.accumulate) {
     float4* ac = reinterpret_cast<float4*>(P.accum) + pixel_index;
+    if (P.accum_half && (P.frame_index & 1) == 0) { // convergence estimate: H = the sum of the even-numbered frames, kept exactly as A is
+      float4* hp = reinterpret_cast<float4*>(P.accum_half) + pixel_index;
+      if (P.frame_index == 2) {
+        *hp = out;
+      }
+      else {
+        float4 h = *hp;
+        h.x += out.x; h.y += out.y; h.z += out.z; h.w += out.w;
+        *hp = h;
+      }
+    }
     if (P.frame_index == 1) {
       *ac = out;
     }
@@ -1857,7 +1868,8 @@ constexpr int kReduceBlocks = 64;
 hipError_t launch_composite(const RayMarchParams& q, dim3 grid, hipStream_t stream);
 hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream);
 hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, const unsigned int* shade_partials, int n_shade_blocks,
-                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream);
+                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream,
+                                  unsigned int* conv_asked = nullptr);
 
 inline dim3 raymarch_grid(const RayMarchParams& p)
 {
@@ -1931,7 +1943,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
     if (p.block_counters && p.counters) {
       if (!p.publish || p.zero_first)
         if ((e = hipMemsetAsync(p.counters, 0, 8 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
-      if ((e = launch_reduce_counters(p.block_counters, (int)raymarch_grid_blocks(p), nullptr, 0, p.counters, nullptr, p.publish, p.reduce_done, stream)) != hipSuccess) return e;
+      if ((e = launch_reduce_counters(p.block_counters, (int)raymarch_grid_blocks(p), nullptr, 0, p.counters, nullptr, p.publish, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e;
     }
     return hipGetLastError();
   }
@@ -1981,7 +1993,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
       if (grid.x > 0 && (e = launch_composite(q, grid, stream)) != hipSuccess) return e;
       if (p.block_counters && p.counters)
         if ((e = launch_reduce_counters(p.block_counters, (int)raymarch_grid_blocks(p), (const unsigned int*)p.pool.shade_counters, shade_grid_blocks(p), p.counters,
-                                        p.pool.ctrl, g == p.spp - 1 ? p.publish : nullptr, p.reduce_done, stream)) != hipSuccess) return e; // the frame's last generation publishes
+                                        p.pool.ctrl, g == p.spp - 1 ? p.publish : nullptr, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e; // the frame's last generation publishes
     }
     return hipGetLastError();
   }

@@ -125,6 +125,7 @@ struct RayMarchParams {
   float* rgba;   // W*H*4
   float* grad;   // W*H*3 (may be null)
   float* accum;  // W*H*4 (may be null when !accumulate)
+  float* accum_half; // W*H*4: the sum of the even-numbered frames (convergence estimate); null = the estimate is off
   int width, height;
   int frame_index;  // 1-based
   int accumulate;
@@ -178,6 +179,9 @@ struct RayMarchParams {
   unsigned long long* publish;
   unsigned int* reduce_done;
   int zero_first;
+  // convergence estimate: the publishing reduction leaves here (device memory) the most chunks any sub-pool was asked for in the frame - 0 without a
+  // pool - so that the kernels launched BEHIND the frame can tell an attempt that overflowed the pool (it wrote no pixel) from a complete frame; null = off
+  unsigned int* conv_asked;
   const float* majorant;        // per-macrocell max TF opacity: empty-space skipping (null = off)
   const unsigned char* occupancy; // per 4^3 macrocells: majorant > 0 in one of them or next to them (set with majorant)
   const unsigned char* occupancy_fine; // the same per macrocell (primary rays refine their skip interval with it)
@@ -208,6 +212,42 @@ hipError_t launch_schedule(const RayMarchParams& p, const unsigned int* src, uns
                            hipStream_t stream);
 // zero the pixels (RGBA, gradient layer, optionally the accumulation buffer) of `n` blocks that are not launched: what their rays' miss would write
 hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* blocks, unsigned int n, int clear_accum, hipStream_t stream);
+
+// ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
+// Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:
+//   m = A / n, h = H / (n / 2) per channel; d = sum of |m - h| over r, g, b, a; s = r + g + b + a of m; e = s > 0 ? d / sqrt(s) : 0
+//   E_b = (pairwise tree over the lanes of e) / (pixels of the block that this renderer owns)
+// block_error / block_frames are indexed by + bx + by * blocks_x; block_frames: the even frame of the block's estimate, negated once the block is retired, 0 = none yet.
+// words (device): [0] largest E_b of the blocks estimated by this launch, as a bit pattern (non-negative floats order like unsigned integers); the publishing
+// kernel reads and zeroes it; [1] the same over the blocks retired since the accumulation began; [2] RayMarchParams::conv_asked.
+// publish (pinned host memory, 4 words): { frame error bits, active entries, retired entries, n }
+struct ConvergenceParams {
+  const float* accum;       // A
+  const float* accum_half;  // H
+  const float* grad;        // the gradient layer frame n was rendered into ...
+  float* grad_keep;         // ... whose pixels a block keeps when it retires (adaptive only)
+  int width, height, frame_index;
+  int rank, world, tile_w, tile_h;
+  int blocks_x;
+  int adaptive;             // 1: blocks with E_b <= threshold are retired
+  float threshold;
+  const unsigned int* sorted; // the launch list in its sorted order (launch_schedule): its first n_work entries get work
+  unsigned int n_work;
+  const unsigned int* active; // the entries marched by frame n (== sorted while nothing is retired)
+  unsigned int n_active;
+  unsigned int* active_out;   // adaptive: the entries still active after this estimate, in the order of `sorted` ...
+  unsigned int* retired_out;  // ... and the retired ones
+  unsigned int* counts;       // workspace: ceil(n_work / 1024) words
+  float* block_error;
+  int* block_frames;
+  unsigned int* words;
+  unsigned int sub_capacity;  // words[2] > sub_capacity: the attempt overflowed the request pool - nothing is estimated, retired or published
+  unsigned int* publish;
+};
+hipError_t launch_convergence(const ConvergenceParams& c, hipStream_t stream);
+// retired blocks: RGBA = A / n_b, gradient layer = what the block kept, into the set p renders into
+hipError_t launch_resolve_blocks(const RayMarchParams& p, const unsigned int* retired, unsigned int n, const int* block_frames, const float* grad_keep, int blocks_x,
+                                 hipStream_t stream);
 
 // linear (x fastest) -> bricked layout; src may be any reference ValueType, dst is laid out as vd.type says (the VoxelType
 // chosen by device_voxel_type() or one of its replicas).  z0/nz_chunk allow chunked uploads from host staging.

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void composite_kernel(const RayMarchParams 
 // atomic each (integer sums: the result does not depend on the order); counters are zeroed by a memset node before
 __global__ __launch_bounds__(256) void reduce_counters_kernel(const unsigned int* __restrict__ partials, int n_blocks, const unsigned int* __restrict__ shade_partials,
                                                              int n_shade_blocks, unsigned long long* counters, unsigned int* pool_ctrl,
-                                                             unsigned long long* publish, unsigned int* done)
+                                                             unsigned long long* publish, unsigned int* done, unsigned int* conv_asked)
 {
   if (pool_ctrl && blockIdx.x == 0 && threadIdx.x < 64) { // most chunks any sub-pool was asked for in any generation (kPoolSubs == 64: one wave)
     unsigned int v = threadIdx.x < (unsigned int)kPoolSubs ? pool_ctrl[32u * (threadIdx.x + 1u)] : 0u;
@@ -149,9 +149,12 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(const unsigned int
   unsigned int* pub_ctrl = reinterpret_cast<unsigned int*>(publish + 8);
   if (pool_ctrl)
     for (int i = threadIdx.x; i < kPoolCtrlWords; i += 256) {
-      pub_ctrl[i] = __hip_atomic_load(&pool_ctrl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned int w = __hip_atomic_load(&pool_ctrl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      pub_ctrl[i] = w;
       pool_ctrl[i] = 0u;
+      if (conv_asked && i == 32 * (kPoolSubs + 1)) *conv_asked = w; // for the convergence kernels behind this frame (RayMarchParams::conv_asked)
     }
+  else if (conv_asked && threadIdx.x == 0) *conv_asked = 0u;
   if (threadIdx.x == 0) *done = 0u;
 }
 // ------------------------------------------------------------------------------------------------------------------
@@ -361,11 +364,182 @@ __global__ __launch_bounds__(256) void clear_blocks_kernel(const RayMarchParams 
   reinterpret_cast<float4*>(P.rgba)[pi] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (P.grad) { float* g = P.grad + 3 * pi; g[0] = 0.f; g[1] = 0.f; g[2] = 0.f; }
   if (clear_accum && P.accum) reinterpret_cast<float4*>(P.accum)[pi] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (clear_accum && P.accum_half) reinterpret_cast<float4*>(P.accum_half)[pi] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* blocks, unsigned int n, int clear_accum, hipStream_t stream)
 {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(clear_blocks_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, p, blocks, n, clear_accum);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// convergence estimate and adaptive refinement (ConvergenceParams, ovr_hip_kernels.h)
+//   convergence_kernel      one wave per block marched by the even frame n: E_b, the block's state, the maxima; a block that retires keeps its gradient pixels
+//   convergence_count /     (adaptive) stable compaction of the SORTED launch list by the blocks' states into the active and the retired list: per-workgroup
+//   convergence_scatter     counts, then every workgroup adds up the counts in front of it (as schedule_hist / schedule_scatter do); workgroup 0 publishes
+//   convergence_publish     (estimate only) one wave publishes
+//   resolve_blocks_kernel   every frame after a retirement: a retired block's pixels are A / n_b and the gradient pixels it kept
+// Kernel boundaries order everything; all of them return at once behind an attempt that overflowed the request pool (no pixel was written: A and H are
+// those of the frame before, the host renders the frame again and these kernels with it).
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool convergence_attempt_void(const ConvergenceParams& C) { return C.words[2] > C.sub_capacity; }
+
+__global__ __launch_bounds__(256) void convergence_kernel(const ConvergenceParams C)
+{
+  const unsigned int i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= C.n_active) return; // wave-uniform
+  if (convergence_attempt_void(C)) return;
+  const int lane = threadIdx.x & 63;
+  const unsigned int ent = C.active[i];
+  const int bx = (int)(ent & 0xffffu), by = (int)(ent >> 16);
+  const int ix = bx * 8 + (lane & 7), iy = by * 8 + (lane >> 3);
+  bool present = ix < C.width && iy < C.height;
+  if (C.world > 1 && present) present = ((ix / C.tile_w + iy / C.tile_h) % C.world) == C.rank; // assign_pixel_quad's ownership test
+  const size_t pi = (size_t)(present ? ix : 0) + (size_t)(present ? iy : 0) * (size_t)C.width;
+  float e = 0.f;
+  if (present) {
+    const float4 a = reinterpret_cast<const float4*>(C.accum)[pi], h = reinterpret_cast<const float4*>(C.accum_half)[pi];
+    const float fn = (float)C.frame_index, fh = (float)(C.frame_index / 2);
+    const float mr = a.x / fn, mg = a.y / fn, mb = a.z / fn, ma = a.w / fn;
+    const float hr = h.x / fh, hg = h.y / fh, hb = h.z / fh, ha = h.w / fh;
+    const float d = ((fabsf(mr - hr) + fabsf(mg - hg)) + fabsf(mb - hb)) + fabsf(ma - ha);
+    const float s = ((mr + mg) + mb) + ma;
+    e = s > 0.f ? d / sqrtf(s) : 0.f;
+  }
+  const int count = (int)__popcll(__ballot(present));
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) e += __shfl_xor(e, off); // the balanced pairwise tree over the lane index: the same value in every lane
+  const float E = count > 0 ? e / (float)count : 0.f;
+  const bool retire = C.adaptive != 0 && E <= C.threshold;
+  if (lane == 0) {
+    const size_t b = (size_t)bx + (size_t)by * (size_t)C.blocks_x;
+    C.block_error[b] = E;
+    C.block_frames[b] = retire ? -C.frame_index : C.frame_index;
+    // a maximum only grows: a block that cannot raise what the word already shows (0 for every block of a static scene) sends no atomic - tens of
+    // thousands of atomics on one address would serialise in L2; a stale read only costs an atomic that changes nothing
+    unsigned int* w = &C.words[retire ? 1 : 0];
+    const unsigned int bits = __float_as_uint(E);
+    if (bits > __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(w, bits);
+  }
+  if (retire && present) {
+    const float* g = C.grad + 3 * pi;
+    float* k = C.grad_keep + 3 * pi;
+    k[0] = g[0]; k[1] = g[1]; k[2] = g[2];
+  }
+}
+
+__device__ __forceinline__ bool convergence_entry_active(const ConvergenceParams& C, unsigned int ent)
+{
+  return C.block_frames[(size_t)(ent & 0xffffu) + (size_t)(ent >> 16) * (size_t)C.blocks_x] >= 0;
+}
+
+__global__ __launch_bounds__(1024) void convergence_count_kernel(const ConvergenceParams C)
+{
+  if (convergence_attempt_void(C)) return;
+  __shared__ unsigned int wave_count[16];
+  const unsigned int i = blockIdx.x * 1024u + threadIdx.x;
+  const bool keep = i < C.n_work && convergence_entry_active(C, C.sorted[i]);
+  const unsigned long long m = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = (unsigned int)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int t = 0u;
+    for (int w = 0; w < 16; ++w) t += wave_count[w];
+    C.counts[blockIdx.x] = t;
+  }
+}
+
+__device__ __forceinline__ void convergence_publish(const ConvergenceParams& C, unsigned int n_active)
+{
+  C.publish[0] = max(C.words[0], C.words[1]);
+  C.publish[1] = n_active;
+  C.publish[2] = C.n_work - n_active;
+  C.publish[3] = (unsigned int)C.frame_index;
+  C.words[0] = 0u; // the next estimate starts from 0; the retired blocks' maximum stays
+}
+
+__global__ __launch_bounds__(1024) void convergence_scatter_kernel(const ConvergenceParams C)
+{
+  if (convergence_attempt_void(C)) return;
+  __shared__ unsigned int wave_base[16];
+  __shared__ unsigned int before_s, total_s;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0) { // the active entries of the workgroups in front of this one, and of all of them
+    unsigned int before = 0u, all = 0u;
+    for (unsigned int w = (unsigned int)lane; w < gridDim.x; w += 64u) {
+      const unsigned int c = C.counts[w];
+      before += w < blockIdx.x ? c : 0u;
+      all += c;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { before += __shfl_xor(before, off); all += __shfl_xor(all, off); }
+    if (lane == 0) { before_s = before; total_s = all; }
+  }
+  const unsigned int i = blockIdx.x * 1024u + threadIdx.x;
+  const bool valid = i < C.n_work;
+  const unsigned int ent = valid ? C.sorted[i] : 0u;
+  const bool keep = valid && convergence_entry_active(C, ent);
+  const unsigned long long m = __ballot(keep);
+  const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u)); // kept lanes below this one
+  if (lane == 0) wave_base[wave] = (unsigned int)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int run = before_s;
+    for (int w = 0; w < 16; ++w) { const unsigned int t = wave_base[w]; wave_base[w] = run; run += t; }
+    if (blockIdx.x == 0) convergence_publish(C, total_s);
+  }
+  __syncthreads();
+  if (!valid) return;
+  const unsigned int kept_before = wave_base[wave] + rank; // active entries in front of entry i: both lists keep the sorted order
+  if (keep) C.active_out[kept_before] = ent;
+  else C.retired_out[i - kept_before] = ent;
+}
+
+__global__ __launch_bounds__(64) void convergence_publish_kernel(const ConvergenceParams C)
+{
+  if (convergence_attempt_void(C)) return;
+  if (threadIdx.x == 0) convergence_publish(C, C.n_work);
+}
+
+hipError_t launch_convergence(const ConvergenceParams& c, hipStream_t stream)
+{
+  if (c.n_active > 0) hipLaunchKernelGGL(convergence_kernel, dim3((c.n_active + 3u) / 4u), dim3(256), 0, stream, c);
+  if (c.adaptive && c.n_work > 0) {
+    const dim3 grid((c.n_work + 1023u) / 1024u);
+    hipLaunchKernelGGL(convergence_count_kernel, grid, dim3(1024), 0, stream, c);
+    hipLaunchKernelGGL(convergence_scatter_kernel, grid, dim3(1024), 0, stream, c);
+  }
+  else hipLaunchKernelGGL(convergence_publish_kernel, dim3(1), dim3(64), 0, stream, c);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void resolve_blocks_kernel(const RayMarchParams P, const unsigned int* __restrict__ retired, unsigned int n, const int* __restrict__ block_frames,
+                                                            const float* __restrict__ grad_keep, int blocks_x)
+{
+  const unsigned int i = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int lane = threadIdx.x & 63;
+  const unsigned int e = retired[i];
+  const int ix = (int)(e & 0xffffu) * 8 + (lane & 7), iy = (int)(e >> 16) * 8 + (lane >> 3);
+  bool active = ix < P.width && iy < P.height;
+  if (P.world > 1 && active) active = ((ix / P.tile_w + iy / P.tile_h) % P.world) == P.rank;
+  if (!active) return;
+  const float fn = (float)(-block_frames[(size_t)(e & 0xffffu) + (size_t)(e >> 16) * (size_t)blocks_x]); // n_b: the frame the block retired after
+  const size_t pi = (size_t)ix + (size_t)iy * (size_t)P.width;
+  const float4 a = reinterpret_cast<const float4*>(P.accum)[pi];
+  reinterpret_cast<float4*>(P.rgba)[pi] = make_float4(a.x / fn, a.y / fn, a.z / fn, a.w / fn); // write_pixel's expression
+  if (P.grad) {
+    const float* k = grad_keep + 3 * pi;
+    float* g = P.grad + 3 * pi;
+    g[0] = k[0]; g[1] = k[1]; g[2] = k[2];
+  }
+}
+hipError_t launch_resolve_blocks(const RayMarchParams& p, const unsigned int* retired, unsigned int n, const int* block_frames, const float* grad_keep, int blocks_x,
+                                 hipStream_t stream)
+{
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(resolve_blocks_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, p, retired, n, block_frames, grad_keep, blocks_x);
   return hipGetLastError();
 }
 
@@ -480,10 +654,11 @@ hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream)
 }
 
 hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, const unsigned int* shade_partials, int n_shade_blocks,
-                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream)
+                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream,
+                                  unsigned int* conv_asked)
 {
   hipLaunchKernelGGL(reduce_counters_kernel, dim3(kReduceBlocks), dim3(256), 0, stream, partials, n_blocks, shade_partials, n_shade_blocks, counters, pool_ctrl,
-                     done ? publish : nullptr, done);
+                     done ? publish : nullptr, done, conv_asked);
   return hipGetLastError();
 }
 

@@ -114,6 +114,7 @@ class DeviceHIP:
         self.variance = float("inf")          # renderer.h:287
         self._fbsize = (0, 0)
         self._keep = []                        # keeps ctypes buffers alive across calls
+        self._convergence_mode = L.CONVERGENCE_OFF
 
     # ---- lifetime -------------------------------------------------------------------------------------------
     def close(self):
@@ -233,6 +234,36 @@ class DeviceHIP:
         (general, thin, thin transposed, quad).  Frames are bit-identical."""
         L.check(self._lib.ovr_hip_set_layout_choice(self._h, int(choice)))
 
+    def set_convergence(self, mode, threshold=0.0):
+        """convergence estimate (include/ovr_hip.h, convergence.py): 0 off, 1 estimate - frames unchanged, render() stores the frame error in
+        `variance` -, 2 adaptive - 8x8 blocks whose error is <= threshold are retired: no longer marched, shown as their mean.  Applied at commit;
+        resets the accumulation."""
+        L.check(self._lib.ovr_hip_set_convergence(self._h, int(mode), float(threshold)))
+        self._convergence_mode = int(mode)
+
+    def convergence(self):
+        """ovr_hip_convergence of the last frame: error (inf while valid == 0), threshold, mode, valid, frames, blocks, active_blocks, retired_blocks"""
+        c = L.Convergence()
+        L.check(self._lib.ovr_hip_get_convergence(self._h, C.byref(c)))
+        return c
+
+    def convergence_blocks(self, member=0):
+        """(E_b[by, bx] float32, n_b[by, bx] int32 - negative when the block is retired) of one member (known-answer tests)"""
+        dims = (C.c_int32 * 2)()
+        L.check(self._lib.ovr_hip_get_convergence_blocks(self._h, int(member), dims, None, None, 0))
+        err = np.zeros((dims[1], dims[0]), np.float32)
+        frames = np.zeros((dims[1], dims[0]), np.int32)
+        L.check(self._lib.ovr_hip_get_convergence_blocks(self._h, int(member), dims, err.ctypes.data_as(C.POINTER(C.c_float)),
+                                                         frames.ctypes.data_as(C.POINTER(C.c_int32)), err.size))
+        return err, frames
+
+    def accumulation(self, which=0, member=0):
+        """the accumulation buffer A (which = 0) or H, the sum of the even-numbered frames (1), as (H, W, 4) float32 (known-answer tests)"""
+        w, h = self._fbsize
+        out = np.zeros((h, w, 4), np.float32)
+        L.check(self._lib.ovr_hip_get_accumulation(self._h, int(member), int(which), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
     def set_grid_convention(self, convention):
         L.check(self._lib.ovr_hip_set_grid_convention(self._h, int(convention)))
 
@@ -312,6 +343,9 @@ class DeviceHIP:
     def render(self):
         L.check(self._lib.ovr_hip_render(self._h))
         self.variance = 0.0  # device_impl.cpp:266
+        if self._convergence_mode != L.CONVERGENCE_OFF:  # the frame error, as the reference's OSPRay device fills it in (renderer.h:124-127)
+            c = self.convergence()
+            self.variance = float(c.error) if c.valid else float("inf")
 
     def render_async(self):
         L.check(self._lib.ovr_hip_render_async(self._h))

@@ -63,7 +63,15 @@ bool load_noise_tile(ovr_hip_renderer* h)
 class DeviceHIP : public ovr::MainRenderer {
 public:
   DeviceHIP() = default;
-  ~DeviceHIP() override { ovr_hip_destroy(h); }
+  ~DeviceHIP() override
+  {
+    if (h && convergence_mode != OVR_HIP_CONVERGENCE_OFF && !(std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0')) {
+      ovr_hip_convergence c;
+      if (ovr_hip_get_convergence(h, &c) == 0)
+        std::fprintf(stderr, "[hip] convergence: error %g after %d frames, %d of %d blocks retired\n", (double)c.error, c.frames, c.retired_blocks, c.blocks);
+    }
+    ovr_hip_destroy(h);
+  }
   DeviceHIP(const DeviceHIP&) = delete;
   DeviceHIP& operator=(const DeviceHIP&) = delete;
 
@@ -114,6 +122,14 @@ public:
     // nothing behind this interface reads per-phase device times: no events between the frame's kernels (OVR_HIP_PHASE_TIMING=1 keeps them)
     const char* phases = std::getenv("OVR_HIP_PHASE_TIMING");
     check(ovr_hip_set_phase_timing(h, (phases && phases[0] == '1') ? 1 : 0));
+    // MainRenderer::variance (ovr/renderer.h:124-127,287) - what renderapp shows in its title bar and renderbatch's progressive loop stops on - is the frame
+    // error of the convergence estimate when OVR_HIP_CONVERGENCE=1 (estimate only: same frames) or =2 (blocks whose error is <= OVR_HIP_CONVERGENCE_THRESHOLD,
+    // default 0, are retired: no longer marched).  Unset: 0, like the reference's OptiX device (device_impl.cpp:266)
+    if (const char* cv = std::getenv("OVR_HIP_CONVERGENCE")) {
+      convergence_mode = std::atoi(cv);
+      const char* th = std::getenv("OVR_HIP_CONVERGENCE_THRESHOLD");
+      check(ovr_hip_set_convergence(h, convergence_mode, th ? (float)std::atof(th) : 0.f));
+    }
     commit();
   }
 
@@ -161,6 +177,11 @@ public:
     const auto end = std::chrono::high_resolution_clock::now();
     render_time += std::chrono::duration_cast<std::chrono::milliseconds>(end - start).count();
     variance = 0.f; // device_impl.cpp:266
+    if (convergence_mode != OVR_HIP_CONVERGENCE_OFF) {
+      ovr_hip_convergence c;
+      check(ovr_hip_get_convergence(h, &c));
+      variance = c.error; // +inf until the second accumulated frame
+    }
   }
 
   // Impl::mapframe (device_impl.cpp:271-281).  The reference hands out device pointers (DEVICE_CUDA), which only exist
@@ -182,6 +203,7 @@ public:
 private:
   ovr_hip_renderer* h = nullptr;
   bool have_noise = false;
+  int convergence_mode = OVR_HIP_CONVERGENCE_OFF;
 };
 
 } // namespace

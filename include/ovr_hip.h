@@ -260,6 +260,42 @@ int ovr_hip_get_convergence_blocks(ovr_hip_renderer* r, int32_t member, int32_t 
 /* the accumulation buffers, W*H*4 floats: which = 0: A, 1: H (ESTATE while the mode is OFF) */
 int ovr_hip_get_accumulation(ovr_hip_renderer* r, int32_t member, int32_t which, float* host, size_t capacity_floats);
 
+/* Pull-push reconstruction (added within ABI v11: new entry points and a new struct only, nothing that existed changed its layout or meaning;
+ * a library without them fails to load in _lib.py by the missing symbols) - pull-push reconstruction of sparse-sampled frames.  A frame rendered with sparse sampling on is mostly holes: the pixels
+ * the mask drops are exactly 0, and with accumulation a pixel sampled in k of n frames shows A / n, dimmed by k / n.  With the mode FILL such a frame is
+ * completed on the device before anything maps it.  N(p) counts the frames that sampled pixel p (this frame alone without accumulation, since the last
+ * reset with it); with accumulation G accumulates the gradient layer of the sampled pixels as A accumulates RGBA.  Level 0 of a pyramid is
+ *     v0(p) = the framebuffer's pixel (without accumulation) or N > 0 ? (A / N, G / N) : 0;   w0(p) = N > 0 and all seven channels finite ? 1 : 0
+ * a PULL halves the resolution up to 1 x 1 - a texel is the mean of its valid children (pairwise sums, x first; invalid children contribute a selected
+ * +0) and is valid when one of them is - and a PUSH comes back down: a texel without data takes the bilinear interpolation (weights 0.75 / 0.25) of the
+ * completed coarser level, a texel with data keeps its value.  On level 0 every pixel with N > 0 keeps v0 bit for bit (a non-finite sample stays where it
+ * is and spreads nowhere), every other pixel is filled; RGBA and the gradient layer of the set the frame rendered into are written, so mapframe,
+ * mapframe_rgba8 / rgba16f and save_image see the filled frame.  open-volume-renderer_amd/reconstruction.py is this arithmetic in numpy, the normative
+ * text: the kernels agree with it bit for bit.
+ *   OFF   today's behaviour: no buffer, no launch
+ *   FILL  acts on frames rendered with sparse sampling on; a dense frame is bit-identical to OFF, with the same counters and launches
+ * Queued like every setter, applied at commit; every call resets the accumulation.  EINVAL: unknown mode.  ESTATE: FILL on a device group of more than one
+ * device (use ovr_hip_reconstruct_image on the assembled frame).  A renderer with an image shard (world > 1) leaves its frames alone (valid = 0). */
+#define OVR_HIP_RECONSTRUCT_OFF 0
+#define OVR_HIP_RECONSTRUCT_FILL 1
+int ovr_hip_set_reconstruction(ovr_hip_renderer* r, int32_t mode);
+
+typedef struct ovr_hip_reconstruction {
+  int32_t mode, valid;      /* valid: 1 when the last frame was reconstructed; 0: mode OFF, sparse sampling off, an image shard */
+  int32_t levels;           /* of the pyramid, the image (level 0) included; 0 while valid == 0 */
+  uint64_t sampled_pixels;  /* pixels with N > 0 */
+  uint64_t filled_pixels;   /* the others: W * H - sampled_pixels */
+  double reconstruct_ms;    /* device time of the reconstruction's kernels; measured only while phase timing is on (else 0); never part of kernel_ms */
+} ovr_hip_reconstruction;
+int ovr_hip_get_reconstruction(const ovr_hip_renderer* r, ovr_hip_reconstruction* out);
+/* for known-answer tests: N (W*H floats) and G (W*H*3 floats; ESTATE unless the last reconstructed frame accumulated).  ESTATE while the mode is OFF. */
+int ovr_hip_get_reconstruction_weights(ovr_hip_renderer* r, float* host, size_t capacity_floats);
+int ovr_hip_get_reconstruction_gradient(ovr_hip_renderer* r, float* host, size_t capacity_floats);
+/* the same kernels on a caller's device image, in place: rgba_device W*H*4 floats, grad_device W*H*3 floats or NULL, weight_device W*H floats
+ * (> 0 = sampled; not modified).  Stand-alone: needs no volume and no committed framebuffer; returns when the image is complete.  What the gathering
+ * rank of a multi-process run calls on the assembled frame. */
+int ovr_hip_reconstruct_image(ovr_hip_renderer* r, float* rgba_device, float* grad_device, const float* weight_device, int32_t width, int32_t height);
+
 /* replaces DeviceOptix7::Impl::commit (device_impl.cpp:113-197): applies every queued setter; any change resets
  * the accumulation (frame_index restarts at 1 on the next render). */
 int ovr_hip_commit(ovr_hip_renderer* r);

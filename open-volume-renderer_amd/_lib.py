@@ -20,6 +20,7 @@ GRID_CELL_CENTRED, GRID_VERTEX_CENTRED = 0, 1
 PIPELINE_AUTO, PIPELINE_IN_PLACE, PIPELINE_POOLED = 0, 1, 2
 JITTER_TEA, JITTER_BLUE_NOISE = 0, 1
 CONVERGENCE_OFF, CONVERGENCE_ESTIMATE, CONVERGENCE_ADAPTIVE = 0, 1, 2
+RECONSTRUCT_OFF, RECONSTRUCT_FILL = 0, 1
 LAYOUT_AUTO, LAYOUT_GENERAL, LAYOUT_THIN, LAYOUT_THIN_T, LAYOUT_QUAD = -1, 0, 1, 2, 3
 # the ABI these ctypes structures describe: load() refuses a library of another version (ovr_hip_get_stats would write past them)
 EXPECTED_ABI = 11
@@ -75,6 +76,17 @@ class Convergence(C.Structure):
         ("blocks", C.c_int32),
         ("active_blocks", C.c_int32),
         ("retired_blocks", C.c_int32),
+    ]
+
+
+class Reconstruction(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("valid", C.c_int32),
+        ("levels", C.c_int32),
+        ("sampled_pixels", C.c_uint64),
+        ("filled_pixels", C.c_uint64),
+        ("reconstruct_ms", C.c_double),
     ]
 
 
@@ -138,6 +150,11 @@ SYMBOLS = {
     "ovr_hip_get_convergence": (C.c_int, [_H, C.POINTER(Convergence)]),
     "ovr_hip_get_convergence_blocks": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), _F3, C.POINTER(C.c_int32), C.c_size_t]),
     "ovr_hip_get_accumulation": (C.c_int, [_H, C.c_int32, C.c_int32, _F3, C.c_size_t]),
+    "ovr_hip_set_reconstruction": (C.c_int, [_H, C.c_int32]),
+    "ovr_hip_get_reconstruction": (C.c_int, [_H, C.POINTER(Reconstruction)]),
+    "ovr_hip_get_reconstruction_weights": (C.c_int, [_H, _F3, C.c_size_t]),
+    "ovr_hip_get_reconstruction_gradient": (C.c_int, [_H, _F3, C.c_size_t]),
+    "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
 }
 
 _lib = None

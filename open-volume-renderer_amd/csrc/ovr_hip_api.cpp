@@ -231,6 +231,19 @@ struct ovr_hip_renderer {
   float conv_error = 0.f;
   int conv_frames = 0;
   unsigned int conv_active = 0, conv_retired = 0; // entries of the launch list that are marched / resolved (conv_active + conv_retired == n_work while adaptive)
+  // ---- pull-push reconstruction of sparse-sampled frames (ovr_hip_set_reconstruction).  Everything below exists only while the mode is FILL.
+  Queued<int> reconstruction;
+  float* d_recon_count = nullptr;        // N: per pixel, the frames that sampled it (W*H)
+  float* d_recon_grad = nullptr;         // G: the gradient layer of the sampled pixels, accumulated like A (W*H*3)
+  float4* d_recon_pyramid = nullptr;     // levels >= 1, two float4 per texel
+  unsigned int* d_recon_words = nullptr; // ReconParams::words (kReconWords)
+  unsigned int* h_recon = nullptr;       // pinned: ReconParams::publish
+  hipEvent_t ev_recon[2] = { nullptr, nullptr };
+  bool recon_frame = false;              // the frame in flight is reconstructed behind its last kernel
+  bool recon_timed = false;              // ... between ev_recon[0] and ev_recon[1]
+  bool recon_accumulated = false;        // the last reconstructed frame accumulated: G is defined
+  ReconParams recon{};
+  ovr_hip_reconstruction recon_info{};
   uint32_t* d_rgba8 = nullptr; // mapframe_rgba8: device and pinned host copy of the 8-bit frame
   uint32_t* h_rgba8 = nullptr;
   uint16_t* d_rgba16f = nullptr; // mapframe_rgba16f: the half frame of the EXR writer
@@ -392,6 +405,47 @@ int ensure_convergence(ovr_hip_renderer* r, bool lists)
   return 0;
 }
 
+// the reconstruction's buffers: gone with the mode, the framebuffer size or the renderer (ensure_reconstruction brings them back, zeroed)
+constexpr size_t kReconWords = 2 + 64;
+int free_reconstruction(ovr_hip_renderer* r)
+{
+  if (r->d_recon_count) HIP_TRY(hipFree(r->d_recon_count));
+  if (r->d_recon_grad) HIP_TRY(hipFree(r->d_recon_grad));
+  if (r->d_recon_pyramid) HIP_TRY(hipFree(r->d_recon_pyramid));
+  if (r->d_recon_words) HIP_TRY(hipFree(r->d_recon_words));
+  r->d_recon_count = r->d_recon_grad = nullptr;
+  r->d_recon_pyramid = nullptr;
+  r->d_recon_words = nullptr;
+  r->recon_frame = r->recon_accumulated = false;
+  r->recon_info = ovr_hip_reconstruction{};
+  r->recon_info.mode = r->reconstruction.current;
+  return 0;
+}
+
+int ensure_reconstruction(ovr_hip_renderer* r)
+{
+  const size_t n = std::max<size_t>(r->fb_pixels, 1);
+  if (!r->d_recon_count) {
+    HIP_TRY(hipMalloc((void**)&r->d_recon_count, n * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&r->d_recon_grad, n * 3 * sizeof(float)));
+    HIP_TRY(hipMemset(r->d_recon_count, 0, n * sizeof(float)));
+    HIP_TRY(hipMemset(r->d_recon_grad, 0, n * 3 * sizeof(float)));
+    ReconParams c{};
+    c.width = r->fbsize.current.w; c.height = r->fbsize.current.h;
+    const size_t texels = recon_plan(c);
+    HIP_TRY(hipMalloc((void**)&r->d_recon_pyramid, std::max<size_t>(texels, 1) * 2 * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&r->d_recon_words, kReconWords * sizeof(unsigned int)));
+    HIP_TRY(hipMemset(r->d_recon_words, 0, kReconWords * sizeof(unsigned int)));
+  }
+  if (!r->h_recon) {
+    HIP_TRY(hipHostMalloc((void**)&r->h_recon, 2 * sizeof(unsigned int), hipHostMallocDefault));
+    std::memset(r->h_recon, 0, 2 * sizeof(unsigned int));
+  }
+  for (int i = 0; i < 2; ++i)
+    if (!r->ev_recon[i]) HIP_TRY(hipEventCreate(&r->ev_recon[i]));
+  return 0;
+}
+
 int free_framebuffers(ovr_hip_renderer* r)
 {
   for (int i = 0; i < 2; ++i) {
@@ -404,6 +458,7 @@ int free_framebuffers(ovr_hip_renderer* r)
   if (r->d_accum) HIP_TRY(hipFree(r->d_accum));
   r->d_accum = nullptr;
   if (int e = free_convergence(r)) return e;
+  if (int e = free_reconstruction(r)) return e;
   if (r->d_rgba8) HIP_TRY(hipFree(r->d_rgba8));
   if (r->h_rgba8) HIP_TRY(hipHostFree(r->h_rgba8));
   r->d_rgba8 = nullptr; r->h_rgba8 = nullptr;
@@ -933,6 +988,10 @@ int enqueue_frame(ovr_hip_renderer* r)
   const bool accumulate = r->accumulate.current != 0;
   const bool sparse = r->sparse.current != 0;
   const size_t n = r->fb_pixels;
+  // ---- pull-push reconstruction: acts on sparse frames of a single renderer that owns the whole image
+  const bool recon_on = r->reconstruction.current == OVR_HIP_RECONSTRUCT_FILL && sparse && r->shard.current.world <= 1 && r->members.size() <= 1 && !r->leader;
+  if (recon_on)
+    if (int e = ensure_reconstruction(r)) return e;
   if (accumulate) { // device_impl.cpp:226-233
     if (r->fb_reset) {
       for (int i = 0; i < 2; ++i) {
@@ -948,6 +1007,10 @@ int enqueue_frame(ovr_hip_renderer* r)
       // the reference leaves the accumulation buffer as it is (device_impl.cpp:229-230 are commented out), which is
       // only sound because frame 1 overwrites it; sparse frames do not overwrite every pixel, so it is cleared here
       if (sparse) HIP_TRY(hipMemsetAsync(r->d_accum, 0, n * 4 * sizeof(float), st));
+      if (recon_on) { // N and G start over with A
+        HIP_TRY(hipMemsetAsync(r->d_recon_count, 0, std::max<size_t>(n, 1) * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(r->d_recon_grad, 0, std::max<size_t>(n, 1) * 3 * sizeof(float), st));
+      }
       r->fb_reset = false;
       r->frame_index = 0;
     }
@@ -957,6 +1020,7 @@ int enqueue_frame(ovr_hip_renderer* r)
       HIP_TRY(hipMemsetAsync(r->d_rgba[i], 0, n * 4 * sizeof(float), st));
       HIP_TRY(hipMemsetAsync(r->d_grad[i], 0, n * 3 * sizeof(float), st));
     }
+    if (recon_on) HIP_TRY(hipMemsetAsync(r->d_recon_count, 0, std::max<size_t>(n, 1) * sizeof(float), st)); // N is this frame's list alone
   }
   r->frame_index++;
 
@@ -967,6 +1031,11 @@ int enqueue_frame(ovr_hip_renderer* r)
     int* q = r->d_rect[r->cur];     // also outside the box's rectangle: such a set is mapped whole (found by tests/fuzz_states.py, seeds 61 / 62)
     q[0] = 0; q[1] = 0; q[2] = W; q[3] = H;
   }
+  if (recon_on) { // a filled frame is not 0 outside the box's rectangle: the set is mapped whole
+    int* q = r->d_rect[r->cur];
+    q[0] = 0; q[1] = 0; q[2] = W; q[3] = H;
+  }
+  r->recon_frame = recon_on;
   r->frame_set = r->cur;
   P.grad = r->d_grad[r->cur];
   P.accum = r->d_accum;
@@ -1182,6 +1251,7 @@ int enqueue_frame(ovr_hip_renderer* r)
     P.sparse_xy = r->d_sparse_xy;
     P.sparse_count = r->d_sparse_count;
     P.sparse_hint_pixels = r->sparse_prev_pixels;
+    if (recon_on) P.conv_asked = r->d_recon_words; // words[0]: an attempt that overflowed the request pool is not counted and not filled
   }
   // ---- shading pipeline: pooled (march -> shade -> composite) when it applies, else in place
   const int pipe = r->pipeline.current;
@@ -1260,6 +1330,27 @@ int launch_frame(ovr_hip_renderer* r)
     c.publish = r->h_conv;
     r->h_conv[3] = 0u; // (finish_frame_one expects this frame's number here)
     HIP_TRY(launch_convergence(c, st));
+  }
+  if (r->recon_frame) { // behind the frame's last kernel and its last event, like the estimate: kernel_ms stays the frame's own time
+    ReconParams& c = r->recon;
+    c = ReconParams{};
+    c.width = r->P.width; c.height = r->P.height;
+    (void)recon_plan(c);
+    c.rgba = r->P.rgba; c.grad = r->P.grad;
+    c.count = r->d_recon_count;
+    c.accum = r->P.accumulate ? r->d_accum : nullptr;
+    c.grad_sum = r->P.accumulate ? r->d_recon_grad : nullptr;
+    c.pyramid = r->d_recon_pyramid;
+    c.words = r->d_recon_words;
+    c.sub_capacity = r->P.pool.reqs ? r->P.pool.sub_capacity : 0xffffffffu;
+    c.publish = r->h_recon;
+    c.frame_index = r->P.frame_index;
+    r->h_recon[1] = 0u; // (finish_frame_one expects this frame's number here)
+    r->recon_timed = phases;
+    if (phases) HIP_TRY(hipEventRecord(r->ev_recon[0], st));
+    HIP_TRY(launch_recon_scatter(c, r->d_recon_count, r->P.accumulate ? r->d_recon_grad : nullptr, r->P.sparse_xy, r->P.sparse_count, st));
+    HIP_TRY(launch_reconstruct(c, st));
+    if (phases) HIP_TRY(hipEventRecord(r->ev_recon[1], st));
   }
   r->async_pending = true;
   return 0;
@@ -1445,6 +1536,21 @@ int finish_frame_one(ovr_hip_renderer* r)
       r->conv_active = r->h_conv[1];
       r->conv_retired = r->h_conv[2];
     }
+  }
+  r->recon_info = ovr_hip_reconstruction{};
+  r->recon_info.mode = r->reconstruction.current;
+  if (r->recon_frame) { // published by the reconstruction's last kernel
+    if (r->h_recon[1] != (unsigned int)r->frame_index) return fail(OVR_HIP_EDEVICE, "[hip] the reconstruction of the frame was not published");
+    r->recon_info.valid = 1;
+    r->recon_info.levels = r->recon.levels;
+    r->recon_info.sampled_pixels = r->h_recon[0];
+    r->recon_info.filled_pixels = (uint64_t)r->fb_pixels - r->recon_info.sampled_pixels;
+    if (r->recon_timed) {
+      float rm = 0.f;
+      HIP_TRY(hipEventElapsedTime(&rm, r->ev_recon[0], r->ev_recon[1]));
+      r->recon_info.reconstruct_ms = rm;
+    }
+    r->recon_accumulated = r->P.accumulate != 0;
   }
   if (r->d_trace) {
     if (const char* path = getenv("OVR_HIP_TRACE_FILE")) {
@@ -2073,6 +2179,8 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_data_range) (void)hipFree(r->d_data_range);
   if (r->h_counters) (void)hipHostFree(r->h_counters);
   if (r->h_conv) (void)hipHostFree(r->h_conv);
+  if (r->h_recon) (void)hipHostFree(r->h_recon);
+  for (int i = 0; i < 2; ++i) if (r->ev_recon[i]) (void)hipEventDestroy(r->ev_recon[i]);
   for (int i = 0; i < 4; ++i) if (r->ev[i]) (void)hipEventDestroy(r->ev[i]);
   if (r->pool.reqs) (void)hipFree(r->pool.reqs);
   if (r->pool.chunk_next) (void)hipFree(r->pool.chunk_next);
@@ -2434,6 +2542,17 @@ int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold)
   return 0;
 }
 
+int ovr_hip_set_reconstruction(ovr_hip_renderer* r, int32_t mode)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (mode != OVR_HIP_RECONSTRUCT_OFF && mode != OVR_HIP_RECONSTRUCT_FILL) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_reconstruction: unknown mode");
+  if (mode != OVR_HIP_RECONSTRUCT_OFF && (r->members.size() > 1 || r->leader))
+    return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_set_reconstruction: a device group of more than one device does not reconstruct its frames - call "
+                                "ovr_hip_reconstruct_image on the assembled frame");
+  { std::lock_guard<std::mutex> lk(r->mtx); r->reconstruction.set(mode); }
+  return 0;
+}
+
 int ovr_hip_set_focus(ovr_hip_renderer* r, float cx, float cy, float scale, float base_noise)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -2583,6 +2702,16 @@ int commit_one(ovr_hip_renderer* r)
       if (r->convergence.current.mode != before) { // OFF keeps no buffer; the other two allocate what they need with their next frame
         HIP_TRY(hipDeviceSynchronize());
         if (int e = free_convergence(r)) return e;
+      }
+    }
+  }
+  {
+    const int before = r->reconstruction.current;
+    if (r->reconstruction.update()) { // any call resets the accumulation; OFF keeps no buffer, FILL allocates with its next sparse frame
+      r->fb_reset = true;
+      if (r->reconstruction.current != before) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (int e = free_reconstruction(r)) return e;
       }
     }
   }
@@ -2865,6 +2994,69 @@ int ovr_hip_get_accumulation(ovr_hip_renderer* r, int32_t member, int32_t which,
   HIP_TRY(hipStreamSynchronize(m->stream()));
   HIP_TRY(hipMemcpy(host, src, floats * sizeof(float), hipMemcpyDeviceToHost));
   return set_device(r);
+}
+
+int ovr_hip_get_reconstruction(const ovr_hip_renderer* r, ovr_hip_reconstruction* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_reconstruction: null argument");
+  if (r->async_pending) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_reconstruction: a frame is still in flight (call ovr_hip_sync)");
+  *out = r->recon_info;
+  out->mode = r->reconstruction.current;
+  return 0;
+}
+
+namespace {
+int recon_read(ovr_hip_renderer* r, const char* what, bool gradient, float* host, size_t capacity_floats)
+{
+  if (!r || !host) return fail(OVR_HIP_EINVAL, std::string("[hip] ") + what + ": null argument");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  const size_t floats = r->fb_pixels * (gradient ? 3 : 1);
+  if (capacity_floats < floats) return fail(OVR_HIP_EINVAL, std::string("[hip] ") + what + ": output too small");
+  const float* src = gradient ? r->d_recon_grad : r->d_recon_count;
+  if (!src) return fail(OVR_HIP_ESTATE, std::string("[hip] ") + what + ": no frame was rendered with the reconstruction on");
+  if (gradient && !r->recon_accumulated) return fail(OVR_HIP_ESTATE, std::string("[hip] ") + what + ": the last reconstructed frame did not accumulate");
+  if (floats == 0) return 0;
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  HIP_TRY(hipMemcpy(host, src, floats * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+} // namespace
+
+int ovr_hip_get_reconstruction_weights(ovr_hip_renderer* r, float* host, size_t capacity_floats)
+{
+  return recon_read(r, "ovr_hip_get_reconstruction_weights", false, host, capacity_floats);
+}
+
+int ovr_hip_get_reconstruction_gradient(ovr_hip_renderer* r, float* host, size_t capacity_floats)
+{
+  return recon_read(r, "ovr_hip_get_reconstruction_gradient", true, host, capacity_floats);
+}
+
+int ovr_hip_reconstruct_image(ovr_hip_renderer* r, float* rgba_device, float* grad_device, const float* weight_device, int32_t width, int32_t height)
+{
+  if (!r || !rgba_device || !weight_device) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_reconstruct_image: null argument");
+  if (width < 0 || height < 0 || (int64_t)width * (int64_t)height > (int64_t)0x7fffffff) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_reconstruct_image: bad image size");
+  if (width == 0 || height == 0) return 0;
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  ReconParams c{};
+  c.width = width; c.height = height;
+  const size_t texels = recon_plan(c);
+  float4* pyramid = nullptr;
+  unsigned int* words = nullptr;
+  HIP_TRY(hipMalloc((void**)&pyramid, std::max<size_t>(texels, 1) * 2 * sizeof(float4)));
+  if (hipMalloc((void**)&words, kReconWords * sizeof(unsigned int)) != hipSuccess) { (void)hipFree(pyramid); return fail(OVR_HIP_EDEVICE, "[hip] ovr_hip_reconstruct_image: out of device memory"); }
+  hipStream_t st = r->stream();
+  c.rgba = rgba_device; c.grad = grad_device; c.count = weight_device;
+  c.pyramid = pyramid; c.words = words; c.sub_capacity = 0xffffffffu;
+  hipError_t e = hipMemsetAsync(words, 0, kReconWords * sizeof(unsigned int), st);
+  if (e == hipSuccess) e = launch_reconstruct(c, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(pyramid);
+  (void)hipFree(words);
+  if (e != hipSuccess) return fail(OVR_HIP_EDEVICE, std::string("[hip] ovr_hip_reconstruct_image: ") + hipGetErrorString(e));
+  return 0;
 }
 
 int ovr_hip_get_macrocells(ovr_hip_renderer* r, int32_t dims[3], float* minmax_host, float* majorant_host, size_t capacity_cells)

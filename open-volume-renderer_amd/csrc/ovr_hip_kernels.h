@@ -249,6 +249,39 @@ hipError_t launch_convergence(const ConvergenceParams& c, hipStream_t stream);
 hipError_t launch_resolve_blocks(const RayMarchParams& p, const unsigned int* retired, unsigned int n, const int* block_frames, const float* grad_keep, int blocks_x,
                                  hipStream_t stream);
 
+// ---- pull-push reconstruction of sparse-sampled frames (include/ovr_hip.h ovr_hip_set_reconstruction; DESIGN.md section 10;
+// open-volume-renderer_amd/reconstruction.py is the arithmetic in numpy and the kernels are held to it bit for bit)
+// Level 0 is the image: seven channels per pixel (RGBA + gradient layer; four when grad is null) and the per-pixel sample count N.  Levels >= 1 live in
+// `pyramid`, two float4 per texel: { r, g, b, a }, { gx, gy, gz, weight }; level l starts at texel level_offset[l] and has level_w[l] x level_h[l] texels.
+// words (device): [0] RayMarchParams::conv_asked of the frame in front (an attempt that overflowed the request pool wrote no pixel: nothing is counted,
+// filled or published behind it), [1] the pixels with N > 0, counted by the first pull pass; the last kernel publishes and zeroes it.
+// publish (pinned host memory, 2 words): { pixels with N > 0, frame_index }
+constexpr int kReconMaxLevels = 20;
+struct ReconParams {
+  float* rgba;              // W*H*4: read (level 0 without accumulation) and written in place
+  float* grad;              // W*H*3 or null
+  const float* count;       // N, W*H: > 0 = the pixel was sampled
+  const float* accum;       // A (W*H*4): non-null = level 0 is A / N and G / N, not the framebuffer's pixel
+  const float* grad_sum;    // G (W*H*3)
+  int width, height;
+  int levels;               // including level 0; the last one is 1 x 1
+  int top;                  // the first level of at most 64 x 64 texels: it and everything above is pulled and pushed by one workgroup
+  int level_w[kReconMaxLevels], level_h[kReconMaxLevels];
+  unsigned int level_offset[kReconMaxLevels];
+  float4* pyramid;
+  unsigned int* words;
+  unsigned int sub_capacity; // words[0] > sub_capacity: the attempt overflowed the request pool
+  unsigned int* publish;     // may be null
+  int frame_index;
+};
+// fills levels, top, level_w / level_h / level_offset for width x height; returns the texels of the pyramid (levels >= 1)
+size_t recon_plan(ReconParams& c);
+// the frame's sample list (x, y pairs; *list_count = int32 elements, as launch_sparse_mask leaves it): N = 1 at the listed pixels (count cleared by the
+// caller), or with grad_sum: N += 1 and G += the gradient pixel
+hipError_t launch_recon_scatter(const ReconParams& c, float* count, float* grad_sum, const int32_t* list_xy, const unsigned long long* list_count, hipStream_t stream);
+hipError_t launch_reconstruct(const ReconParams& c, hipStream_t stream);
+int recon_launch_count(const ReconParams& c); // kernels launch_reconstruct enqueues
+
 // linear (x fastest) -> bricked layout; src may be any reference ValueType, dst is laid out as vd.type says (the VoxelType
 // chosen by device_voxel_type() or one of its replicas).  z0/nz_chunk allow chunked uploads from host staging.
 int device_voxel_type(int ovr_value_type);

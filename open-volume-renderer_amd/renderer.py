@@ -264,6 +264,50 @@ class DeviceHIP:
         L.check(self._lib.ovr_hip_get_accumulation(self._h, int(member), int(which), out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
 
+    def set_reconstruction(self, mode):
+        """pull-push hole filling of sparse-sampled frames (include/ovr_hip.h, reconstruction.py): 0 off, 1 fill - a frame rendered with sparse
+        sampling on is completed on the device before anything maps it; dense frames are unchanged.  Applied at commit; resets the accumulation."""
+        L.check(self._lib.ovr_hip_set_reconstruction(self._h, int(mode)))
+
+    def reconstruction(self):
+        """ovr_hip_reconstruction of the last frame: mode, valid, levels, sampled_pixels, filled_pixels, reconstruct_ms"""
+        c = L.Reconstruction()
+        L.check(self._lib.ovr_hip_get_reconstruction(self._h, C.byref(c)))
+        return c
+
+    def reconstruction_weights(self):
+        """N as (H, W) float32: how many frames of the running accumulation (this frame alone without accumulation) sampled each pixel"""
+        w, h = self._fbsize
+        out = np.zeros((h, w), np.float32)
+        L.check(self._lib.ovr_hip_get_reconstruction_weights(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def reconstruction_gradient(self):
+        """G as (H, W, 3) float32: the gradient layer of the sampled pixels, accumulated like A (accumulating frames only)"""
+        w, h = self._fbsize
+        out = np.zeros((h, w, 3), np.float32)
+        L.check(self._lib.ovr_hip_get_reconstruction_gradient(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def reconstruct_image(self, rgba, grad, weight):
+        """fills the holes of a device image in place with the renderer's kernels: rgba (H, W, 4), grad (H, W, 3) or None, weight (H, W) - > 0 = sampled,
+        not modified -, contiguous float32 torch tensors on this renderer's device.  Returns (rgba, grad)."""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        for name, t, last in (("rgba", rgba, 4), ("grad", grad, 3), ("weight", weight, None)):
+            if t is None and name == "grad":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError(f"reconstruct_image: {name} must be a contiguous float32 tensor on {dev}")
+            if last is not None and (t.dim() != 3 or t.shape[2] != last):
+                raise RuntimeError(f"reconstruct_image: {name} must have shape (H, W, {last})")
+        h, w = int(rgba.shape[0]), int(rgba.shape[1])
+        if tuple(weight.shape) != (h, w) or (grad is not None and tuple(grad.shape[:2]) != (h, w)):
+            raise RuntimeError("reconstruct_image: the planes disagree on the image size")
+        torch.cuda.current_stream(dev).synchronize()  # the kernels run on the renderer's stream
+        L.check(self._lib.ovr_hip_reconstruct_image(self._h, rgba.data_ptr(), grad.data_ptr() if grad is not None else None, weight.data_ptr(), w, h))
+        return rgba, grad
+
     def set_grid_convention(self, convention):
         L.check(self._lib.ovr_hip_set_grid_convention(self._h, int(convention)))
 

@@ -130,6 +130,15 @@ public:
       const char* th = std::getenv("OVR_HIP_CONVERGENCE_THRESHOLD");
       check(ovr_hip_set_convergence(h, convergence_mode, th ? (float)std::atof(th) : 0.f));
     }
+    // OVR_HIP_RECONSTRUCT=1: frames rendered with sparse sampling on ("Sparse Sampling" in renderapp) are completed by the pull-push reconstruction
+    //  before they are mapped; off by default, like the reference, whose sparse frames are mostly holes
+    {
+      const char* rc = std::getenv("OVR_HIP_RECONSTRUCT");
+      const int mode = (rc && rc[0] == '1') ? OVR_HIP_RECONSTRUCT_FILL : OVR_HIP_RECONSTRUCT_OFF;
+      if (mode != OVR_HIP_RECONSTRUCT_OFF) check(ovr_hip_set_reconstruction(h, mode));
+      if (rc && !(std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0'))
+        std::fprintf(stderr, "[hip] reconstruction of sparse-sampled frames: %s\n", mode == OVR_HIP_RECONSTRUCT_FILL ? "on (pull-push fill)" : "off");
+    }
     commit();
   }
 

@@ -296,6 +296,35 @@ int ovr_hip_get_reconstruction_gradient(ovr_hip_renderer* r, float* host, size_t
  * rank of a multi-process run calls on the assembled frame. */
 int ovr_hip_reconstruct_image(ovr_hip_renderer* r, float* rgba_device, float* grad_device, const float* weight_device, int32_t width, int32_t height);
 
+/* Light and material (added within ABI v11 like the reconstruction above: new entry points and a new struct only, nothing that existed
+ * changed its layout or meaning; a library without them fails to load in _lib.py by the missing symbols).  The renderer interface has seven lighting controls - MainRenderer::set_light_phi / _theta /
+ * _intensity, set_mat_ambient / _diffuse / _specular / _shininess, ovr/renderer.h:210-248, the sliders of the interactive app - that the reference's OptiX
+ * device never reads: its light is a literal (params.h:79) and so is its shade expression (shaders_raymarching.cu:138,156-157).  Here they are real, and
+ * until one of the two setters is called every frame, counter and time is what the literals give.
+ *   direction  a world-space vector TOWARDS the light, any length; normalised on the host as the literal is.  NULL = the reference's literal.
+ *              The interface's angles, in degrees, mean (sin phi cos theta, sin phi sin theta, cos phi): the app's defaults (99.53, 112.2) lie 0.15
+ *              degrees from the literal.  The shadow march and the shade order by light beams follow the direction.
+ *   intensity  the reference's light_rgb = 2 is intensity 1
+ *   shade      per shaded sample, IEEE float in this order (n the world normal, L the unit light, I2 = 2 * intensity, shadow = 0 under SHADE_GRADIENT):
+ *                  cosNL = |L . n|;  d = (diffuse * cosNL) * I2
+ *                  if specular > 0:  V = normalize(camera - position), H = normalize(L + V), cosNH = |H . n|,
+ *                                    sp = cosNH >= 2^-126 ? exp2(shininess * log2(cosNH)) : 0,  d = d + (specular * sp) * I2
+ *                  shade = ambient + d * (1 - shadow)
+ *              (0.5, 0.5, 0, any shininess) at intensity 1 is the reference's expression operation for operation.  open-volume-renderer_amd/lighting.py
+ *              is this arithmetic in numpy, the normative text; the exact-parity build agrees with it bit for bit.
+ * Queued like every setter, applied at commit; a CHANGED value resets the accumulation and voids what the layout / pipeline tuner measured.  EINVAL: a
+ * zero, non-finite or not normalisable direction; a negative or non-finite intensity or material value.  A device group forwards both to every member. */
+int ovr_hip_set_light(ovr_hip_renderer* r, const float direction[3], float intensity);
+int ovr_hip_set_material(ovr_hip_renderer* r, float ambient, float diffuse, float specular, float shininess);
+typedef struct ovr_hip_lighting {
+  float direction[3];      /* the unit vector the kernels use */
+  float intensity;
+  float ambient, diffuse, specular, shininess;
+  int32_t is_reference;    /* 1: the committed state shades exactly as the reference's literals do */
+} ovr_hip_lighting;
+/* the COMMITTED state: what the last frame used and the next one will, until a commit applies queued values */
+int ovr_hip_get_lighting(const ovr_hip_renderer* r, ovr_hip_lighting* out);
+
 /* replaces DeviceOptix7::Impl::commit (device_impl.cpp:113-197): applies every queued setter; any change resets
  * the accumulation (frame_index restarts at 1 on the next render). */
 int ovr_hip_commit(ovr_hip_renderer* r);
@@ -381,6 +410,9 @@ int ovr_hip_tea_floats(ovr_hip_renderer* r, uint32_t* v0v1_device, float* out_de
  * tolerated count differences. */
 int ovr_hip_pow_floats(ovr_hip_renderer* r, const float* x_device, const float* y_device, float* out_device, int64_t n, int32_t which);
 int ovr_hip_built_for_exact_parity(void);
+/* the shade factor as the kernels evaluate it (added with the light and material entry points): n (world normal, world position, shadow) triples -> n floats (device buffers; normal_w and
+ * pos hold 3 floats per sample), through the device function the frame's shading calls, with the committed light, material and camera position. */
+int ovr_hip_shade_floats(ovr_hip_renderer* r, const float* normal_w_device, const float* pos_device, const float* shadow_device, float* out_device, int64_t n);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,18 @@ class Reconstruction(C.Structure):
     ]
 
 
+class Lighting(C.Structure):
+    _fields_ = [
+        ("direction", C.c_float * 3),
+        ("intensity", C.c_float),
+        ("ambient", C.c_float),
+        ("diffuse", C.c_float),
+        ("specular", C.c_float),
+        ("shininess", C.c_float),
+        ("is_reference", C.c_int32),
+    ]
+
+
 # every symbol include/ovr_hip.h declares: name -> (restype, argtypes)
 _F3 = C.POINTER(C.c_float)
 _H = C.c_void_p
@@ -154,6 +166,10 @@ SYMBOLS = {
     "ovr_hip_get_reconstruction": (C.c_int, [_H, C.POINTER(Reconstruction)]),
     "ovr_hip_get_reconstruction_weights": (C.c_int, [_H, _F3, C.c_size_t]),
     "ovr_hip_get_reconstruction_gradient": (C.c_int, [_H, _F3, C.c_size_t]),
+    "ovr_hip_set_light": (C.c_int, [_H, _F3, C.c_float]),
+    "ovr_hip_set_material": (C.c_int, [_H, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "ovr_hip_get_lighting": (C.c_int, [_H, C.POINTER(Lighting)]),
+    "ovr_hip_shade_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
 }
 

@@ -96,6 +96,10 @@ struct TfnP { std::vector<float> colors, alphas; float lo = 1, hi = -1; };
 struct ShardP { int rank = 0, world = 1, tw = 64, th = 64; };
 struct Size2 { int w = 0, h = 0; };
 struct ConvP { int mode = OVR_HIP_CONVERGENCE_OFF; float threshold = 0.f; };
+// ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
+// and the 0.5 / 0.5 of its shade expression (shaders_raymarching.cu:138,156-157)
+struct LightP { float dir[3] = { -907.108f, 2205.875f, -400.0267f }; float intensity = 1.f; };
+struct MaterialP { float ambient = 0.5f, diffuse = 0.5f, specular = 0.f, shininess = 0.f; };
 
 } // namespace
 
@@ -216,6 +220,8 @@ struct ovr_hip_renderer {
   float* d_accum = nullptr;
   // ---- convergence estimate and adaptive refinement (ovr_hip_set_convergence).  Everything below exists only while the mode is not OFF.
   Queued<ConvP> convergence;
+  Queued<LightP> light;        // the raw vector: normalised when it is applied (apply_lighting)
+  Queued<MaterialP> material;
   float* d_accum_half = nullptr;        // H: the sum of the even-numbered frames (W*H*4)
   float* d_grad_keep = nullptr;         // adaptive: the gradient pixels of the retired blocks (W*H*3)
   float* d_conv_error = nullptr;        // per block of the image (bx + by * ceil(W / 8)): E_b
@@ -630,10 +636,21 @@ void update_volume_params(ovr_hip_renderer* r)
   P.coord_scale = { cs[0], cs[1], cs[2] };
   P.coord_bias = { cb[0], cb[1], cb[2] };
   P.grad_step = { gs[0], gs[1], gs[2] };
-  const V3 L = normalize({ -907.108f, 2205.875f, -400.0267f }); // params.h:79
-  P.light = { L.x, L.y, L.z };
   P.vol = r->vd;
   P.vol.data = r->d_volume;
+}
+
+// the committed light and material into the frame's parameters.  The raw vector is normalised here, by the routine that normalised the reference's
+// literal when the light was one: the same raw vector gives the same unit vector as the CPU oracle's (shade_order_params reads it per frame)
+void apply_lighting(ovr_hip_renderer* r)
+{
+  RayMarchParams& P = r->P;
+  const LightP& l = r->light.current;
+  const MaterialP& m = r->material.current;
+  const V3 L = normalize({ l.dir[0], l.dir[1], l.dir[2] });
+  P.light = { L.x, L.y, L.z };
+  P.light_i2 = 2.f * l.intensity;
+  P.mat_ka = m.ambient; P.mat_kd = m.diffuse; P.mat_ks = m.specular; P.mat_shininess = m.shininess;
 }
 
 // StructuredRegularVolume::set_value_range (volume.cpp:131-145): a valid range replaces the one in effect, an invalid one
@@ -1938,6 +1955,7 @@ int ovr_hip_create(ovr_hip_renderer** out, int device_id)
     return fail(OVR_HIP_EDEVICE, std::string("[hip] device is ") + prop.gcnArchName + ", this library is built for gfx950 (MI355X) only");
   ovr_hip_renderer* r = new ovr_hip_renderer();
   r->device = device_id;
+  apply_lighting(r);
   auto acquire = [&]() -> int {
     HIP_TRY(hipStreamCreate(&r->own_stream[0]));
     HIP_TRY(hipStreamCreate(&r->own_stream[1]));
@@ -2542,6 +2560,50 @@ int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold)
   return 0;
 }
 
+int ovr_hip_set_light(ovr_hip_renderer* r, const float direction[3], float intensity)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  LightP l; // the reference's literal
+  if (direction) {
+    const float len2 = direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2];
+    if (!std::isfinite(direction[0]) || !std::isfinite(direction[1]) || !std::isfinite(direction[2]) || !std::isfinite(len2) || !(len2 > 0.f)
+        || !std::isfinite(1.f / std::sqrt(len2)))
+      return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_light: the direction must be finite and have a length a float can normalise");
+    std::memcpy(l.dir, direction, sizeof(l.dir));
+  }
+  if (!std::isfinite(intensity) || intensity < 0.f) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_light: the intensity must be finite and not negative");
+  l.intensity = intensity;
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->light.set(l); }
+  GROUP_FORWARD(r, ovr_hip_set_light(m, direction, intensity));
+  return 0;
+}
+
+int ovr_hip_set_material(ovr_hip_renderer* r, float ambient, float diffuse, float specular, float shininess)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  for (float v : { ambient, diffuse, specular, shininess })
+    if (!std::isfinite(v) || v < 0.f) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_material: every value must be finite and not negative");
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); MaterialP p; p.ambient = ambient; p.diffuse = diffuse; p.specular = specular; p.shininess = shininess; r->material.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_material(m, ambient, diffuse, specular, shininess));
+  return 0;
+}
+
+int ovr_hip_get_lighting(const ovr_hip_renderer* r, ovr_hip_lighting* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_lighting: null argument");
+  const RayMarchParams& P = r->P;
+  out->direction[0] = P.light.x; out->direction[1] = P.light.y; out->direction[2] = P.light.z;
+  out->intensity = r->light.current.intensity;
+  out->ambient = P.mat_ka; out->diffuse = P.mat_kd; out->specular = P.mat_ks; out->shininess = P.mat_shininess;
+  const LightP lit;
+  const MaterialP ref;
+  out->is_reference = std::memcmp(r->light.current.dir, lit.dir, sizeof(lit.dir)) == 0 && r->light.current.intensity == 1.f && P.mat_ka == ref.ambient
+                      && P.mat_kd == ref.diffuse && P.mat_ks == 0.f;
+  return 0;
+}
+
 int ovr_hip_set_reconstruction(ovr_hip_renderer* r, int32_t mode)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -2618,7 +2680,8 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
          && a->tfn.current.lo == b->tfn.current.lo && a->tfn.current.hi == b->tfn.current.hi && a->tfn.current.colors == b->tfn.current.colors && a->tfn.current.alphas == b->tfn.current.alphas
          && std::memcmp(&a->focus.current, &b->focus.current, sizeof(FocusP)) == 0 && a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw
          && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn && a->convergence.current.mode == b->convergence.current.mode
-         && a->convergence.current.threshold == b->convergence.current.threshold;
+         && a->convergence.current.threshold == b->convergence.current.threshold && std::memcmp(&a->light.current, &b->light.current, sizeof(LightP)) == 0
+         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0;
 }
 } // namespace
 extern "C" {
@@ -2713,6 +2776,18 @@ int commit_one(ovr_hip_renderer* r)
         HIP_TRY(hipDeviceSynchronize());
         if (int e = free_reconstruction(r)) return e;
       }
+    }
+  }
+  // light and material: a changed value resets the accumulation (and with it the convergence estimate, the retired blocks and the reconstruction's counts)
+  // and, below, voids what the layout / pipeline tuner measured - shadow rays change their length with the light; the beam grid of the shade order is
+  // rebuilt from RayMarchParams::light with every frame (shade_order_params)
+  {
+    const LightP lb = r->light.current;
+    const MaterialP mb = r->material.current;
+    const bool lu = r->light.update(), mu = r->material.update();
+    if (lu || mu) {
+      apply_lighting(r);
+      if (std::memcmp(&lb, &r->light.current, sizeof(LightP)) != 0 || std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0) r->fb_reset = true;
     }
   }
   (void)r->lds_staging.update(); // same frame either way
@@ -3166,6 +3241,16 @@ int ovr_hip_pow_floats(ovr_hip_renderer* r, const float* x, const float* y, floa
 }
 
 int ovr_hip_built_for_exact_parity(void) { return built_for_exact_parity(); }
+
+int ovr_hip_shade_floats(ovr_hip_renderer* r, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n)
+{
+  if (!r || !normal_w || !pos || !shadow || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_shade_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  HIP_TRY(launch_shade_floats(r->P, normal_w, pos, shadow, out, n, r->stream())); // the committed light, material and camera position
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
 
 int ovr_hip_tea_floats(ovr_hip_renderer* r, uint32_t* v0v1, float* out, int64_t n)
 {

@@ -938,9 +938,43 @@ __device__ __forceinline__ void write_pixel(const RayMarchParams& P, unsigned in
   }
 }
 
-// shade one request: gradient (shaders_common.h:195-215), normals, shadow march, Lambert-ish term
+// The shade factor (include/ovr_hip.h ovr_hip_set_light / ovr_hip_set_material; open-volume-renderer_amd/lighting.py is the normative arithmetic), in
+// two steps so that shade_request can take the first BEFORE its shadow march - one value crosses the march, as cosNL did, and the specular term's
+// temporaries (and the sample's position) are dead by then.  shade_light: what the light contributes to an unshadowed sample, (kd * cosNL) * I2
+// [+ (ks * sp) * I2]; shade_factor: ka + that * (1 - shadow).  The reference's state (0.5, 0.5, 0, -, I2 = 2) is its literal expression,
+// 0.5f + 0.5f * cosNL * 2.f * (1.f - shadow) (shaders_raymarching.cu:156-157), operation for operation.  Material, light and camera are kernel
+// arguments: scalar registers, and the specular term sits behind a wave-uniform branch on ks > 0.
+// MAT = false is the reference state with its values as literals: the kernels every frame runs until a setter is called are the ones that existed
+// before the setters did.  (One kernel for both was tried: nine more live scalars - the shade kernels spill scalars already - moved every
+// shading instantiation, +3 ... +6 VGPRs and an occupancy step for the gradient-shaded quad layouts, +11 ... +18 spilled scalars with shadows;
+// profiles/r08_lighting.md.)  The host picks MAT = true when the committed material or intensity is not the reference's (reference_material).
+__host__ __device__ inline bool reference_material(const RayMarchParams& P) { return P.mat_ka == 0.5f && P.mat_kd == 0.5f && P.mat_ks == 0.f && P.light_i2 == 2.f; }
+template <bool MAT>
+__device__ __forceinline__ float shade_light(const RayMarchParams& P, f3 light, f3 n_w, f3 pos)
+{
+  const float cosNL = fabsf(dot3(light, n_w));
+  float d = ((MAT ? P.mat_kd : 0.5f) * cosNL) * (MAT ? P.light_i2 : 2.f);
+  if (MAT && P.mat_ks > 0.f) {
+    const f3 v = normalize3(mk3(P.cam_pos.x - pos.x, P.cam_pos.y - pos.y, P.cam_pos.z - pos.z)); // from the sample's position, not from its ray: a pooled request holds no direction
+    const f3 h = normalize3(mk3(light.x + v.x, light.y + v.y, light.z + v.z));
+    const float cosNH = fabsf(dot3(h, n_w)); // two-sided, like the diffuse term
+    // NaN (a sample at the camera, h of length 0) and denormals (v_log_f32 takes them for 0: -inf, times shininess 0 = NaN) select 0
+#if OVR_PARITY_EXACT
+    const float pw = det_exp2f(P.mat_shininess * det_log2f(cosNH));
+#else
+    const float pw = __builtin_amdgcn_exp2f(P.mat_shininess * __builtin_amdgcn_logf(cosNH));
+#endif
+    const float sp = cosNH >= FLT_MIN ? pw : 0.f;
+    d = d + (P.mat_ks * sp) * P.light_i2;
+  }
+  return d;
+}
+template <bool MAT>
+__device__ __forceinline__ float shade_factor(const RayMarchParams& P, float lit, float shadow) { return (MAT ? P.mat_ka : 0.5f) + lit * (1.f - shadow); }
+
+// shade one request: gradient (shaders_common.h:195-215), normals, shadow march, shade factor
 // (shaders_raymarching.cu:124-158).  Writes the result over the request.
-template <int VT, int SHADE, int AM, bool SKIP>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT>
 __device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r,
                                               unsigned int& n_shadow, unsigned int& n_shadow_skipped)
 {
@@ -975,10 +1009,10 @@ __device__ __forceinline__ void shade_request(const RayMarchParams& P, const Vol
     n_c = normalize3(mk3(fmaf(n_w.x, m[0], fmaf(n_w.y, m[3], n_w.z * m[6])), fmaf(n_w.x, m[1], fmaf(n_w.y, m[4], n_w.z * m[7])),
                          fmaf(n_w.x, m[2], fmaf(n_w.y, m[5], n_w.z * m[8]))));
   }
+  const float lit = shade_light<MAT>(P, mc.light, n_w, pos);
   float shadow = 0.f;
   if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP>(vc, tf, mc, pos, n_shadow, n_shadow_skipped);
-  const float cosNL = fabsf(dot3(mc.light, n_w));
-  const float shade = 0.5f + 0.5f * cosNL * 2.f * (1.f - shadow); // shaders_raymarching.cu:156-157
+  const float shade = shade_factor<MAT>(P, lit, shadow); // shaders_raymarching.cu:156-157
   const float tr = r.tr;
   r.px = tr * clamp01(rgb.x * shade);
   r.py = tr * clamp01(rgb.y * shade);
@@ -1165,12 +1199,13 @@ struct LdsRegion { int bx0, by0, bz0, ebx, eby, ebz, nbr, ok; };
 constexpr int kDeepK = 6;
 // (the skipping pooled march sits at the edge of the 3-waves budget: 169 VGPRs - one too many - cost it 15 %; it is pinned to 3)
 constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scratch under the pin
-template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false>
+template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
   static_assert(!LDSB || (SHADE == 0 && !POOLED && !SKIP && AM <= 1 && !Vox<VT>::kTransposed), "LDS-staged bricks: unshaded in-place march only");
   using Cfg = QCfg<SHADE, POOLED>;
   static_assert(!DEEP || (POOLED && !SKIP && !LDSB), "the deep variant exists for the plain pooled march");
+  static_assert(!MAT || (SHADE != 0 && !POOLED), "the material variant exists where the march shades: in place (pooled: shade_pool_kernel)");
   constexpr int K = DEEP ? kDeepK : Cfg::K;
   constexpr int QCAP = Cfg::QCAP;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1392,7 +1427,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
           r.px = r.py = r.pz = r.s = r.v = r.tr = r.a = 0.f; r.next = 0;
           if ((unsigned int)lane < n) {
             r = queue[(q_head + lane) & (QCAP - 1)];
-            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
+            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
           }
           int opend = owner ? pend : 0;
           apply_batch(r, q_head, n, lane, opend, first, color, gradient);
@@ -1736,7 +1771,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
 // ------------------------------------------------------------------------------------------------------------------
 // pooled pipeline, kernel B: persistent waves shade chunks from all tiles; one returning atomic per chunk
 // ------------------------------------------------------------------------------------------------------------------
-template <int VT, int SHADE, int AM, bool SKIP>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT>
 __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams P)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1782,7 +1817,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     if ((unsigned int)lane < n) {
       ShadeReq r = Q.reqs[(size_t)c * 64 + lane];
       if (r.a > 0.f) { // a == 0: null request (a step of the quad that needs no shading)
-        shade_request<VT, SHADE, AM, SKIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
+        shade_request<VT, SHADE, AM, SKIP, MAT>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
         Q.reqs[(size_t)c * 64 + lane] = r;
       }
     }
@@ -1934,9 +1969,20 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
       }
     }
     if (!launched) {
-      auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP>;
-      if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-      if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+      bool with_material = false;
+      if constexpr (SHADE != 0) {
+        if (!reference_material(p)) { // a material or intensity of the caller's (shade_light)
+          auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, true>;
+          if ((e = set_lds(kern, lds)) != hipSuccess) return e;
+          if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+          with_material = true;
+        }
+      }
+      if (!with_material) {
+        auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP>;
+        if ((e = set_lds(kern, lds)) != hipSuccess) return e;
+        if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+      }
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev && ev[1] && ev[2]) { (void)hipEventRecord(ev[1], stream); (void)hipEventRecord(ev[2], stream); }
@@ -1984,7 +2030,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
       if (q.pool.order && (e = launch_shade_order(q, stream)) != hipSuccess) return e; // runs sorted by light beam (PoolDesc)
       {
         const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM), 64);
-        auto kern = shade_pool_kernel<VT, SHADE, AM, SKIP>;
+        auto kern = reference_material(p) ? shade_pool_kernel<VT, SHADE, AM, SKIP, false> : shade_pool_kernel<VT, SHADE, AM, SKIP, true>;
         if ((e = set_lds(kern, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)shade_grid_blocks(p)), block, lds, stream, q);
         if ((e = hipGetLastError()) != hipSuccess) return e;

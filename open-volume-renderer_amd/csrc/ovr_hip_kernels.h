@@ -139,7 +139,7 @@ struct RayMarchParams {
   // volume transform: world -> object is diagonal (device_impl.cpp:288-296)
   float3_ inv_scale, wto_p, otw_it;
   float wtc_it[9]; // columns of inverse-transpose(world_to_camera)
-  float3_ light;   // normalized params.h:79
+  float3_ light;   // unit vector towards the light (ovr_hip_set_light; the reference's literal, params.h:79, until it is called)
   // object [0,1] -> voxel coordinate: x = p * coord_scale + coord_bias, clamped to [0, n-1]
   float3_ coord_scale, coord_bias, grad_step;
   float step, base;           // volume.cpp:172-179
@@ -189,6 +189,10 @@ struct RayMarchParams {
   unsigned int* block_counters; // workspace: raymarch_grid_blocks() * kBlockCounters per-workgroup partial sums
   PoolDesc pool;
   VolumeDesc vol;
+  // material and light intensity of the shade factor (ovr_hip_set_material; open-volume-renderer_amd/lighting.py is the arithmetic):
+  // ambient, diffuse, specular, shininess, 2 * intensity.  The reference's literal expression is (0.5, 0.5, 0, -, 2).  Behind everything else: the
+  // kernels of the reference state do not read them, and with every other argument at the offset it had their code is what it was
+  float mat_ka, mat_kd, mat_ks, mat_shininess, light_i2;
 };
 
 // returns hipSuccess or the launch error; ev = 4 events (start, after march, after shade, end) or null
@@ -328,6 +332,9 @@ hipError_t launch_sparse_mask(const SparseMaskParams& p, hipStream_t stream);
 hipError_t launch_tea(uint32_t* v0v1, float* out, int64_t n, hipStream_t stream);
 hipError_t launch_pow(const float* x, const float* y, float* out, int64_t n, int which, hipStream_t stream);
 int built_for_exact_parity();
+// known-answer entry of the shade factor (shade_factor in ovr_hip_device.h, the function shade_request calls): n (world normal, world position,
+// shadow) triples -> n factors, with p's light, material and camera position
+hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n, hipStream_t stream);
 
 // macrocells (reference accel/sp_singlemc.cu): (min,max) per 16^3 cell once per volume; majorant per cell on every TF change
 hipError_t launch_macrocell_ranges(const VolumeDesc& vd, float* out_minmax, hipStream_t stream);

@@ -1733,6 +1733,23 @@ hipError_t launch_pow(const float* x, const float* y, float* out, int64_t n, int
 }
 int built_for_exact_parity() { return OVR_PARITY_EXACT; }
 
+// known-answer entry of the shade factor: shade_light + shade_factor exactly as shade_request calls them, with the frame's parameter block
+template <bool MAT>
+__global__ void shade_floats_kernel(const RayMarchParams P, const float* normal_w, const float* pos, const float* shadow, float* out, long long n)
+{
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const f3 n_w = mk3(normal_w[3 * i], normal_w[3 * i + 1], normal_w[3 * i + 2]), p = mk3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+  out[i] = shade_factor<MAT>(P, shade_light<MAT>(P, ld3(P.light), n_w, p), shadow[i]);
+}
+hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as launch_vsbs picks the frame's kernels
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, normal_w, pos, shadow, out, (long long)n);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // tile pack / unpack (payload of the per-frame RCCL gather): slot k = k-th tile owned by `rank` in row-major tile order
 // ------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from . import lighting
 
 _NP_TO_TYPE = {
     np.dtype(np.uint8): L.TYPE_UINT8, np.dtype(np.int8): L.TYPE_INT8,
@@ -115,6 +116,10 @@ class DeviceHIP:
         self._fbsize = (0, 0)
         self._keep = []                        # keeps ctypes buffers alive across calls
         self._convergence_mode = L.CONVERGENCE_OFF
+        self._light_dir = None                 # None = the reference's literal
+        self._light_angles = lighting.angles_of(lighting.LITERAL_LIGHT)
+        self._light_intensity = 1.0
+        self._material = lighting.REFERENCE_MATERIAL
 
     # ---- lifetime -------------------------------------------------------------------------------------------
     def close(self):
@@ -169,18 +174,78 @@ class DeviceHIP:
         if on:  # the path tracer is outside this backend's scope
             raise RuntimeError("[hip] path tracing is not part of the ray-marching backend")
 
-    # accepted and ignored exactly as the reference's ray marcher ignores them (device_impl.cpp:113-197 never reads them)
+    # accepted and ignored, as the reference's ray marcher ignores them (device_impl.cpp:113-197 never reads them): more than one light and the
+    # scene file's lights, photon mapping and the density scale belong to its path tracer, and the light's radius - the interactive app has its
+    # own call commented out - would make the shadow rays of a frame stop being parallel, which the shade order by light beams relies on
     def set_add_lights(self, v): pass
     def set_photonmapping(self, v): pass
     def set_volume_density_scale(self, v): pass
-    def set_mat_ambient(self, v): pass
-    def set_mat_diffuse(self, v): pass
-    def set_mat_specular(self, v): pass
-    def set_mat_shininess(self, v): pass
-    def set_light_phi(self, v): pass
-    def set_light_theta(self, v): pass
     def set_light_radius(self, v): pass
-    def set_light_intensity(self, v): pass
+
+    # the seven lighting controls of the interface (renderer.h:210-248), which the reference's OptiX device leaves dead: real here (include/ovr_hip.h,
+    # lighting.py).  Angles in degrees, d = (sin phi cos theta, sin phi sin theta, cos phi); the state starts as the reference's literal
+    # light and material, setting one value keeps the others.  Queued, applied at commit; a changed value resets the accumulation.
+    def set_light_phi(self, v):
+        self._push_angles(float(v), self._light_angles[1])
+
+    def set_light_theta(self, v):
+        self._push_angles(self._light_angles[0], float(v))
+
+    def _push_angles(self, phi, theta):
+        self._push_light(lighting.direction_from_angles(phi, theta))
+        self._light_angles = (phi, theta)
+
+    def set_light_intensity(self, v):
+        self._push_light(self._light_dir, float(v))
+
+    def set_mat_ambient(self, v): self._push_material(0, v)
+    def set_mat_diffuse(self, v): self._push_material(1, v)
+    def set_mat_specular(self, v): self._push_material(2, v)
+    def set_mat_shininess(self, v): self._push_material(3, v)
+
+    def _push_light(self, direction, intensity=None):
+        intensity = self._light_intensity if intensity is None else float(intensity)
+        d = None if direction is None else _f3(direction)
+        L.check(self._lib.ovr_hip_set_light(self._h, d, intensity))
+        # (kept only when the library accepted them)
+        self._light_dir, self._light_intensity = None if direction is None else tuple(float(x) for x in direction), intensity
+
+    def _push_material(self, k, v):
+        m = list(self._material)
+        m[k] = float(v)
+        L.check(self._lib.ovr_hip_set_material(self._h, *m))
+        self._material = tuple(m)
+
+    def set_light_direction(self, vec, intensity=1.0):
+        """direct binding of ovr_hip_set_light: a world-space vector towards the light, any length; None = the reference's literal"""
+        self._push_light(None if vec is None else [float(x) for x in vec], intensity)
+        self._light_angles = lighting.angles_of(lighting.LITERAL_LIGHT if vec is None else vec)
+
+    def set_material(self, ambient=0.5, diffuse=0.5, specular=0.0, shininess=0.0):
+        """direct binding of ovr_hip_set_material; the defaults are the reference's shade expression"""
+        m = (float(ambient), float(diffuse), float(specular), float(shininess))
+        L.check(self._lib.ovr_hip_set_material(self._h, *m))
+        self._material = m
+
+    def lighting(self):
+        """ovr_hip_lighting, the COMMITTED state: direction (the unit vector the kernels use), intensity, ambient, diffuse, specular, shininess, is_reference"""
+        c = L.Lighting()
+        L.check(self._lib.ovr_hip_get_lighting(self._h, C.byref(c)))
+        return c
+
+    def shade_floats(self, normal_w, pos, shadow):
+        """the shade factor as the kernels evaluate it (ovr_hip_shade_floats; known-answer tests): (n, 3), (n, 3), (n,) -> (n,) float32, with the
+        committed light, material and camera position"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (normal_w, pos, shadow)]
+        n = int(t[2].numel())
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("shade_floats: normal_w and pos hold three floats per sample")
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_shade_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), n))
+        return out.cpu().numpy()
 
     # ---- extensions of this backend ----------------------------------------------------------------------------
     def set_shading(self, mode):

@@ -139,6 +139,27 @@ public:
       if (rc && !(std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0'))
         std::fprintf(stderr, "[hip] reconstruction of sparse-sampled frames: %s\n", mode == OVR_HIP_RECONSTRUCT_FILL ? "on (pull-push fill)" : "off");
     }
+    // The interface's lighting controls (set_light_phi / _theta / _intensity, set_mat_*: renderapp's sliders) are forwarded by commit() below.  The batch app
+    // has no sliders: OVR_HIP_LIGHT=phi,theta[,intensity] (degrees) and OVR_HIP_MATERIAL=ambient,diffuse,specular,shininess set them once.  Unset: nothing
+    // is called, the frames are the reference's literal light and shade expression
+    {
+      const bool quiet = std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0';
+      if (const char* lv = std::getenv("OVR_HIP_LIGHT")) {
+        float a[3] = { 0.f, 0.f, intensity };
+        const int n = std::sscanf(lv, "%f,%f,%f", &a[0], &a[1], &a[2]);
+        if (n < 2) throw std::runtime_error("[hip] OVR_HIP_LIGHT expects phi,theta[,intensity] in degrees");
+        phi = a[0]; theta = a[1]; intensity = a[2];
+        angles_set = true;
+        push_light();
+        if (!quiet) std::fprintf(stderr, "[hip] light: phi %g, theta %g degrees, intensity %g\n", (double)phi, (double)theta, (double)intensity);
+      }
+      if (const char* mv = std::getenv("OVR_HIP_MATERIAL")) {
+        if (std::sscanf(mv, "%f,%f,%f,%f", &material[0], &material[1], &material[2], &material[3]) != 4)
+          throw std::runtime_error("[hip] OVR_HIP_MATERIAL expects ambient,diffuse,specular,shininess");
+        check(ovr_hip_set_material(h, material[0], material[1], material[2], material[3]));
+        if (!quiet) std::fprintf(stderr, "[hip] material: ambient %g, diffuse %g, specular %g, shininess %g\n", (double)material[0], (double)material[1], (double)material[2], (double)material[3]);
+      }
+    }
     commit();
   }
 
@@ -175,6 +196,18 @@ public:
     }
     if (params.frame_accumulation.update()) check(ovr_hip_set_frame_accumulation(h, params.frame_accumulation.ref()));
     if (params.volume_sampling_rate.update()) check(ovr_hip_set_volume_sampling_rate(h, params.volume_sampling_rate.get()));
+    // the seven lighting controls (ovr/renderer.h:210-248; the OptiX device never reads them).  A member that was never set keeps the backend's value:
+    // the state below starts as the reference's literals, and until an angle arrives the direction stays the literal vector itself (NULL)
+    bool light_changed = false, material_changed = false;
+    if (params.phi.update()) { phi = params.phi.ref(); angles_set = light_changed = true; }
+    if (params.theta.update()) { theta = params.theta.ref(); angles_set = light_changed = true; }
+    if (params.intensity.update()) { intensity = params.intensity.ref(); light_changed = true; }
+    if (params.ambient.update()) { material[0] = params.ambient.ref(); material_changed = true; }
+    if (params.diffuse.update()) { material[1] = params.diffuse.ref(); material_changed = true; }
+    if (params.specular.update()) { material[2] = params.specular.ref(); material_changed = true; }
+    if (params.shininess.update()) { material[3] = params.shininess.ref(); material_changed = true; }
+    if (light_changed) push_light();
+    if (material_changed) check(ovr_hip_set_material(h, material[0], material[1], material[2], material[3]));
     check(ovr_hip_commit(h));
   }
 
@@ -210,6 +243,19 @@ public:
   }
 
 private:
+  // degrees -> (sin phi cos theta, sin phi sin theta, cos phi), in double, rounded to float per component (include/ovr_hip.h: ovr_hip_set_light)
+  void push_light()
+  {
+    if (!angles_set) { check(ovr_hip_set_light(h, nullptr, intensity)); return; }
+    const double p = (double)phi * M_PI / 180.0, t = (double)theta * M_PI / 180.0;
+    const float d[3] = { (float)(std::sin(p) * std::cos(t)), (float)(std::sin(p) * std::sin(t)), (float)std::cos(p) };
+    check(ovr_hip_set_light(h, d, intensity));
+  }
+
+  // the literal light's own angles (used for the angle that was not set when the other one is): acos(z / |L|), atan2(y, x) of params.h:79
+  float phi = 99.52095708f, theta = 112.35362395f, intensity = 1.f;
+  float material[4] = { 0.5f, 0.5f, 0.f, 0.f };
+  bool angles_set = false;
   ovr_hip_renderer* h = nullptr;
   bool have_noise = false;
   int convergence_mode = OVR_HIP_CONVERGENCE_OFF;

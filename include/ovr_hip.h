@@ -325,6 +325,29 @@ typedef struct ovr_hip_lighting {
 /* the COMMITTED state: what the last frame used and the next one will, until a commit applies queued values */
 int ovr_hip_get_lighting(const ovr_hip_renderer* r, ovr_hip_lighting* out);
 
+/* Clip box (added within ABI v11 like the light and the material: new entry points and one new struct only).  The VIDI3D scene format
+ * carries a `view.volume.clippingBox` next to `boundingBox`; the reference's loader drops it and its marcher has no place for it.  Here an axis-aligned box in
+ * the space of grid_origin / grid_spacing cuts the volume open:
+ *   lower, upper   world coordinates; lower may hold -inf and upper +inf ("open on this side").  Both NULL = no clip box.
+ *   object box     per axis lo = clamp01(fmaf(lower, inv_scale, wto_p)), hi likewise from upper - the float constants that take a world position into the
+ *                  volume's [0, 1] box; recomputed whenever the volume or the grid convention changes.
+ *   box test       the march's test of the unit cube with lo in place of 0 and hi in place of 1 (lo = 0, hi = 1 gives the same bits); it cuts the primary
+ *                  ray, EVERY shadow ray - what is cut away casts no shadow - and the schedule's block test.  Voxel taps and gradient taps read the true
+ *                  voxels, also across a clip face.  lo >= hi on any axis: every ray misses (a zero frame, samples == 0).
+ *                  open-volume-renderer_amd/clipping.py is this arithmetic in numpy, the normative text.
+ * Queued like every setter, applied at commit; a CHANGED value resets the accumulation and voids what the layout / pipeline tuner measured, the same value
+ * again resets nothing.  Until the setter is called every frame, counter and kernel is what it was without it; a clipped frame never takes the LDS-staged
+ * march (the same frame, lds_rounds == 0).  EINVAL (the state stays): a NaN, lower[k] > upper[k], or exactly one pointer NULL.  A device group forwards
+ * the call to every member. */
+int ovr_hip_set_clip_box(ovr_hip_renderer* r, const float lower[3], const float upper[3]);
+typedef struct ovr_hip_clip_box {
+  int32_t enabled;                  /* 1: a clip box is committed */
+  float lower[3], upper[3];         /* the world box as given (-inf / +inf without one) */
+  float object_lower[3], object_upper[3]; /* what the kernels test: inside [0, 1] ((0, 0, 0), (1, 1, 1) without a clip box) */
+} ovr_hip_clip_box;
+/* the COMMITTED state, not the queued one */
+int ovr_hip_get_clip_box(const ovr_hip_renderer* r, ovr_hip_clip_box* out);
+
 /* replaces DeviceOptix7::Impl::commit (device_impl.cpp:113-197): applies every queued setter; any change resets
  * the accumulation (frame_index restarts at 1 on the next render). */
 int ovr_hip_commit(ovr_hip_renderer* r);
@@ -413,6 +436,10 @@ int ovr_hip_built_for_exact_parity(void);
 /* the shade factor as the kernels evaluate it (added with the light and material entry points): n (world normal, world position, shadow) triples -> n floats (device buffers; normal_w and
  * pos hold 3 floats per sample), through the device function the frame's shading calls, with the committed light, material and camera position. */
 int ovr_hip_shade_floats(ovr_hip_renderer* r, const float* normal_w_device, const float* pos_device, const float* shadow_device, float* out_device, int64_t n);
+/* the box test as the kernels evaluate it (added with the clip box): n world-space rays (3 floats each for origin and direction; the direction is used as given)
+ * -> n triples (t0, t1, hit ? 1 : 0) (device buffers), through the device function the march, the shadow march and the schedule call, with the committed
+ * volume transform and clip box - without a clip box the unit cube's result.  Needs a volume. */
+int ovr_hip_clip_intervals(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* t0t1hit_device, int64_t n);
 
 #ifdef __cplusplus
 }

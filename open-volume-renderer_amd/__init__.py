@@ -6,7 +6,7 @@ one-process-per-GPU runs (tiles) and the synthetic inputs the reference does not
 from . import _lib
 from ._lib import (GRID_CELL_CENTRED, GRID_VERTEX_CENTRED, JITTER_BLUE_NOISE, JITTER_TEA, RECONSTRUCT_FILL, RECONSTRUCT_OFF, SHADE_FULL, SHADE_GRADIENT, SHADE_NONE)
 from .renderer import (Camera, CrossDeviceBuffer, DeviceHIP, FrameBufferData, Scene, TransferFunction, create_renderer)
-from . import convergence, imageio, lighting, reconstruction, synth, tiles, vidi3d
+from . import clipping, convergence, imageio, lighting, reconstruction, synth, tiles, vidi3d
 
 __all__ = ["Camera", "CrossDeviceBuffer", "DeviceHIP", "FrameBufferData", "Scene", "TransferFunction", "create_renderer",
-           "convergence", "imageio", "lighting", "reconstruction", "synth", "tiles", "vidi3d", "JITTER_TEA", "JITTER_BLUE_NOISE", "SHADE_NONE", "SHADE_GRADIENT", "SHADE_FULL", "GRID_CELL_CENTRED", "GRID_VERTEX_CENTRED", "RECONSTRUCT_OFF", "RECONSTRUCT_FILL"]
+           "clipping", "convergence", "imageio", "lighting", "reconstruction", "synth", "tiles", "vidi3d", "JITTER_TEA", "JITTER_BLUE_NOISE", "SHADE_NONE", "SHADE_GRADIENT", "SHADE_FULL", "GRID_CELL_CENTRED", "GRID_VERTEX_CENTRED", "RECONSTRUCT_OFF", "RECONSTRUCT_FILL"]

@@ -102,6 +102,16 @@ class Lighting(C.Structure):
     ]
 
 
+class ClipBox(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_int32),
+        ("lower", C.c_float * 3),
+        ("upper", C.c_float * 3),
+        ("object_lower", C.c_float * 3),
+        ("object_upper", C.c_float * 3),
+    ]
+
+
 # every symbol include/ovr_hip.h declares: name -> (restype, argtypes)
 _F3 = C.POINTER(C.c_float)
 _H = C.c_void_p
@@ -170,6 +180,9 @@ SYMBOLS = {
     "ovr_hip_set_material": (C.c_int, [_H, C.c_float, C.c_float, C.c_float, C.c_float]),
     "ovr_hip_get_lighting": (C.c_int, [_H, C.POINTER(Lighting)]),
     "ovr_hip_shade_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "ovr_hip_set_clip_box": (C.c_int, [_H, _F3, _F3]),
+    "ovr_hip_get_clip_box": (C.c_int, [_H, C.POINTER(ClipBox)]),
+    "ovr_hip_clip_intervals": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
 }
 

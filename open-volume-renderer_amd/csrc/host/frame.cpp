@@ -287,7 +287,7 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.world = r->shard.current.world;
   P.tile_w = r->shard.current.tw;
   P.tile_h = r->shard.current.th;
-  P.lds_staging = r->lds_staging.current;
+  P.lds_staging = P.clip_on ? 0 : r->lds_staging.current; // a clipped frame takes the ordinary march: the same frame, lds_rounds == 0
   P.lds_brick_offset = 0;
   P.jitter_mode = r->jitter.current;
   P.jitter_noise = r->d_noise;

@@ -68,6 +68,9 @@ struct ConvP { int mode = OVR_HIP_CONVERGENCE_OFF; float threshold = 0.f; };
 // and the 0.5 / 0.5 of its shade expression (shaders_raymarching.cu:138,156-157)
 struct LightP { float dir[3] = { -907.108f, 2205.875f, -400.0267f }; float intensity = 1.f; };
 struct MaterialP { float ambient = 0.5f, diffuse = 0.5f, specular = 0.f, shininess = 0.f; };
+// ovr_hip_set_clip_box: the world box as given (-inf / +inf: open on that side).  The object box the kernels test is derived from it and the volume
+// (apply_clip_box)
+struct ClipP { int enabled = 0; float lower[3] = { -INFINITY, -INFINITY, -INFINITY }, upper[3] = { INFINITY, INFINITY, INFINITY }; };
 
 // the frame words on the device (ovr_hip_renderer::d_counters): 8 counters, the pool's control words from byte 128, the reduction's ticket word behind them
 constexpr size_t kFrameWordsBytes = 128 + (size_t)ovrhip::kPoolCtrlWords * sizeof(unsigned int) + 128;
@@ -184,6 +187,7 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::ShardP> shard;
   Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (apply_lighting)
   Queued<ovrhip::host::MaterialP> material;
+  Queued<ovrhip::host::ClipP> clip;          // the world box: the object box follows the volume (apply_clip_box)
   Queued<ovrhip::host::ConvP> convergence;
   Queued<int> reconstruction;
   Queued<int> layouts;      // ovr_hip_set_volume_layouts: which replicas the next ovr_hip_set_volume plans (2: builds at once)
@@ -334,6 +338,7 @@ int ensure_sparse_buffers(ovr_hip_renderer* r);
 void update_camera(ovr_hip_renderer* r);
 void update_volume_params(ovr_hip_renderer* r);
 void apply_lighting(ovr_hip_renderer* r);
+void apply_clip_box(ovr_hip_renderer* r);
 void update_tfn_range(ovr_hip_renderer* r);
 int upload_tfn(ovr_hip_renderer* r);
 int update_macrocells(ovr_hip_renderer* r, hipStream_t st);

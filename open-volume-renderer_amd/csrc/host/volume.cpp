@@ -94,6 +94,26 @@ void update_volume_params(ovr_hip_renderer* r)
   P.grad_step = { gs[0], gs[1], gs[2] };
   P.vol = r->vd;
   P.vol.data = r->d_volume;
+  apply_clip_box(r); // the object box follows the volume's transform
+}
+
+// the committed clip box into the frame's parameters: per axis clamp01(fmaf(world, inv_scale, wto_p)) - the float constants that take a world position
+// into the volume's [0, 1] box (to_object in the kernels; open-volume-renderer_amd/clipping.py object_box).  -inf / +inf clamp to 0 / 1.  Without a clip
+// box, or before a volume is set, the unit cube - and clip_on = 0: the kernels of the unclipped state are launched
+void apply_clip_box(ovr_hip_renderer* r)
+{
+  RayMarchParams& P = r->P;
+  const ClipP& c = r->clip.current;
+  const float inv[3] = { P.inv_scale.x, P.inv_scale.y, P.inv_scale.z }, wp[3] = { P.wto_p.x, P.wto_p.y, P.wto_p.z };
+  float lo[3] = { 0.f, 0.f, 0.f }, hi[3] = { 1.f, 1.f, 1.f };
+  P.clip_on = c.enabled && r->have_volume ? 1 : 0;
+  if (P.clip_on)
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::fmin(std::fmax(std::fma(c.lower[k], inv[k], wp[k]), 0.f), 1.f);
+      hi[k] = std::fmin(std::fmax(std::fma(c.upper[k], inv[k], wp[k]), 0.f), 1.f);
+    }
+  P.clip_lo = { lo[0], lo[1], lo[2] };
+  P.clip_hi = { hi[0], hi[1], hi[2] };
 }
 
 // the committed light and material into the frame's parameters.  The raw vector is normalised here, by the routine that normalised the reference's

@@ -47,6 +47,7 @@ int ovr_hip_create(ovr_hip_renderer** out, int device_id)
   ovr_hip_renderer* r = new ovr_hip_renderer();
   r->device = device_id;
   apply_lighting(r);
+  apply_clip_box(r);
   auto acquire = [&]() -> int {
     HIP_TRY(hipStreamCreate(&r->own_stream[0]));
     HIP_TRY(hipStreamCreate(&r->own_stream[1]));
@@ -294,6 +295,38 @@ int ovr_hip_get_lighting(const ovr_hip_renderer* r, ovr_hip_lighting* out)
   return 0;
 }
 
+int ovr_hip_set_clip_box(ovr_hip_renderer* r, const float lower[3], const float upper[3])
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if ((lower == nullptr) != (upper == nullptr)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_clip_box: lower and upper must both be given, or both be NULL (no clip box)");
+  ClipP c; // none
+  if (lower) {
+    for (int k = 0; k < 3; ++k)
+      if (std::isnan(lower[k]) || std::isnan(upper[k]) || lower[k] > upper[k])
+        return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_clip_box: the bounds must not be NaN, and lower must not exceed upper");
+    c.enabled = 1;
+    std::memcpy(c.lower, lower, sizeof(c.lower));
+    std::memcpy(c.upper, upper, sizeof(c.upper));
+  }
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->clip.set(c); }
+  GROUP_FORWARD(r, ovr_hip_set_clip_box(m, lower, upper));
+  return 0;
+}
+
+int ovr_hip_get_clip_box(const ovr_hip_renderer* r, ovr_hip_clip_box* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_clip_box: null argument");
+  const RayMarchParams& P = r->P;
+  const ClipP& c = r->clip.current;
+  out->enabled = c.enabled;
+  std::memcpy(out->lower, c.lower, sizeof(c.lower));
+  std::memcpy(out->upper, c.upper, sizeof(c.upper));
+  out->object_lower[0] = P.clip_lo.x; out->object_lower[1] = P.clip_lo.y; out->object_lower[2] = P.clip_lo.z;
+  out->object_upper[0] = P.clip_hi.x; out->object_upper[1] = P.clip_hi.y; out->object_upper[2] = P.clip_hi.z;
+  return 0;
+}
+
 int ovr_hip_set_reconstruction(ovr_hip_renderer* r, int32_t mode)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -371,7 +404,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
          && std::memcmp(&a->focus.current, &b->focus.current, sizeof(FocusP)) == 0 && a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw
          && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn && a->convergence.current.mode == b->convergence.current.mode
          && a->convergence.current.threshold == b->convergence.current.threshold && std::memcmp(&a->light.current, &b->light.current, sizeof(LightP)) == 0
-         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0;
+         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0 && std::memcmp(&a->clip.current, &b->clip.current, sizeof(ClipP)) == 0;
 }
 } // namespace
 extern "C" {
@@ -478,6 +511,15 @@ int commit_one(ovr_hip_renderer* r)
     if (lu || mu) {
       apply_lighting(r);
       if (std::memcmp(&lb, &r->light.current, sizeof(LightP)) != 0 || std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0) r->fb_reset = true;
+    }
+  }
+  // clip box: a changed value resets the accumulation like a changed light, re-sorts the schedule (its block test is the clipped one) and, below, voids
+  // the tuner's measurement - a cut volume is another workload; the same value again resets nothing
+  {
+    const ClipP cb = r->clip.current;
+    if (r->clip.update()) {
+      apply_clip_box(r);
+      if (std::memcmp(&cb, &r->clip.current, sizeof(ClipP)) != 0) { r->fb_reset = true; r->sched.dirty = true; }
     }
   }
   (void)r->lds_staging.update(); // same frame either way
@@ -936,6 +978,17 @@ int ovr_hip_shade_floats(ovr_hip_renderer* r, const float* normal_w, const float
   if (int e = set_device(r)) return e;
   if (int e = finish_frame(r)) return e;
   HIP_TRY(launch_shade_floats(r->P, normal_w, pos, shadow, out, n, r->stream())); // the committed light, material and camera position
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_clip_intervals(ovr_hip_renderer* r, const float* org, const float* dir, float* t0t1hit, int64_t n)
+{
+  if (!r || !org || !dir || !t0t1hit || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_clip_intervals: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_clip_intervals: no volume was set");
+  HIP_TRY(launch_clip_intervals(r->P, org, dir, t0t1hit, n, r->stream())); // the committed volume transform and clip box
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

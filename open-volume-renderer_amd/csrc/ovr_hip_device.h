@@ -569,6 +569,42 @@ __device__ __forceinline__ bool ignored_slab_outside(f3 o, f3 d)
          (fabsf(d.z) < FLT_MIN && !(o.z >= 0.f && o.z <= 1.f));
 }
 
+// The clip box (include/ovr_hip.h ovr_hip_set_clip_box; open-volume-renderer_amd/clipping.py is the normative arithmetic): the same test against
+// [lo, hi] instead of [0, 1] per axis - the expressions above, operation for operation, with the literal 0.f replaced by lo_k and 1.f by hi_k, so
+// that lo = 0, hi = 1 returns the bits intersect_unit_box returns.  An empty box (lo_k >= hi_k on an axis) is missed by every ray, also by one whose
+// slab on that axis is ignored.
+__device__ __forceinline__ bool intersect_bounds_box(float& t0, float& t1, f3 o, f3 d, f3 lo, f3 hi)
+{
+  const bool sx = fabsf(d.x) < FLT_MIN, sy = fabsf(d.y) < FLT_MIN, sz = fabsf(d.z) < FLT_MIN;
+  const float rx = 1.f / d.x, ry = 1.f / d.y, rz = 1.f / d.z;
+  const float lx = sx ? FLT_MAX : (lo.x - o.x) * rx, ly = sy ? FLT_MAX : (lo.y - o.y) * ry, lz = sz ? FLT_MAX : (lo.z - o.z) * rz;
+  const float hx = sx ? -FLT_MAX : (hi.x - o.x) * rx, hy = sy ? -FLT_MAX : (hi.y - o.y) * ry, hz = sz ? -FLT_MAX : (hi.z - o.z) * rz;
+  t0 = fmaxf(t0, fmaxf(fmaxf(fminf(lx, hx), fminf(ly, hy)), fminf(lz, hz)));
+  t1 = fminf(t1, fminf(fminf(fmaxf(lx, hx), fmaxf(ly, hy)), fmaxf(lz, hz)));
+  const bool empty = lo.x >= hi.x || lo.y >= hi.y || lo.z >= hi.z;
+  return t1 > t0 && !empty;
+}
+__device__ __forceinline__ bool ignored_slab_outside_bounds(f3 o, f3 d, f3 lo, f3 hi)
+{
+  return (fabsf(d.x) < FLT_MIN && !(o.x >= lo.x && o.x <= hi.x)) || (fabsf(d.y) < FLT_MIN && !(o.y >= lo.y && o.y <= hi.y)) ||
+         (fabsf(d.z) < FLT_MIN && !(o.z >= lo.z && o.z <= hi.z));
+}
+// CLIP = false is the state without a clip box with its bounds as literals: the kernels every frame runs until ovr_hip_set_clip_box is called are
+// the ones that existed before it did (the route of MAT, shade_light below).  The bounds are kernel arguments behind every
+// other one (RayMarchParams::clip_lo / clip_hi): scalar registers.
+template <bool CLIP>
+__device__ __forceinline__ bool box_test(const RayMarchParams& P, float& t0, float& t1, f3 o, f3 d)
+{
+  if (CLIP) return intersect_bounds_box(t0, t1, o, d, mk3(P.clip_lo.x, P.clip_lo.y, P.clip_lo.z), mk3(P.clip_hi.x, P.clip_hi.y, P.clip_hi.z));
+  return intersect_unit_box(t0, t1, o, d);
+}
+template <bool CLIP>
+__device__ __forceinline__ bool box_ignored_slab_outside(const RayMarchParams& P, f3 o, f3 d)
+{
+  if (CLIP) return ignored_slab_outside_bounds(o, d, mk3(P.clip_lo.x, P.clip_lo.y, P.clip_lo.z), mk3(P.clip_hi.x, P.clip_hi.y, P.clip_hi.z));
+  return ignored_slab_outside(o, d);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // TEA, random.h:146-188
 // ------------------------------------------------------------------------------------------------------------------
@@ -602,6 +638,7 @@ __device__ __forceinline__ f3 to_object(const MarchConsts& mc, f3 p)
 // Does the ray of pixel (ix, iy) - one sample per pixel, no jitter - meet the volume's box?  The expressions are the march's own
 // (raymarch_kernel: screen position, ray direction, object-space ray, box test), so the answer is the march's answer bit for bit, the
 // ignored-slab quirk of the reference's box test included.  launch_schedule uses it to find the 8x8 blocks NONE of whose rays hits.
+template <bool CLIP = false>
 __device__ __forceinline__ bool pixel_ray_hits_box(const RayMarchParams& P, const MarchConsts& mc, int ix, int iy)
 {
   const float rsx = 1.f / (float)P.width, rsy = 1.f / (float)P.height;
@@ -612,7 +649,7 @@ __device__ __forceinline__ bool pixel_ray_hits_box(const RayMarchParams& P, cons
   const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
   const f3 oo = to_object(mc, ld3(P.cam_pos));
   float t0 = 0.f, t1 = FLT_MAX;
-  return intersect_unit_box(t0, t1, oo, od);
+  return box_test<CLIP>(P, t0, t1, oo, od);
 }
 
 // Empty-space skipping, per ray: the t interval outside of which every sample lies in a macrocell with majorant 0.
@@ -690,15 +727,16 @@ __device__ __forceinline__ void skip_walk(const VolConsts& vc, f3 oo, f3 od, flo
 // raymarching_shadow, shaders_raymarching.cu:44-85 (+ :205-229): alpha-only march toward the light.
 // KS taps are issued before the first one is consumed; taps past the end of the march or past the early-termination
 // point are speculative (their coordinates are clamped, so the loads are always in bounds) and simply dropped.
-template <int VT, int AM, int KS, bool SKIP>
-__device__ __forceinline__ float march_shadow(const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, f3 org, unsigned int& n_shadow,
+// CLIP: the shadow ray is cut by the clip box like the primary ray - what is cut away casts no shadow
+template <int VT, int AM, int KS, bool SKIP, bool CLIP = false>
+__device__ __forceinline__ float march_shadow(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, f3 org, unsigned int& n_shadow,
                                               unsigned int& n_shadow_skipped)
 {
   const f3 oo = to_object(mc, org);
   const f3 od = mk3(mc.light.x * mc.inv_scale.x, mc.light.y * mc.inv_scale.y, mc.light.z * mc.inv_scale.z);
   float t0 = 0.f, t1 = FLT_MAX;
   float alpha = 0.f;
-  if (!intersect_unit_box(t0, t1, oo, od)) return alpha;
+  if (!box_test<CLIP>(P, t0, t1, oo, od)) return alpha;
   float tx = t0, ty = fminf(t1, t0 + mc.shadow_stride);
   bool live = true;
   // empty-space skipping: the shadow ray's own skip interval (a handful of coarse entries: the ray is a few hundred voxels)
@@ -974,7 +1012,7 @@ __device__ __forceinline__ float shade_factor(const RayMarchParams& P, float lit
 
 // shade one request: gradient (shaders_common.h:195-215), normals, shadow march, shade factor
 // (shaders_raymarching.cu:124-158).  Writes the result over the request.
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false>
 __device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r,
                                               unsigned int& n_shadow, unsigned int& n_shadow_skipped)
 {
@@ -1011,7 +1049,7 @@ __device__ __forceinline__ void shade_request(const RayMarchParams& P, const Vol
   }
   const float lit = shade_light<MAT>(P, mc.light, n_w, pos);
   float shadow = 0.f;
-  if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP>(vc, tf, mc, pos, n_shadow, n_shadow_skipped);
+  if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP, CLIP>(P, vc, tf, mc, pos, n_shadow, n_shadow_skipped);
   const float shade = shade_factor<MAT>(P, lit, shadow); // shaders_raymarching.cu:156-157
   const float tr = r.tr;
   r.px = tr * clamp01(rgb.x * shade);
@@ -1199,13 +1237,16 @@ struct LdsRegion { int bx0, by0, bz0, ebx, eby, ebz, nbr, ok; };
 constexpr int kDeepK = 6;
 // (the skipping pooled march sits at the edge of the 3-waves budget: 169 VGPRs - one too many - cost it 15 %; it is pinned to 3)
 constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scratch under the pin
-template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false>
+// CLIP = true: the clipped march (box_test).  Where the march shades in place it rides on MAT = true - the material's values as arguments give the
+// reference state's bits when they are the reference's - so a clipped state adds one instantiation per kernel, not two
+template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
   static_assert(!LDSB || (SHADE == 0 && !POOLED && !SKIP && AM <= 1 && !Vox<VT>::kTransposed), "LDS-staged bricks: unshaded in-place march only");
   using Cfg = QCfg<SHADE, POOLED>;
   static_assert(!DEEP || (POOLED && !SKIP && !LDSB), "the deep variant exists for the plain pooled march");
   static_assert(!MAT || (SHADE != 0 && !POOLED), "the material variant exists where the march shades: in place (pooled: shade_pool_kernel)");
+  static_assert(!CLIP || (!LDSB && !DEEP && (MAT || SHADE == 0 || POOLED)), "the clipped variant: the ordinary march, with the material variant where it shades");
   constexpr int K = DEEP ? kDeepK : Cfg::K;
   constexpr int QCAP = Cfg::QCAP;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1275,7 +1316,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
       const f3 d0 = normalize3_exact(mk3(c0.x + ux0 * h0.x + uy0 * v0.x, c0.y + ux0 * h0.y + uy0 * v0.y, c0.z + ux0 * h0.z + uy0 * v0.z));
       float a0 = 0.f, b0 = FLT_MAX;
       const f3 oo0 = to_object(mc, ld3(P.cam_pos)), od0 = mk3(d0.x * mc.inv_scale.x, d0.y * mc.inv_scale.y, d0.z * mc.inv_scale.z);
-      need = intersect_unit_box(a0, b0, oo0, od0);
+      need = box_test<CLIP>(P, a0, b0, oo0, od0);
       if (SKIP && need) { // skipping: a ray that meets no occupied macrocell never fetches a voxel or a TF entry either
         pro_span = skip_interval(vc, oo0, od0, a0, b0, sub, true);
         need = pro_span.first <= pro_span.last;
@@ -1392,9 +1433,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
     alpha = 0.f;
     color = mk3(0, 0, 0);
     gradient = mk3(0, 0, 0);
-    bool live = active && intersect_unit_box(t0, t1, oo, od);
+    bool live = active && box_test<CLIP>(P, t0, t1, oo, od);
     if (active && owner) ++n_rays;
-    if (live && owner && ignored_slab_outside(oo, od)) ++n_outside_hits;
+    if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
     SkipSpan span = skipspan_all(); // samples outside the hull, or in an unmarked segment of it, are in empty macrocells
     if (SKIP) {
       if (P.spp == 1) span = pro_span; // same ray, same [t0, t1] as in the prologue
@@ -1427,7 +1468,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
           r.px = r.py = r.pz = r.s = r.v = r.tr = r.a = 0.f; r.next = 0;
           if ((unsigned int)lane < n) {
             r = queue[(q_head + lane) & (QCAP - 1)];
-            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
+            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT, CLIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
           }
           int opend = owner ? pend : 0;
           apply_batch(r, q_head, n, lane, opend, first, color, gradient);
@@ -1771,9 +1812,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
 // ------------------------------------------------------------------------------------------------------------------
 // pooled pipeline, kernel B: persistent waves shade chunks from all tiles; one returning atomic per chunk
 // ------------------------------------------------------------------------------------------------------------------
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false>
 __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams P)
 {
+  static_assert(!CLIP || (SHADE == 2 && MAT), "the clipped variant exists where the shade kernel marches shadow rays, on the material variant");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   TfConsts tf;
@@ -1817,7 +1859,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     if ((unsigned int)lane < n) {
       ShadeReq r = Q.reqs[(size_t)c * 64 + lane];
       if (r.a > 0.f) { // a == 0: null request (a step of the quad that needs no shading)
-        shade_request<VT, SHADE, AM, SKIP, MAT>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
+        shade_request<VT, SHADE, AM, SKIP, MAT, CLIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
         Q.reqs[(size_t)c * 64 + lane] = r;
       }
     }
@@ -1958,7 +2000,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
     const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM) + (size_t)kWaves * QCfg<SHADE, false>::QCAP * sizeof(ShadeReq), (size_t)kWaves * kNC * sizeof(unsigned int)); // the counter reduction reuses it
     bool launched = false;
     if constexpr (VT == VOX_F32 && SHADE == 0 && AM <= 1 && !SKIP) {
-      if (p.lds_staging && !p.sparse_xy) { // LDS-staged bricks (see raymarch_kernel): the bricks follow the tables and the TF
+      if (p.lds_staging && !p.sparse_xy && !p.clip_on) { // LDS-staged bricks (see raymarch_kernel): the bricks follow the tables and the TF
         RayMarchParams q = p;
         q.lds_brick_offset = (unsigned int)((lds + 15) & ~(size_t)15);
         const size_t lds2 = q.lds_brick_offset + (size_t)kLdsBrickCap * 128 + sizeof(LdsRegion) + 12 * sizeof(float) + 2 * sizeof(int) + 16;
@@ -1970,7 +2012,13 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
     }
     if (!launched) {
       bool with_material = false;
-      if constexpr (SHADE != 0) {
+      if (p.clip_on) { // a committed clip box (box_test): the clipped instantiation - where the march shades, of the material variant
+        auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, SHADE != 0, true>;
+        if ((e = set_lds(kern, lds)) != hipSuccess) return e;
+        if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+        with_material = true;
+      }
+      else if constexpr (SHADE != 0) {
         if (!reference_material(p)) { // a material or intensity of the caller's (shade_light)
           auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, true>;
           if ((e = set_lds(kern, lds)) != hipSuccess) return e;
@@ -2012,7 +2060,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
         const size_t lds = (size_t)kWaves * QCfg<SH, true>::QCAP * sizeof(ShadeReq) + table_lds_bytes(p, AM) + (size_t)p.n_alpha * sizeof(float) + 64;
         bool launched = false;
         if constexpr (!SKIP && (AM <= 1 || AM == 4)) {
-          if (use_deep_rounds(p)) { // a small image shard: the longest ray's chain of rounds is the floor - deeper rounds
+          if (use_deep_rounds(p) && !p.clip_on) { // (a clipped frame takes the plain rounds: the same frame, and no third set of pooled kernels) a small image shard: the longest ray's chain of rounds is the floor - deeper rounds
             auto kern = raymarch_kernel<VT, SH, AM, true, SKIP, false, true>;
             if ((e = set_lds(kern, lds)) != hipSuccess) return e;
             if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, q);
@@ -2020,7 +2068,7 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
           }
         }
         if (!launched) {
-          auto kern = raymarch_kernel<VT, SH, AM, true, SKIP>;
+          auto kern = p.clip_on ? raymarch_kernel<VT, SH, AM, true, SKIP, false, false, false, true> : raymarch_kernel<VT, SH, AM, true, SKIP>;
           if ((e = set_lds(kern, lds)) != hipSuccess) return e;
           if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, q);
         }
@@ -2031,6 +2079,9 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
       {
         const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM), 64);
         auto kern = reference_material(p) ? shade_pool_kernel<VT, SHADE, AM, SKIP, false> : shade_pool_kernel<VT, SHADE, AM, SKIP, true>;
+        if constexpr (SHADE == 2) { // shadow rays are clipped too; without them (SHADE == 1) the shade kernel never tests the box
+          if (p.clip_on) kern = shade_pool_kernel<VT, SHADE, AM, SKIP, true, true>;
+        }
         if ((e = set_lds(kern, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3((unsigned)shade_grid_blocks(p)), block, lds, stream, q);
         if ((e = hipGetLastError()) != hipSuccess) return e;

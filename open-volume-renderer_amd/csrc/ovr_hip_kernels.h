@@ -193,6 +193,11 @@ struct RayMarchParams {
   // ambient, diffuse, specular, shininess, 2 * intensity.  The reference's literal expression is (0.5, 0.5, 0, -, 2).  Behind everything else: the
   // kernels of the reference state do not read them, and with every other argument at the offset it had their code is what it was
   float mat_ka, mat_kd, mat_ks, mat_shininess, light_i2;
+  // clip box (ovr_hip_set_clip_box; open-volume-renderer_amd/clipping.py is the arithmetic): the object-space bounds the box test of the clipped
+  // kernels uses in place of the unit cube's 0 and 1.  Behind everything else, like the material: only the clipped instantiations read them, and the
+  // host launches those only while clip_on is set (the kernels do not read clip_on)
+  float3_ clip_lo, clip_hi;
+  int clip_on;
 };
 
 // returns hipSuccess or the launch error; ev = 4 events (start, after march, after shade, end) or null
@@ -335,6 +340,9 @@ int built_for_exact_parity();
 // known-answer entry of the shade factor (shade_factor in ovr_hip_device.h, the function shade_request calls): n (world normal, world position,
 // shadow) triples -> n factors, with p's light, material and camera position
 hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n, hipStream_t stream);
+// known-answer entry of the box test (box_test in ovr_hip_device.h, the function the march, the shadow march and the schedule call): n world-space rays
+// (origin, direction - used as given, not normalised) -> n triples (t0, t1, hit ? 1 : 0) with p's volume transform and clip box (the unit cube without one)
+hipError_t launch_clip_intervals(const RayMarchParams& p, const float* org, const float* dir, float* t0t1hit, int64_t n, hipStream_t stream);
 
 // macrocells (reference accel/sp_singlemc.cu): (min,max) per 16^3 cell once per volume; majorant per cell on every TF change
 hipError_t launch_macrocell_ranges(const VolumeDesc& vd, float* out_minmax, hipStream_t stream);

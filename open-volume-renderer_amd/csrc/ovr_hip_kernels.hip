@@ -168,6 +168,7 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(const unsigned int
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kSchedClasses = 64;
 // length of probe ray k of block e inside the box (k = 0: the block's centre, 1 ... 4: its corners), -1 = it misses
+template <bool CLIP>
 __device__ __forceinline__ float schedule_probe(const RayMarchParams& P, const MarchConsts& mc, unsigned int e, int k)
 {
   const f3 c0 = ld3(P.cam_dir), h0 = ld3(P.cam_hor), v0 = ld3(P.cam_ver);
@@ -177,7 +178,7 @@ __device__ __forceinline__ float schedule_probe(const RayMarchParams& P, const M
   const float ux = ((float)ix + .5f) / (float)P.width - 0.5f, uy = ((float)iy + .5f) / (float)P.height - 0.5f;
   const f3 d = normalize3_exact(mk3(c0.x + ux * h0.x + uy * v0.x, c0.y + ux * h0.y + uy * v0.y, c0.z + ux * h0.z + uy * v0.z));
   float a = 0.f, b = FLT_MAX;
-  if (intersect_unit_box(a, b, oo, mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z))) return b - a;
+  if (box_test<CLIP>(P, a, b, oo, mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z))) return b - a;
   return -1.f;
 }
 // the block's class from the longest of its five probe rays: 0 = none meets the volume (last), 1 ... kSchedClasses - 1 by length
@@ -201,6 +202,9 @@ __device__ __forceinline__ unsigned int schedule_class_of(const RayMarchParams& 
 // (Mapping the 16 blocks of a supertile to ONE XCD - workgroup s runs on XCD s % 8 - was measured slower: C3 march 1.63 vs 1.57 ms.)
 //   schedule_classify_kernel one WAVE per block: its length class (five probe rays, one per lane) and - `exact` - whether ANY of its 64 pixel rays meets the box
 //                            (pixel_ray_hits_box: the march's own test); cls[i] = class | active pixels << 8, class 0 <=> (exact) no ray hits
+//                            CLIP: both against the committed clip box, as the clipped march tests it (the frustum culling of exact == 2 keeps the
+//                            volume's own box: a superset)
+template <bool CLIP>
 __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchParams P, const unsigned int* __restrict__ src, unsigned int n, int exact,
                                                                unsigned int* __restrict__ cls)
 {
@@ -214,7 +218,7 @@ __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchPa
   const int ix = (int)(e & 0xffffu) * 8 + (lane & 7), iy = (int)(e >> 16) * 8 + (lane >> 3);
   bool active = ix < P.width && iy < P.height;
   if (P.world > 1 && active) active = ((ix / P.tile_w + iy / P.tile_h) % P.world) == P.rank; // assign_pixel_quad's ownership test
-  const bool hit = exact == 1 && active && pixel_ray_hits_box(P, mc, ix, iy);
+  const bool hit = exact == 1 && active && pixel_ray_hits_box<CLIP>(P, mc, ix, iy);
   const unsigned long long any = __ballot(hit), act = __ballot(active);
   // exact == 2 (several samples per pixel, or jittered ones: a pixel's rays are only known to lie within half a pixel of its centre): the block
   // is surely empty if the cone of ALL rays through the block widened by 1.5 pixels lies beyond one of its own four side planes from the whole
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchPa
     }
     culled = beyond && sign_safe;
   }
-  float longest = lane < 5 ? schedule_probe(P, mc, e, lane) : -1.f; // (until round 4 lane 0 traced all five: 58 us per camera change at 1080p)
+  float longest = lane < 5 ? schedule_probe<CLIP>(P, mc, e, lane) : -1.f; // (until round 4 lane 0 traced all five: 58 us per camera change at 1080p)
 #pragma unroll
   for (int off = 1; off < 8; off <<= 1) longest = fmaxf(longest, __shfl_xor(longest, off));
   if (lane == 0) {
@@ -342,7 +346,8 @@ hipError_t launch_schedule(const RayMarchParams& p, const unsigned int* src, uns
   const dim3 grid((n + 1023u) / 1024u);
   unsigned int* hist = workspace;
   unsigned int* cls = workspace + (size_t)grid.x * kSchedRow;
-  hipLaunchKernelGGL(schedule_classify_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, p, src, n, exact, cls);
+  auto classify = p.clip_on ? schedule_classify_kernel<true> : schedule_classify_kernel<false>;
+  hipLaunchKernelGGL(classify, dim3((n + 3u) / 4u), dim3(256), 0, stream, p, src, n, exact, cls);
   hipLaunchKernelGGL(schedule_hist_kernel, grid, dim3(1024), 0, stream, cls, n, hist);
   hipLaunchKernelGGL(schedule_scatter_kernel, grid, dim3(1024), 0, stream, src, cls, n, hist, dst, info);
   return hipGetLastError();
@@ -1747,6 +1752,30 @@ hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, c
   if (n <= 0) return hipSuccess;
   auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as launch_vsbs picks the frame's kernels
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, normal_w, pos, shadow, out, (long long)n);
+  return hipGetLastError();
+}
+
+// known-answer entry of the box test: the object-space ray as the march forms it (to_object of the origin, the direction scaled by inv_scale, not
+// renormalised), then box_test exactly as the march, the shadow march and the schedule call it
+template <bool CLIP>
+__global__ void clip_intervals_kernel(const RayMarchParams P, const float* org, const float* dir, float* out, long long n)
+{
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  const f3 oo = to_object(mc, mk3(org[3 * i], org[3 * i + 1], org[3 * i + 2]));
+  const f3 od = mk3(dir[3 * i] * mc.inv_scale.x, dir[3 * i + 1] * mc.inv_scale.y, dir[3 * i + 2] * mc.inv_scale.z);
+  float t0 = 0.f, t1 = FLT_MAX;
+  const bool hit = box_test<CLIP>(P, t0, t1, oo, od);
+  out[3 * i] = t0; out[3 * i + 1] = t1; out[3 * i + 2] = hit ? 1.f : 0.f;
+}
+hipError_t launch_clip_intervals(const RayMarchParams& p, const float* org, const float* dir, float* t0t1hit, int64_t n, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  auto kern = p.clip_on ? clip_intervals_kernel<true> : clip_intervals_kernel<false>; // as launch_vsbs picks the frame's kernels
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, org, dir, t0t1hit, (long long)n);
   return hipGetLastError();
 }
 

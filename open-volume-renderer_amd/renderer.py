@@ -50,6 +50,7 @@ class Scene:
     camera: Camera = field(default_factory=Camera)
     volume_sampling_rate: float = 1.0
     spp: int = 1
+    clipping_box: object = None                # (lower, upper) in world units or None (vidi3d.read_scene: the file's clippingBox)
 
 
 class _DevicePtr:
@@ -247,6 +248,39 @@ class DeviceHIP:
         L.check(self._lib.ovr_hip_shade_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), n))
         return out.cpu().numpy()
 
+    # the clip box (include/ovr_hip.h ovr_hip_set_clip_box; clipping.py is the arithmetic): an axis-aligned box in the space of grid_origin /
+    # grid_spacing that cuts the primary rays, the shadow rays and the schedule's block test.  Queued, applied at commit; a changed value resets
+    # the accumulation.
+    def set_clip_box(self, lower, upper=None):
+        """set_clip_box(lower, upper): world coordinates, -inf / +inf = open on that side; set_clip_box(None): no clip box"""
+        if lower is None and upper is None:
+            L.check(self._lib.ovr_hip_set_clip_box(self._h, None, None))
+            return
+        lo = None if lower is None else _f3(lower)
+        hi = None if upper is None else _f3(upper)
+        L.check(self._lib.ovr_hip_set_clip_box(self._h, lo, hi))
+
+    def clip_box(self):
+        """ovr_hip_clip_box, the COMMITTED state: enabled, lower / upper (the world box as given), object_lower / object_upper (what the kernels test)"""
+        c = L.ClipBox()
+        L.check(self._lib.ovr_hip_get_clip_box(self._h, C.byref(c)))
+        return c
+
+    def clip_intervals(self, org, direction):
+        """the box test as the kernels evaluate it (ovr_hip_clip_intervals; known-answer tests): world rays (n, 3), (n, 3) -> t0 (n,), t1 (n,) float32 and
+        hit (n,) bool, with the committed volume and clip box (the unit cube without one)"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("clip_intervals: org and direction hold three floats per ray")
+        out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_clip_intervals(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n))
+        o = out.cpu().numpy()
+        return o[:, 0].copy(), o[:, 1].copy(), o[:, 2] != 0
+
     # ---- extensions of this backend ----------------------------------------------------------------------------
     def set_shading(self, mode):
         L.check(self._lib.ovr_hip_set_shading(self._h, int(mode)))
@@ -408,6 +442,8 @@ class DeviceHIP:
         self.set_scene(scene)
         self.set_camera(camera)
         self._upload_volume(scene)
+        if scene.clipping_box is not None:
+            self.set_clip_box(*scene.clipping_box)
         # buildScene applies the scene's rate directly; an earlier set_volume_sampling_rate() stays queued and wins at commit
         # (device_impl.cpp:298 then :190-196) - reproduced by not queuing the scene's rate when the app already set one.
         if not getattr(self, "_rate_set_by_app", False):

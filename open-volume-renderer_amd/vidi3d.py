@@ -14,10 +14,12 @@ _TYPE_NAME = {np.dtype(np.uint8): "UNSIGNED_BYTE", np.dtype(np.int8): "BYTE", np
 
 
 def write_scene(directory, name, volume, color_controls, alpha_table, scalar_range_normalized, camera, fovy=45.0,
-                sample_distance=1.0):
+                sample_distance=1.0, clipping_box=None):
     """volume: (nz, ny, nx) array; color_controls: [(position, r, g, b)]; alpha_table: float32 opacities (its length is the
     TF resolution); scalar_range_normalized: (lo, hi) as a fraction of the type's maximum for integer data, raw for floats
-    (scalarMappingRange, serializer_vidi3d.cpp:236-272); camera: (eye, center, up)."""
+    (scalarMappingRange, serializer_vidi3d.cpp:236-272); camera: (eye, center, up); clipping_box: (lower, upper) in world units
+    (spacing 1: voxels) or None - written as `clippingBox` in the units of `boundingBox`, which spans (0, 0, 0) .. dims - 1 as in
+    the reference's shipped scenes (`read_scene` maps it back)."""
     os.makedirs(directory, exist_ok=True)
     volume = np.ascontiguousarray(volume)
     raw = os.path.join(directory, name + ".raw")
@@ -49,6 +51,11 @@ def write_scene(directory, name, volume, color_controls, alpha_table, scalar_ran
                 "transferFunctionType": "TRANSFER_FUNCTION", "visible": True},
         },
     }
+    if clipping_box is not None:  # world box (0 .. dims) -> the bounding box's units (0 .. dims - 1); without one the file is what it always was
+        to_file = lambda w, n: float(w) / n * (n - 1)
+        doc["view"]["volume"]["boundingBox"] = {"minimum": xyz((0, 0, 0)), "maximum": xyz((nx - 1, ny - 1, nz - 1))}
+        doc["view"]["volume"]["clippingBox"] = {"minimum": xyz([to_file(w, n) for w, n in zip(clipping_box[0], (nx, ny, nz))]),
+                                                "maximum": xyz([to_file(w, n) for w, n in zip(clipping_box[1], (nx, ny, nz))])}
     path = os.path.join(directory, name + ".json")
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
@@ -165,7 +172,10 @@ _INT_MAX = {np.dtype(np.uint8): 255.0, np.dtype(np.int8): 127.0, np.dtype(np.uin
 
 def read_scene(path, load_volume=True):
     """VIDI3D scene file -> dict(volume, dtype, dims, grid_origin, grid_spacing, tfn_color (N x 4), tfn_opacity (N), value_range,
-    camera (eye, at, up, fovy), lights [(direction, color)], volume_sampling_rate).  `scene_from_file` wraps it into a Scene."""
+    camera (eye, at, up, fovy), lights [(direction, color)], volume_sampling_rate, clipping_box).  `scene_from_file` wraps it into a Scene.
+    clipping_box: the file's `view.volume.clippingBox` - which the reference's loader drops - mapped linearly from `boundingBox` onto the volume's
+    world box (grid_origin .. grid_origin + grid_spacing * dims) as (lower, upper), or None when the two boxes are equal (all of the reference's
+    shipped scenes) or the file has none."""
     with open(path) as f:
         root = json.loads(_strip_json_comments(f.read()))
     workdir = os.path.dirname(os.path.abspath(path)) or "."
@@ -226,10 +236,18 @@ def read_scene(path, load_volume=True):
     if not lights:
         lights.append(((1.0, 1.0, 1.0), (1.0, 1.0, 1.0)))
     rate = _F(1.0) / _F(float(jv["sampleDistance"]))                                       # :399
+    clipping_box = None
+    if "clippingBox" in jv and "boundingBox" in jv:
+        bb = [[float(jv["boundingBox"][m][k]) for k in "xyz"] for m in ("minimum", "maximum")]
+        cb = [[float(jv["clippingBox"][m][k]) for k in "xyz"] for m in ("minimum", "maximum")]
+        if cb != bb:
+            world = [(0.0, spacing[k] * n) for k, n in enumerate((nx, ny, nz))]
+            to_world = lambda c, k: world[k][0] + (c - bb[0][k]) / (bb[1][k] - bb[0][k]) * (world[k][1] - world[k][0])
+            clipping_box = (tuple(to_world(cb[0][k], k) for k in range(3)), tuple(to_world(cb[1][k], k) for k in range(3)))
     return dict(volume=volume, dtype=dtype, dims=(nx, ny, nz), grid_origin=(0.0, 0.0, 0.0), grid_spacing=spacing,
                 tfn_color=color, tfn_opacity=opacity, value_range=(float(vr[0]), float(vr[1])),
                 camera=(xyz(cam["eye"]), xyz(cam["center"]), xyz(cam["up"]), float(cam["fovy"])), lights=lights,
-                volume_sampling_rate=float(rate))
+                volume_sampling_rate=float(rate), clipping_box=clipping_box)
 
 
 def scene_from_file(path):
@@ -240,5 +258,5 @@ def scene_from_file(path):
     cam = Camera(eye, at, up, fovy)
     scene = Scene(volume=d["volume"], grid_origin=d["grid_origin"], grid_spacing=d["grid_spacing"],
                   transfer_function=TransferFunction(color=d["tfn_color"], opacity=d["tfn_opacity"], value_range=d["value_range"]),
-                  camera=cam, volume_sampling_rate=d["volume_sampling_rate"])
+                  camera=cam, volume_sampling_rate=d["volume_sampling_rate"], clipping_box=d["clipping_box"])
     return scene, cam

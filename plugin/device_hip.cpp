@@ -159,6 +159,16 @@ public:
         check(ovr_hip_set_material(h, material[0], material[1], material[2], material[3]));
         if (!quiet) std::fprintf(stderr, "[hip] material: ambient %g, diffuse %g, specular %g, shininess %g\n", (double)material[0], (double)material[1], (double)material[2], (double)material[3]);
       }
+      // The clip box (ovr_hip_set_clip_box): the scene file's view.volume.clippingBox never reaches a device - the reference's loader discards it - so
+      // OVR_HIP_CLIP_BOX=x0,y0,z0,x1,y1,z1 (world units: the space of the volume's grid_origin / grid_spacing; inf / -inf leave a side open) is the
+      // batch app's only switch.  Unset: nothing is called
+      if (const char* cv = std::getenv("OVR_HIP_CLIP_BOX")) {
+        float lo[3], hi[3];
+        if (std::sscanf(cv, "%f,%f,%f,%f,%f,%f", &lo[0], &lo[1], &lo[2], &hi[0], &hi[1], &hi[2]) != 6)
+          throw std::runtime_error("[hip] OVR_HIP_CLIP_BOX expects x0,y0,z0,x1,y1,z1 in world units");
+        check(ovr_hip_set_clip_box(h, lo, hi));
+        if (!quiet) std::fprintf(stderr, "[hip] clip box (%g, %g, %g) .. (%g, %g, %g)\n", (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2]);
+      }
     }
     commit();
   }

@@ -1,0 +1,100 @@
+"""Register and scratch metadata of the march / shade kernels in a built libovr_hip.so, read from its embedded code objects (no GPU): the table of
+DESIGN.md section 12 and profiles/r09_clipping.md.
+
+    python tools/kernel_metadata.py LIB                   one line per raymarch_kernel / shade_pool_kernel instantiation
+    python tools/kernel_metadata.py LIB --against PARENT  every instantiation of PARENT must be in LIB with the same VGPRs, SGPRs, spilled scalars and
+                                                          scratch (exit status 1 otherwise); the instantiations only LIB has are summarised
+
+A template parameter appended behind the existing ones with the value `false` (how MAT and CLIP were added) renames every kernel: names are compared
+with trailing `false` parameters removed."""
+import argparse
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+FIELDS = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size")
+
+
+def read(lib):
+    """mangled kernel name -> {field: value} for the march / shade kernels of lib"""
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        shutil.copy(lib, os.path.join(tmp, "lib.so"))
+        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp, capture_output=True, check=True)
+        for f in sorted(os.listdir(tmp)):
+            if "gfx950" not in f:
+                continue
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=tmp, capture_output=True, text=True, check=True).stdout
+            name = None
+            for line in notes.splitlines():
+                line = line.strip()
+                if line.startswith(".name:"):
+                    name = line.split(":", 1)[1].strip()
+                    out[name] = {}
+                elif name:
+                    for k in FIELDS:
+                        if line.startswith(k + ":"):
+                            out[name][k] = int(line.split(":")[1])
+    return {n: k for n, k in out.items() if "raymarch_kernel" in n or "shade_pool_kernel" in n}
+
+
+def key(name):
+    """the instantiation without trailing `false` template parameters"""
+    m = re.match(r"(.*?(?:raymarch_kernel|shade_pool_kernel)I)((?:L[ib]\d+E)+)(E.*)", name)
+    if not m:
+        return name
+    params = re.findall(r"L[ib]\d+E", m.group(2))
+    while params and params[-1] == "Lb0E":
+        params.pop()
+    return m.group(1) + "".join(params) + m.group(3)
+
+
+def params(name):
+    m = re.match(r".*?(raymarch_kernel|shade_pool_kernel)I((?:L[ib]\d+E)+)E", name)
+    return m.group(1), [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2))]
+
+
+def rng(vals):
+    vals = list(vals)
+    return "-" if not vals else str(vals[0]) if min(vals) == max(vals) else f"{min(vals)}-{max(vals)}"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("lib")
+    ap.add_argument("--against")
+    a = ap.parse_args()
+    mine = {key(n): k for n, k in read(a.lib).items()}
+    if not a.against:
+        for n in sorted(mine):
+            print(n, " ".join(f"{f[1:]}={mine[n].get(f, 0)}" for f in FIELDS))
+        return 0
+    parent = {key(n): k for n, k in read(a.against).items()}
+    changed = [n for n in parent if n not in mine or mine[n] != parent[n]]
+    new = sorted(set(mine) - set(parent))
+    print(f"{len(parent)} instantiations in the parent, {len(parent) - len(changed)} with identical metadata here, {len(changed)} changed or missing")
+    for n in changed:
+        print("  CHANGED", n, parent[n], "->", mine.get(n))
+    print(f"{len(new)} new instantiations; using scratch: {sum(1 for n in new if mine[n].get('.private_segment_fixed_size', 0) > 0)}")
+    groups = {}
+    for n in new:
+        kern, p = params(n)
+        p = p + [0] * (9 - len(p))
+        g = (kern, p[1], "pooled" if kern == "raymarch_kernel" and p[3] else "", p[4] if kern == "raymarch_kernel" else p[3])
+        groups.setdefault(g, []).append(mine[n])
+    print("kernel | SHADE | | SKIP | n | VGPR | SGPR | spilled scalars | scratch")
+    for g in sorted(groups):
+        ks = groups[g]
+        print(" | ".join([g[0], str(g[1]), g[2], str(g[3]), str(len(ks))] + [rng(k.get(f, 0) for k in ks) for f in (FIELDS[0], FIELDS[1], FIELDS[2], FIELDS[4])]))
+    for n in new:
+        if mine[n].get(".private_segment_fixed_size", 0) > 0:
+            print("  SCRATCH", n, mine[n])
+    return 1 if changed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

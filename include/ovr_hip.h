@@ -136,6 +136,27 @@ int ovr_hip_set_volume(ovr_hip_renderer* r, const void* data, int mem_kind, int 
  * in a new process, 0.1 ms when the runtime still holds a freed block of that size), [2] copies into the device (host input: through a 1 GiB staging buffer;
  * a device array on another GPU: peer copies), [3] kernels (re-bricking, macrocell ranges, data range; layouts mode 2: the replicas) */
 int ovr_hip_get_upload_times(const ovr_hip_renderer* r, double out_ms[4]);
+/* extension (within ABI v11): replaces the voxels [lower, lower + extent) of the RESIDENT volume - a step of a time series, a
+ * simulation's new state, an edit - in place.  `data` = extent[0]*extent[1]*extent[2] scalars, x fastest, of the value_type the volume was set with; it
+ * is not referenced after the call returns.  Immediate like ovr_hip_set_volume (a frame in flight is resolved first), but nothing is freed or
+ * allocated - no layout, axis table or macrocell grid - and the device is not drained: box-restricted kernels rewrite the stored copies of the box's
+ * voxels in the general layout and in every replica that is resident or being built, and recompute the macrocells whose window meets the box and the
+ * data range.  Host input (or a device array on another GPU) travels through a staging buffer the renderer keeps and only ever grows.
+ * DEFINITION: afterwards every observable - frames, gradient layer, counters, macrocell grids, ovr_hip_get_volume_info, the bytes of every resident
+ * layout - is bit for bit what it would be after ovr_hip_set_volume with the patched array followed by the same setters and ovr_hip_commit.
+ * Reset: the accumulation (with it the convergence estimate, its retired blocks and the reconstruction's counts), the tuner's measurement, the
+ * adaptive-skipping probe, the pool's "roomy" mark.  Kept: the schedule, the queued and committed setters, the layouts' residency.
+ * OVR_HIP_EINVAL (the volume intact and renderable): a null argument, a bad mem_kind, a value_type other than the resident one, an extent < 1, a box
+ * that leaves the grid.  OVR_HIP_ESTATE: no volume is set.  A device group validates once, then updates every member; a device failure on any member
+ * after writing began leaves no member renderable (ovr_hip_set_volume's rule). */
+int ovr_hip_update_volume(ovr_hip_renderer* r, const void* data, int mem_kind, int value_type, const int32_t lower[3], const int32_t extent[3]);
+/* where the last ovr_hip_update_volume spent its time, milliseconds, like ovr_hip_get_upload_times: [0] the whole call, [1] allocation (0 unless the
+ * staging buffer grew), [2] copies into the device, [3] kernels */
+int ovr_hip_get_update_times(const ovr_hip_renderer* r, double out_ms[4]);
+/* for known-answer tests, like ovr_hip_get_macrocells: the raw bytes of a resident layout (0 general ... 3 quad) of member `member` (0 for an ordinary
+ * renderer), without the 64 bytes of slack behind it.  host == NULL only reports the size in *bytes.  OVR_HIP_ESTATE if that layout is not resident
+ * (a planned replica is not built for this call); a replica under construction is waited for. */
+int ovr_hip_get_volume_layout(ovr_hip_renderer* r, int32_t member, int32_t layout, void* host, size_t capacity_bytes, uint64_t* bytes);
 int ovr_hip_set_grid_convention(ovr_hip_renderer* r, int convention);
 /* diagnostic, pure host arithmetic (no device needed): the addressing mode the kernels would take for a volume of these dimensions and
  * type in the given layout (0 general ... 3 quad) with a transfer function of n_colors / n_alphas entries: 0 = 32-bit byte offsets,

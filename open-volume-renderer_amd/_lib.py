@@ -184,6 +184,9 @@ SYMBOLS = {
     "ovr_hip_get_clip_box": (C.c_int, [_H, C.POINTER(ClipBox)]),
     "ovr_hip_clip_intervals": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "ovr_hip_update_volume": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ovr_hip_get_update_times": (C.c_int, [_H, C.POINTER(C.c_double)]),
+    "ovr_hip_get_volume_layout": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

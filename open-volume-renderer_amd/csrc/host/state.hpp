@@ -6,6 +6,7 @@
 
 #include "../../../include/ovr_hip.h"
 #include "../ovr_hip_kernels.h"
+#include "../ovr_hip_update.h"
 #pragma GCC visibility push(hidden)
 #include "policy.hpp"
 #pragma GCC visibility pop
@@ -153,6 +154,7 @@ struct GroupState {
   ovr_hip_stats own_stats{};              // leader: its own frame's counters (ovr_hip_renderer::stats holds the group's sums)
   double gather_ms = 0.0;                 // leader: host time of the last frame's gather tail (after the slowest member's frame: wait for the shipments + scatter)
   double upload_ms = 0.0;                 // leader: wall time of the last volume upload over all members
+  double update_ms = 0.0;                 // leader: ... of the last ovr_hip_update_volume
   // Round 5: every follower has a host thread of its own (device set once, persistent): the leader posts commit / render_async / ship / finish to all of
   // them and waits on their counters, so the members' frames are enqueued side by side instead of one after the other (one thread driving 8 members
   // spent 225 us per frame on it, beside 485 us of device time per member).
@@ -219,6 +221,10 @@ struct ovr_hip_renderer {
   float data_lower = 0.f, data_upper = 0.f; // the volume's data range as the voxel read returns it (array.cpp:297)
   float* d_data_range = nullptr;
   double upload_ms[4] = { 0, 0, 0, 0 };   // the last ovr_hip_set_volume of THIS renderer: total, allocation, copies into the device, kernels (ovr_hip_get_upload_times)
+  // ovr_hip_update_volume: the staging buffer of host input (or of a device array on another GPU) - kept, only ever grown - and the last call's times
+  void* d_update_stage = nullptr;
+  size_t update_stage_bytes = 0;
+  double update_ms[4] = { 0, 0, 0, 0 };
 
   // the automatic decisions (policy.hpp): layout / pipeline tuner, automatic pipeline, adaptive skipping
   ovrhip::policy::Tuner tune;

@@ -525,10 +525,162 @@ static int set_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, i
   return 0;
 }
 
+// one renderer's ovr_hip_update_volume (a group member's or a single renderer's); the arguments have been checked.  r->update_ms like r->upload_ms
+static int update_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, int value_type, const int32_t lower[3], const int32_t extent[3])
+{
+  const auto t_call = std::chrono::high_resolution_clock::now();
+  UploadTimes t;
+  for (double& v : r->update_ms) v = 0.0;
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame_one(r)) return e; // the frame in flight was the last reader of the layouts: nothing else is drained
+  hipStream_t st = r->own_stream[0];
+  update::Box box;
+  for (int k = 0; k < 3; ++k) { box.lo[k] = lower[k]; box.hi[k] = lower[k] + extent[k]; }
+
+  // a replica's build must never read a half-written general layout: the host part of every build ends here, the device part is waited for by
+  // the update's stream (a replica that is only planned needs nothing - its build will read the updated layout)
+  join_builders(r);
+  for (int k = 1; k < kLayouts; ++k)
+    if (r->replica_state[k].load(std::memory_order_acquire) == 2) HIP_TRY(hipStreamWaitEvent(st, r->build_ev[k], 0));
+
+  const size_t in_es = value_type_size(value_type);
+  const size_t slice_bytes = (size_t)extent[0] * (size_t)extent[1] * in_es;
+  int src_device = r->device;
+  if (mem_kind == OVR_HIP_MEM_DEVICE) {
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, data) == hipSuccess) src_device = attr.device;
+    else (void)hipGetLastError();
+  }
+  const bool direct = mem_kind == OVR_HIP_MEM_DEVICE && src_device == r->device;
+  size_t slab = (size_t)extent[2];
+  if (!direct) { // staged like upload_voxels: slabs of <= 1 GiB through the renderer's buffer
+    slab = std::min<size_t>(std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(1, slice_bytes)), (size_t)extent[2]);
+    if (r->update_stage_bytes < slab * slice_bytes) {
+      const auto t_seg = std::chrono::high_resolution_clock::now();
+      if (r->d_update_stage) HIP_TRY(hipFree(r->d_update_stage)); // (idle: every update ends with its stream drained)
+      r->d_update_stage = nullptr; r->update_stage_bytes = 0;
+      HIP_TRY(hipMalloc(&r->d_update_stage, slab * slice_bytes));
+      r->update_stage_bytes = slab * slice_bytes;
+      t.alloc += ms_since(t_seg);
+    }
+  }
+  // from here on the layouts are being written: a device failure leaves a volume that is neither the old nor the new one
+  auto write = [&]() -> int {
+    for (int z0 = 0; z0 < extent[2]; z0 += (int)slab) {
+      const int nzc = (int)std::min<size_t>(slab, (size_t)(extent[2] - z0));
+      const void* src = (const char*)data + (size_t)z0 * slice_bytes;
+      auto t_seg = std::chrono::high_resolution_clock::now();
+      if (!direct) {
+        HIP_TRY(mem_kind == OVR_HIP_MEM_DEVICE ? hipMemcpyPeerAsync(r->d_update_stage, r->device, src, src_device, (size_t)nzc * slice_bytes, st)
+                                               : hipMemcpyAsync(r->d_update_stage, src, (size_t)nzc * slice_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t.copy += ms_since(t_seg);
+        t_seg = std::chrono::high_resolution_clock::now();
+        src = r->d_update_stage;
+      }
+      update::Box part = box;
+      part.lo[2] = box.lo[2] + z0; part.hi[2] = part.lo[2] + nzc;
+      HIP_TRY(launch_update_general(src, value_type, r->d_replica[0], r->vd_replica[0], part, st));
+      if (!direct) HIP_TRY(hipStreamSynchronize(st)); // the next slab's copy overwrites what this kernel reads
+      t.kern += ms_since(t_seg);
+    }
+    const auto t_seg = std::chrono::high_resolution_clock::now();
+    VolumeDesc g = r->vd_replica[LAYOUT_GENERAL];
+    g.data = r->d_volume;
+    for (int k = 1; k < kLayouts; ++k) {
+      const int state = r->replica_state[k].load(std::memory_order_acquire);
+      if (state == 2 || state == 3) HIP_TRY(launch_update_replica(g, r->d_replica[k], r->vd_replica[k], box, st));
+    }
+    // the macrocells whose window meets the box, then the data range over all of them - and what ovr_hip_set_volume derives from it
+    const int dims[3] = { r->vd.nx, r->vd.ny, r->vd.nz };
+    VolumeDesc vd = r->vd;
+    vd.data = r->d_volume;
+    HIP_TRY(launch_macrocell_ranges_box(vd, r->d_mc_minmax, update::macrocell_range(dims, box), st));
+    HIP_TRY(launch_minmax_reduce(r->d_mc_minmax, (unsigned long long)r->mc_cells, r->d_data_range, st));
+    float dr[2] = { 0.f, 0.f };
+    HIP_TRY(hipMemcpyAsync(dr, r->d_data_range, sizeof(dr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st)); // the update is resident; frames on any stream are enqueued behind it
+    r->data_lower = dr[0];
+    r->data_upper = dr[1];
+    r->P.tf_lower = dr[0];
+    r->P.tf_upper = dr[1];
+    update_tfn_range(r);
+    t.kern += ms_since(t_seg);
+    return 0;
+  };
+  if (!r->d_mc_minmax || !r->mc_ranges_valid) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_update_volume: the resident volume has no macrocell ranges");
+  if (int e = write()) {
+    r->have_volume = false;
+    return e;
+  }
+  r->mc_majorant_valid = false; // rebuilt whole with the next frame that skips; restarts the adaptive-skipping probe (policy::Skip)
+  r->fb_reset = true;
+  r->conv.valid = false; r->conv.retired = 0; r->conv.active = r->sched.n_work; // what a commit does with a pending reset
+  r->tune.state = 0;
+  r->pool_roomy = false;
+  r->update_ms[0] = ms_since(t_call); r->update_ms[1] = t.alloc; r->update_ms[2] = t.copy; r->update_ms[3] = t.kern;
+  return 0;
+}
+
 } // namespace host
 } // namespace ovrhip
 
 extern "C" {
+
+int ovr_hip_update_volume(ovr_hip_renderer* r, const void* data, int mem_kind, int value_type, const int32_t lower[3], const int32_t extent[3])
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_update_volume: null argument");
+  if (!r->have_volume && data && lower && extent) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_update_volume: no volume is set");
+  // checked once, on the handle the caller holds, before anything is posted to a member
+  const int dims[3] = { r->vd.nx, r->vd.ny, r->vd.nz };
+  if (const int rule = update::check_arguments(data, lower, extent, mem_kind, value_type, r->value_type, dims))
+    return fail(OVR_HIP_EINVAL, std::string("[hip] ovr_hip_update_volume: ") + update::check_text(rule));
+  if (r->group.members.size() <= 1) return update_volume_one(r, data, mem_kind, value_type, lower, extent);
+  const auto t0 = std::chrono::high_resolution_clock::now();
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  const int e = group_call(r, [=](ovr_hip_renderer* m) { return update_volume_one(m, data, mem_kind, value_type, lower, extent); },
+                           [&] { return update_volume_one(r, data, mem_kind, value_type, lower, extent); });
+  if (e) {
+    const std::string msg = g_last_error;
+    for (ovr_hip_renderer* m : r->group.members) m->have_volume = false;
+    return fail(e, msg + " (device group: the update failed on a member - no member keeps a volume)");
+  }
+  r->group.update_ms = ms_since(t0);
+  return 0;
+}
+
+int ovr_hip_get_update_times(const ovr_hip_renderer* r, double out_ms[4])
+{
+  if (!r || !out_ms) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_update_times: null argument");
+  for (int i = 0; i < 4; ++i) out_ms[i] = r->update_ms[i];
+  if (r->group.members.size() > 1) out_ms[0] = r->group.update_ms;
+  return 0;
+}
+
+int ovr_hip_get_volume_layout(ovr_hip_renderer* r, int32_t member, int32_t layout, void* host, size_t capacity_bytes, uint64_t* bytes)
+{
+  if (!r || !bytes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_volume_layout: null argument");
+  const size_t members = std::max<size_t>(r->group.members.size(), 1);
+  if (member < 0 || (size_t)member >= members || layout < 0 || layout >= kLayouts) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_volume_layout: no such member or layout");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  ovr_hip_renderer* m = members > 1 ? r->group.members[(size_t)member] : r;
+  if (!m->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_volume_layout: no volume is set");
+  if (m->builder[layout].joinable()) m->builder[layout].join();
+  const int state = m->replica_state[layout].load(std::memory_order_acquire);
+  if (state != 2 && state != 3) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_volume_layout: that layout is not resident");
+  *bytes = (uint64_t)m->vd_replica[layout].bytes;
+  if (!host) return 0;
+  if (capacity_bytes < (size_t)*bytes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_volume_layout: output too small");
+  if (int e = set_device(m)) return e;
+  hipError_t err = state == 2 ? hipEventSynchronize(m->build_ev[layout]) : hipSuccess;
+  if (err == hipSuccess) err = hipMemcpy(host, m->d_replica[layout], (size_t)*bytes, hipMemcpyDeviceToHost);
+  (void)set_device(r);
+  if (err != hipSuccess) return fail(OVR_HIP_EDEVICE, std::string("[hip] ovr_hip_get_volume_layout: ") + hipGetErrorString(err));
+  if (state == 2) m->replica_state[layout] = 3;
+  return 0;
+}
 
 int ovr_hip_set_volume(ovr_hip_renderer* r, const void* data, int mem_kind, int value_type, const int32_t dims[3],
                        const float grid_origin[3], const float grid_spacing[3])

@@ -114,6 +114,7 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_counters) (void)hipFree(r->d_counters);
   if (r->d_sparse_count) (void)hipFree(r->d_sparse_count);
   if (r->d_data_range) (void)hipFree(r->d_data_range);
+  if (r->d_update_stage) (void)hipFree(r->d_update_stage);
   if (r->h_counters) (void)hipHostFree(r->h_counters);
   if (r->conv.h_publish) (void)hipHostFree(r->conv.h_publish);
   if (r->recon.h_publish) (void)hipHostFree(r->recon.h_publish);

@@ -15,6 +15,7 @@
 // composites in ray order (pooled pipeline), or that the tile's own wave shades (in-place pipeline).  The transfer
 // function (colour float4 table + alpha table, 20 KiB at the shipped resolution of 1024), the per-axis brick-offset tables,
 #include "ovr_hip_device.h"
+#include "ovr_hip_update.h"
 
 namespace ovrhip {
 static_assert(kPoolSubs <= 64 && (kPoolSubs & (kPoolSubs - 1)) == 0, "reduce_counters_kernel reduces the sub-pool counters with one wave");
@@ -1044,6 +1045,7 @@ template <typename TI> struct SrcLinear {
 template <int VTB> struct SrcBricked {
   typedef typename Vox<VTB>::T value_type;
   static constexpr bool kLinear = false;
+  static constexpr bool kBox = false;
   const value_type* p; unsigned int macro_y; unsigned long long macro_z;
   __device__ __forceinline__ value_type get(size_t x, size_t y, unsigned z) const
   {
@@ -1301,6 +1303,193 @@ hipError_t launch_rebrick(const VolumeDesc& general, void* dst, const VolumeDesc
   return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// ovr_hip_update_volume: the box-restricted siblings of relayout_kernel / relayout_quad_kernel.  The ranges of macro rows,
+// layers, macro blocks and bricks come from host/update_extent.hpp; a kernel applies the per-row predicate "holds a copy of a voxel in the box"
+// ------------------------------------------------------------------------------------------------------------------
+// the caller's box array: voxel (x, y, z) of the volume for x, y, z inside the box
+template <typename TI> struct SrcBox {
+  typedef TI value_type;
+  static constexpr bool kBox = true;
+  const TI* p; int x0, y0, z0, ex, ey;
+  __device__ __forceinline__ TI get(size_t x, size_t y, unsigned z) const { return p[(x - (size_t)x0) + (size_t)ex * ((y - (size_t)y0) + (size_t)ey * (size_t)(z - (unsigned)z0))]; }
+};
+// the box in the layout's axes (a = pair axis, b = the other one), voxels [lo, hi), and where the launch's grid starts
+struct UpdateRows { int alo, ahi, blo, bhi, zlo, zhi; int brick_lo, brick_hi, macro_lo, macros, row_lo, layer_lo; };
+
+// Rows in storage order like relayout_kernel's: a workgroup owns the slab of one macro row and one z layer and sweeps the macro blocks that meet the
+// box, so where the box spans whole macro rows every 128-byte line still leaves the workgroup complete.  From the box array (SrcBox: the general
+// layout) a row wholly inside the box is one unaligned vector load and one row store, a row partly inside is read, patched and stored; from the
+// general layout (SrcBricked: a replica) the whole row is rewritten - its other elements are current in the source.  Padding rows are never touched.
+template <typename SRC, typename TO, int VT>
+__global__ __launch_bounds__(256) void update_rows_kernel(const SRC src, TO* __restrict__ dst, int nx, int ny, unsigned int macro_y, unsigned long long macro_z, const UpdateRows u)
+{
+  typedef typename SRC::value_type TI;
+  typedef BrickMap<VT> M;
+  typedef Vox<VT> V;
+  constexpr bool TR = V::kTransposed;
+  constexpr unsigned SX = M::SX, RB = 1u << (V::by + V::bz);
+  constexpr unsigned ROWS = M::sbz / SX;
+  constexpr unsigned LZ = 32u >> V::bz;
+  const int na = TR ? ny : nx;
+  const unsigned my = (unsigned)u.row_lo + blockIdx.x, layer = (unsigned)u.layer_lo + blockIdx.y;
+  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * M::sbz + (unsigned long long)(layer / LZ) * macro_z;
+  const unsigned total = (unsigned)u.macros * ROWS;
+  for (unsigned g = threadIdx.x; g < total; g += 256u) {
+    const unsigned ml = g / ROWS, i = g - ml * ROWS, mx = (unsigned)u.macro_lo + ml;
+    const unsigned rr = i & (RB - 1u), bi = i / RB;
+    const unsigned ybk = bi / V::mbx, bm = bi - ybk * V::mbx;
+    const int b = (int)(my * 32u + (ybk << V::by) + (rr & ((1u << V::by) - 1u)));
+    const int z = (int)((layer << V::bz) + (rr >> V::by));
+    const int br = (int)(mx * V::mbx + bm);
+    if (b < u.blo || b >= u.bhi || z < u.zlo || z >= u.zhi || br < u.brick_lo || br > u.brick_hi) continue;
+    RowOut<TO, SX>* const row = reinterpret_cast<RowOut<TO, SX>*>(dst + slab + (unsigned long long)mx * M::MV + (unsigned long long)i * SX);
+    const int v0 = br * V::cx - 1;
+    RowOut<TO, SX> out;
+    if constexpr (SRC::kBox) {
+      static_assert(!TR, "the caller's array goes into the general layout");
+      if (v0 >= u.alo && v0 + (int)SX <= u.ahi) {
+        const RowIn<TI, SX> w = *reinterpret_cast<const RowIn<TI, SX>*>(&src.p[((size_t)v0 - (size_t)src.x0) + (size_t)src.ex * (((size_t)b - (size_t)src.y0) + (size_t)src.ey * (size_t)(z - src.z0))]);
+#pragma unroll
+        for (unsigned k = 0; k < SX; ++k) out.v[k] = Conv<TI, TO>::cv(w.v[k]);
+      }
+      else {
+        out = *row;
+#pragma unroll
+        for (unsigned k = 0; k < SX; ++k) {
+          const int as = min(max(v0 + (int)k, 0), na - 1);
+          if (as >= u.alo && as < u.ahi) out.v[k] = Conv<TI, TO>::cv(src.get((size_t)as, (size_t)b, (unsigned)z));
+        }
+      }
+    }
+    else {
+#pragma unroll
+      for (unsigned k = 0; k < SX; ++k) {
+        const size_t as = (size_t)min(max(v0 + (int)k, 0), na - 1);
+        out.v[k] = Conv<TI, TO>::cv(TR ? src.get((size_t)b, as, (unsigned)z) : src.get(as, (size_t)b, (unsigned)z));
+      }
+    }
+    *row = out;
+  }
+}
+
+// the cells [u_lo, u_hi] x [v_lo, v_hi] x [zlo, zhi) of a quad replica (the box grown by one cell: cell (u, v) holds x in { u - 1, u }, y in { v - 1, v })
+struct UpdateCells { int u_lo, u_hi, v_lo, v_hi, zlo, zhi; int macro_lo, macros, row_lo, layer_lo; };
+template <typename SRC, int VT>
+__global__ __launch_bounds__(256) void update_quad_kernel(const SRC src, typename Vox<VT>::T* __restrict__ dst, int nx, int ny, unsigned int macro_y, unsigned long long macro_z,
+                                                         const UpdateCells c)
+{
+  typedef typename SRC::value_type TI;
+  typedef BrickMap<VT> M;
+  typedef Vox<VT> V;
+  typedef typename V::T TO;
+  typedef typename V::Q Q;
+  constexpr unsigned CB = 1u << (V::lx + V::ly + V::lz);
+  constexpr unsigned LAYER = M::bx_ * M::by_ * M::BV;
+  constexpr unsigned CELLS = M::bx_ * M::by_ * CB;
+  constexpr unsigned LZ = 32u >> V::lz;
+  const unsigned my = (unsigned)c.row_lo + blockIdx.x, layer = (unsigned)c.layer_lo + blockIdx.y;
+  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * LAYER + (unsigned long long)(layer / LZ) * macro_z;
+  const unsigned total = (unsigned)c.macros * CELLS;
+  for (unsigned g = threadIdx.x; g < total; g += 256u) {
+    const unsigned ml = g / CELLS, i = g - ml * CELLS, mx = (unsigned)c.macro_lo + ml;
+    const unsigned j = i & (CB - 1u), brick = i / CB;
+    const int u = (int)(mx * 32u + ((brick & (M::bx_ - 1u)) << V::lx) + (j & ((1u << V::lx) - 1u)));
+    const int v = (int)(my * 32u + ((brick / M::bx_) << V::ly) + ((j >> V::lx) & ((1u << V::ly) - 1u)));
+    const int z = (int)((layer << V::lz) + (j >> (V::lx + V::ly)));
+    if (u < c.u_lo || u > c.u_hi || v < c.v_lo || v > c.v_hi || z < c.zlo || z >= c.zhi) continue;
+    Q* const cell = reinterpret_cast<Q*>(dst + slab + (unsigned long long)mx * M::MV + (unsigned long long)i * 4u);
+    const int x = max(u - 1, 0), y = max(v - 1, 0);
+    const int x1 = min(u, nx - 1), y1 = min(v, ny - 1);
+    Q q;
+    q.x = Conv<TI, TO>::cv(src.get((size_t)x, (size_t)y, (unsigned)z)); q.y = Conv<TI, TO>::cv(src.get((size_t)x1, (size_t)y, (unsigned)z));
+    q.z = Conv<TI, TO>::cv(src.get((size_t)x, (size_t)y1, (unsigned)z)); q.w = Conv<TI, TO>::cv(src.get((size_t)x1, (size_t)y1, (unsigned)z));
+    *cell = q;
+  }
+}
+
+template <int VT> static update::Geometry update_geometry()
+{
+  typedef Vox<VT> V;
+  update::Geometry g{ V::cx, V::mbx, V::by, V::bz, V::kTransposed, V::kQuad, 0, 0, 0 };
+  if constexpr (V::kQuad) { g.lx = V::lx; g.ly = V::ly; g.lz = V::lz; }
+  return g;
+}
+constexpr int kUpdateLayers = 32768; // z layers per launch (grid.y)
+
+template <typename SRC, typename TO, int VT>
+static hipError_t update_rows_s(const SRC& src, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  const int dims[3] = { vd.nx, vd.ny, vd.nz };
+  const update::BrickRange r = update::brick_range(update_geometry<VT>(), dims, vd.macros_x, box);
+  constexpr int ia = Vox<VT>::kTransposed ? 1 : 0, ib = Vox<VT>::kTransposed ? 0 : 1;
+  for (int l0 = r.layer_lo; l0 <= r.layer_hi; l0 += kUpdateLayers) {
+    const UpdateRows u{ box.lo[ia], box.hi[ia], box.lo[ib], box.hi[ib], box.lo[2], box.hi[2], r.brick_lo, r.brick_hi, r.macro_lo, r.macro_hi - r.macro_lo + 1, r.row_lo, l0 };
+    const dim3 grid((unsigned)(r.row_hi - r.row_lo + 1), (unsigned)(std::min(r.layer_hi, l0 + kUpdateLayers - 1) - l0 + 1));
+    hipLaunchKernelGGL((update_rows_kernel<SRC, TO, VT>), grid, dim3(256), 0, stream, src, (TO*)dst, vd.nx, vd.ny, vd.macro_elems * (unsigned)vd.macros_x,
+                       (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, u);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
+}
+template <typename SRC, int VT>
+static hipError_t update_quad_s(const SRC& src, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  const update::QuadRange r = update::quad_range(update_geometry<VT>(), box);
+  for (int l0 = r.layer_lo; l0 <= r.layer_hi; l0 += kUpdateLayers) {
+    const UpdateCells c{ r.u_lo, r.u_hi, r.v_lo, r.v_hi, box.lo[2], box.hi[2], r.macro_lo, r.macro_hi - r.macro_lo + 1, r.row_lo, l0 };
+    const dim3 grid((unsigned)(r.row_hi - r.row_lo + 1), (unsigned)(std::min(r.layer_hi, l0 + kUpdateLayers - 1) - l0 + 1));
+    hipLaunchKernelGGL((update_quad_kernel<SRC, VT>), grid, dim3(256), 0, stream, src, (typename Vox<VT>::T*)dst, vd.nx, vd.ny, vd.macro_elems * (unsigned)vd.macros_x,
+                       (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, c);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
+}
+template <typename TI, typename TO, int VT>
+static hipError_t update_general_t(const void* src, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  if (vd.type != VT) return hipErrorInvalidValue;
+  return update_rows_s<SrcBox<TI>, TO, VT>(SrcBox<TI>{ (const TI*)src, box.lo[0], box.lo[1], box.lo[2], box.hi[0] - box.lo[0], box.hi[1] - box.lo[1] }, dst, vd, box, stream);
+}
+hipError_t launch_update_general(const void* src, int vt, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  switch (vt) { // the reference's ValueType, as in launch_relayout: the same Conv per element
+  case 100: return update_general_t<unsigned char, unsigned char, VOX_U8>(src, dst, vd, box, stream);
+  case 101: return update_general_t<signed char, signed char, VOX_I8>(src, dst, vd, box, stream);
+  case 200: return update_general_t<unsigned short, unsigned short, VOX_U16>(src, dst, vd, box, stream);
+  case 201: return update_general_t<short, short, VOX_I16>(src, dst, vd, box, stream);
+  case 300: return update_general_t<unsigned int, float, VOX_F32>(src, dst, vd, box, stream);
+  case 301: return update_general_t<int, float, VOX_F32>(src, dst, vd, box, stream);
+  case 400: return update_general_t<float, float, VOX_F32>(src, dst, vd, box, stream);
+  case 500: return update_general_t<double, float, VOX_F32>(src, dst, vd, box, stream);
+  default: return hipErrorInvalidValue;
+  }
+}
+template <int VTB>
+static hipError_t update_replica_b(const VolumeDesc& g, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  typedef typename Vox<VTB>::T T;
+  typedef SrcBricked<VTB> Src;
+  const Src src{ (const T*)g.data, g.macro_elems * (unsigned)g.macros_x, (unsigned long long)g.macro_elems * (unsigned long long)g.macros_x * (unsigned long long)g.macros_y };
+  constexpr int T1 = VTB == VOX_F32 ? VOX_F32_T : VOX_U16_T, T2 = VTB == VOX_F32 ? VOX_F32_TT : VOX_U16_TT;
+  constexpr int TQ = VTB == VOX_F32 ? VOX_F32_Q : VTB == VOX_U16 ? VOX_U16_Q : VOX_U8_Q;
+  if (vd.type == TQ) return update_quad_s<Src, TQ>(src, dst, vd, box, stream);
+  if constexpr (VTB != VOX_U8) {
+    if (vd.type == T1) return update_rows_s<Src, T, T1>(src, dst, vd, box, stream);
+    if (vd.type == T2) return update_rows_s<Src, T, T2>(src, dst, vd, box, stream);
+  }
+  return hipErrorInvalidValue;
+}
+hipError_t launch_update_replica(const VolumeDesc& general, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
+{
+  switch (general.type) {
+  case VOX_F32: return update_replica_b<VOX_F32>(general, dst, vd, box, stream);
+  case VOX_U16: return update_replica_b<VOX_U16>(general, dst, vd, box, stream);
+  case VOX_U8: return update_replica_b<VOX_U8>(general, dst, vd, box, stream);
+  default: return hipErrorInvalidValue;
+  }
+}
+
 // per-axis offset tables of a layout (VolumeDesc::axis_ab / axis_z), once per volume
 template <int VT>
 __global__ __launch_bounds__(256) void axis_tables_kernel(VolumeDesc vd, unsigned int* __restrict__ ab, unsigned long long* __restrict__ tz)
@@ -1363,8 +1552,10 @@ hipError_t launch_axis_tables(VolumeDesc& vd, void* d_tables, hipStream_t stream
 // A lane owns (y, z) ROWS of the cell's 18^3 box - rows in storage order, so the four lanes of a quad read 64 contiguous bytes - and walks each
 // along x brick by brick: one 8- or 16-byte load per brick row (SX stored voxels), the voxels outside the box masked.  (Until round 4: one voxel per
 // lane and step, each with its own offset arithmetic and three runtime divisions - 2.8 ms for C3, 20.6 ms for C4, bound by the gather-instruction rate.)
+// (the value range of cell (cx, cy, cz), reduced over the wave: what macrocell_range_kernel computes for every cell and macrocell_range_box_kernel for the
+// cells an ovr_hip_update_volume touched - one text, so a recomputed cell is a full rebuild's bit for bit)
 template <int VT>
-__global__ __launch_bounds__(256) void macrocell_range_kernel(const void* __restrict__ vol, VolumeDesc vd, int mcx, int mcy, int mcz, float2* __restrict__ out)
+__device__ __forceinline__ float2 macrocell_cell_range(const void* __restrict__ vol, const VolumeDesc& vd, int cx, int cy, int cz, int lane)
 {
   typedef BrickMap<VT> M;
   typedef Vox<VT> V;
@@ -1373,10 +1564,6 @@ __global__ __launch_bounds__(256) void macrocell_range_kernel(const void* __rest
   constexpr int W = 16;
   // brick-aligned spans that hold W + 2 rows at any alignment
   constexpr unsigned AY = (W + 2 + 2 * (HY - 1) + HY - 1) / HY, AZ = (W + 2 + 2 * (HZ - 1) + HZ - 1) / HZ; // in bricks
-  const int lane = threadIdx.x & 63;
-  const unsigned long long cell = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (cell >= (unsigned long long)mcx * mcy * mcz) return;
-  const int cx = (int)(cell % mcx), cy = (int)((cell / mcx) % mcy), cz = (int)(cell / ((unsigned long long)mcx * mcy));
   const int bx = max(cx * W - 1, 0), by = max(cy * W - 1, 0), bz = max(cz * W - 1, 0);
   const int ex = min(bx + W + 1, vd.nx), ey = min(by + W + 1, vd.ny), ez = min(bz + W + 1, vd.nz);
   const unsigned macro_y = vd.macro_elems * (unsigned)vd.macros_x;
@@ -1412,7 +1599,29 @@ __global__ __launch_bounds__(256) void macrocell_range_kernel(const void* __rest
     lo = fminf(lo, __shfl_xor(lo, off));
     hi = fmaxf(hi, __shfl_xor(hi, off));
   }
-  if (lane == 0) out[cell] = make_float2(lo, hi);
+  return make_float2(lo, hi);
+}
+template <int VT>
+__global__ __launch_bounds__(256) void macrocell_range_kernel(const void* __restrict__ vol, VolumeDesc vd, int mcx, int mcy, int mcz, float2* __restrict__ out)
+{
+  const int lane = threadIdx.x & 63;
+  const unsigned long long cell = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (cell >= (unsigned long long)mcx * mcy * mcz) return;
+  const int cx = (int)(cell % mcx), cy = (int)((cell / mcx) % mcy), cz = (int)(cell / ((unsigned long long)mcx * mcy));
+  const float2 r = macrocell_cell_range<VT>(vol, vd, cx, cy, cz, lane);
+  if (lane == 0) out[cell] = r;
+}
+// ovr_hip_update_volume: the cells lo ... lo + n - 1 per axis alone
+template <int VT>
+__global__ __launch_bounds__(256) void macrocell_range_box_kernel(const void* __restrict__ vol, VolumeDesc vd, int mcx, int mcy, int lx, int ly, int lz, int nx, int ny, int nz,
+                                                                 float2* __restrict__ out)
+{
+  const int lane = threadIdx.x & 63;
+  const unsigned long long s = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (s >= (unsigned long long)nx * ny * nz) return;
+  const int cx = lx + (int)(s % nx), cy = ly + (int)((s / nx) % ny), cz = lz + (int)(s / ((unsigned long long)nx * ny));
+  const float2 r = macrocell_cell_range<VT>(vol, vd, cx, cy, cz, lane);
+  if (lane == 0) out[(unsigned long long)cx + (unsigned long long)mcx * ((unsigned long long)cy + (unsigned long long)mcy * (unsigned long long)cz)] = r;
 }
 
 // majorant_kernel, sp_singlemc.cu:56-97: the alpha table is staged in LDS exactly as the reference stages it in shared memory
@@ -1451,6 +1660,25 @@ hipError_t launch_macrocell_ranges(const VolumeDesc& vd, float* out_minmax, hipS
   case VOX_I16: hipLaunchKernelGGL(macrocell_range_kernel<VOX_I16>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
   default: hipLaunchKernelGGL(macrocell_range_kernel<VOX_F32>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_macrocell_ranges_box(const VolumeDesc& vd, float* out_minmax, const update::CellRange& c, hipStream_t stream)
+{
+  const int mcx = (vd.nx + 15) / 16, mcy = (vd.ny + 15) / 16, mcz = (vd.nz + 15) / 16;
+  const int nx = c.hi[0] - c.lo[0] + 1, ny = c.hi[1] - c.lo[1] + 1, nz = c.hi[2] - c.lo[2] + 1;
+  if (c.lo[0] < 0 || c.lo[1] < 0 || c.lo[2] < 0 || nx < 1 || ny < 1 || nz < 1 || c.hi[0] >= mcx || c.hi[1] >= mcy || c.hi[2] >= mcz) return hipErrorInvalidValue;
+  const unsigned long long cells = (unsigned long long)nx * ny * nz;
+  const dim3 grid((unsigned)((cells + 3) / 4)), block(256);
+#define OVR_MC_BOX(VT) hipLaunchKernelGGL(macrocell_range_box_kernel<VT>, grid, block, 0, stream, vd.data, vd, mcx, mcy, c.lo[0], c.lo[1], c.lo[2], nx, ny, nz, (float2*)out_minmax)
+  switch (vd.type) {
+  case VOX_U8: OVR_MC_BOX(VOX_U8); break;
+  case VOX_I8: OVR_MC_BOX(VOX_I8); break;
+  case VOX_U16: OVR_MC_BOX(VOX_U16); break;
+  case VOX_I16: OVR_MC_BOX(VOX_I16); break;
+  default: OVR_MC_BOX(VOX_F32); break;
+  }
+#undef OVR_MC_BOX
   return hipGetLastError();
 }
 

@@ -450,11 +450,9 @@ class DeviceHIP:
             L.check(self._lib.ovr_hip_set_volume_sampling_rate(self._h, float(scene.volume_sampling_rate)))
         self.commit()
 
-    def _upload_volume(self, scene: Scene):
-        vol = scene.volume
-        if vol is None:
-            raise RuntimeError("expect only one instance")  # parse_single_volume_scene, scene.h:416
-        origin, spacing = _f3(scene.grid_origin), _f3(scene.grid_spacing)
+    @staticmethod
+    def _volume_array(vol):
+        """a (nz, ny, nx) numpy array or torch tensor, host or device -> (contiguous array - keep it alive -, pointer, mem kind, value type)"""
         if isinstance(vol, np.ndarray):
             if vol.ndim != 3:
                 raise RuntimeError("volume must have shape (nz, ny, nx)")
@@ -462,9 +460,7 @@ class DeviceHIP:
             vt = _NP_TO_TYPE.get(vol.dtype)
             if vt is None:
                 raise RuntimeError("[Optix7] unexpected volume type ...")
-            dims = (C.c_int32 * 3)(vol.shape[2], vol.shape[1], vol.shape[0])
-            L.check(self._lib.ovr_hip_set_volume(self._h, C.c_void_p(vol.ctypes.data), L.MEM_HOST, vt, dims, origin, spacing))
-            return
+            return vol, C.c_void_p(vol.ctypes.data), L.MEM_HOST, vt
         import torch
         if not isinstance(vol, torch.Tensor) or vol.dim() != 3:
             raise RuntimeError("volume must be a numpy array or torch tensor of shape (nz, ny, nx)")
@@ -476,11 +472,40 @@ class DeviceHIP:
         vt = tmap.get(vol.dtype)
         if vt is None:
             raise RuntimeError("[Optix7] unexpected volume type ...")
-        dims = (C.c_int32 * 3)(vol.shape[2], vol.shape[1], vol.shape[0])
-        kind = L.MEM_DEVICE if vol.is_cuda else L.MEM_HOST
         if vol.is_cuda:
             torch.cuda.current_stream(vol.device).synchronize()
-        L.check(self._lib.ovr_hip_set_volume(self._h, C.c_void_p(vol.data_ptr()), kind, vt, dims, origin, spacing))
+        return vol, C.c_void_p(vol.data_ptr()), (L.MEM_DEVICE if vol.is_cuda else L.MEM_HOST), vt
+
+    def _upload_volume(self, scene: Scene):
+        if scene.volume is None:
+            raise RuntimeError("expect only one instance")  # parse_single_volume_scene, scene.h:416
+        origin, spacing = _f3(scene.grid_origin), _f3(scene.grid_spacing)
+        vol, ptr, kind, vt = self._volume_array(scene.volume)
+        dims = (C.c_int32 * 3)(vol.shape[2], vol.shape[1], vol.shape[0])
+        L.check(self._lib.ovr_hip_set_volume(self._h, ptr, kind, vt, dims, origin, spacing))
+
+    def update_volume(self, array, lower):
+        """ovr_hip_update_volume: `array` (nz, ny, nx) - numpy or torch, host or device, of the resident volume's type -
+        replaces the voxels [lower, lower + extent) of the resident volume in place; lower = (x, y, z).  Immediate, like the upload in init();
+        afterwards the renderer is, bit for bit, what a fresh upload of the patched array would have made it."""
+        vol, ptr, kind, vt = self._volume_array(array)
+        lo = (C.c_int32 * 3)(*[int(v) for v in lower])
+        ext = (C.c_int32 * 3)(vol.shape[2], vol.shape[1], vol.shape[0])
+        L.check(self._lib.ovr_hip_update_volume(self._h, ptr, kind, vt, lo, ext))
+
+    def update_times(self):
+        """milliseconds of the last update_volume: dict(total, alloc, copy, kernels), like upload_times()"""
+        out = (C.c_double * 4)()
+        L.check(self._lib.ovr_hip_get_update_times(self._h, out))
+        return dict(total_ms=out[0], alloc_ms=out[1], copy_ms=out[2], kernels_ms=out[3])
+
+    def volume_layout(self, layout, member=0):
+        """the raw bytes (numpy uint8) of a resident layout of the volume, 0 general ... 3 quad: a known-answer hook like macrocells()"""
+        n = C.c_uint64()
+        L.check(self._lib.ovr_hip_get_volume_layout(self._h, int(member), int(layout), None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        L.check(self._lib.ovr_hip_get_volume_layout(self._h, int(member), int(layout), C.c_void_p(out.ctypes.data), out.nbytes, C.byref(n)))
+        return out
 
     def commit(self):
         L.check(self._lib.ovr_hip_commit(self._h))

@@ -637,7 +637,7 @@ static int read_frame_stats(ovr_hip_renderer* r)
   if (r->h_counters[7] > 0) r->outside_hits = true;
   if (r->outside_hits) r->map_whole_set(r->frame_set);
   r->stats.lds_fallback_taps = r->stats.lds_unstaged_rounds = r->stats.lds_rounds = 0;
-  if (r->P.lds_staging && !r->P.majorant && r->P.shading == 0 && !r->P.sparse_xy && r->P.vol.type == VOX_F32) {
+  if (raymarch_lds_staged(r->P)) {
     // the unshaded f32 march ran its LDS-staged variant: the two skip counters carried its diagnostics
     r->stats.lds_fallback_taps = r->h_counters[5];
     r->stats.lds_unstaged_rounds = r->h_counters[6];

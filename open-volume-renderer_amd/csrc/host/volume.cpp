@@ -347,10 +347,11 @@ static int plan_replicas(ovr_hip_renderer* r, int vt, const VolumeDesc& vd)
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     double planned = 0.0;
-    auto plan = [&](int k) { VolumeDesc t = vd; t.data = nullptr; t.axis_ab = nullptr; t.axis_z = nullptr; volume_layout(replica_voxel_type(vt, k), vd.nx, vd.ny, vd.nz, t); return t; };
+    // false: the type has no such replica (nothing is planned from a VolumeDesc that volume_layout did not fill)
+    auto plan = [&](int k, VolumeDesc& t) { t = vd; t.data = nullptr; t.axis_ab = nullptr; t.axis_z = nullptr; return volume_layout(replica_voxel_type(vt, k), vd.nx, vd.ny, vd.nz, t); };
     if (r->layouts.current != 0 && replica_voxel_type(vt, LAYOUT_THIN) >= 0) {
-      const VolumeDesc t1 = plan(LAYOUT_THIN), t2 = plan(LAYOUT_THIN_T);
-      if (layout_offsets_fit(t1) && layout_offsets_fit(t2) && (r->layouts.current == 2 || (double)(t1.bytes + t2.bytes) <= 0.4 * (double)free_b)) {
+      VolumeDesc t1, t2;
+      if (plan(LAYOUT_THIN, t1) && plan(LAYOUT_THIN_T, t2) && layout_offsets_fit(t1) && layout_offsets_fit(t2) && (r->layouts.current == 2 || (double)(t1.bytes + t2.bytes) <= 0.4 * (double)free_b)) {
         r->vd_replica[LAYOUT_THIN] = t1; r->vd_replica[LAYOUT_THIN_T] = t2;
         r->replica_state[LAYOUT_THIN] = r->replica_state[LAYOUT_THIN_T] = 1;
         planned += (double)(t1.bytes + t2.bytes);
@@ -359,8 +360,8 @@ static int plan_replicas(ovr_hip_renderer* r, int vt, const VolumeDesc& vd)
     }
     static const bool want_quad = !(getenv("OVR_HIP_QUAD") && atoi(getenv("OVR_HIP_QUAD")) == 0);
     if (want_quad && r->layouts.current != 0 && replica_voxel_type(vt, LAYOUT_QUAD) >= 0) {
-      const VolumeDesc tq = plan(LAYOUT_QUAD);
-      if (layout_offsets_fit(tq) && (r->layouts.current == 2 || (double)tq.bytes + planned <= 0.4 * (double)free_b)) {
+      VolumeDesc tq;
+      if (plan(LAYOUT_QUAD, tq) && layout_offsets_fit(tq) && (r->layouts.current == 2 || (double)tq.bytes + planned <= 0.4 * (double)free_b)) {
         r->vd_replica[LAYOUT_QUAD] = tq;
         r->replica_state[LAYOUT_QUAD] = 1;
       }
@@ -442,7 +443,7 @@ static int set_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, i
 
   hipStream_t st = r->own_stream[0];
   VolumeDesc vd{};
-  volume_layout(vt, dims[0], dims[1], dims[2], vd);
+  if (!volume_layout(vt, dims[0], dims[1], dims[2], vd)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_volume: no layout for this voxel type");
   vd.value_scale = 1.f;
   vd.value_min_clamp = -FLT_MAX;
   if (vt == VOX_U8) vd.value_scale = 1.f / 255.f;
@@ -719,7 +720,7 @@ int ovr_hip_query_addressing_mode(const int32_t dims[3], int value_type, int32_t
   const int rt = replica_voxel_type(vt, layout);
   if (layout < 0 || layout >= kLayouts || rt < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_query_addressing_mode: the type has no such layout");
   VolumeDesc vd{};
-  volume_layout(rt, dims[0], dims[1], dims[2], vd);
+  if (!volume_layout(rt, dims[0], dims[1], dims[2], vd)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_query_addressing_mode: the type has no such layout");
   if (!layout_offsets_fit(vd)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_query_addressing_mode: one z layer of this layout exceeds 2^32 elements - it is not built");
   return volume_addressing_mode(vd, n_colors, n_alphas);
 }

@@ -1,6 +1,6 @@
 // ovr_hip_device.h - device code of the ray-march path that depends on the voxel type: helpers, the bricked voxel access,
 // raymarch_kernel / shade_pool_kernel and their launch dispatch.  Included by ovr_hip_kernels.hip (type-independent kernels
-// and the launch interface) and by ovr_hip_march_<type>.hip (one explicit instantiation of launch_v per voxel type).
+// and the launch interface) and by ovr_hip_march.hip (one explicit instantiation of launch_v, compiled once per voxel type).
 // See ovr_hip_kernels.hip for the overview.
 #pragma once
 #include "ovr_hip_kernels.h"
@@ -1995,41 +1995,39 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
   if (!p.sparse_xy && p.n_schedule > 0 && !p.schedule) return hipErrorInvalidValue;
   const dim3 grid = raymarch_grid(p), block(kBlock);
   hipError_t e;
+  // a march variant's launch: its LDS limit, then the kernel unless no block of this renderer's has a hit
+  auto march = [&](auto kern, size_t lds_bytes, const RayMarchParams& prm) -> hipError_t {
+    if (hipError_t err = set_lds(kern, lds_bytes)) return err;
+    if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, prm);
+    return hipSuccess;
+  };
   const bool pooled = (SHADE != 0) && p.pool.reqs != nullptr;
   if (!pooled) {
     const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM) + (size_t)kWaves * QCfg<SHADE, false>::QCAP * sizeof(ShadeReq), (size_t)kWaves * kNC * sizeof(unsigned int)); // the counter reduction reuses it
     bool launched = false;
     if constexpr (VT == VOX_F32 && SHADE == 0 && AM <= 1 && !SKIP) {
-      if (p.lds_staging && !p.sparse_xy && !p.clip_on) { // LDS-staged bricks (see raymarch_kernel): the bricks follow the tables and the TF
+      if (lds_staging_applies(p)) { // LDS-staged bricks (see raymarch_kernel): the bricks follow the tables and the TF
         RayMarchParams q = p;
         q.lds_brick_offset = (unsigned int)((lds + 15) & ~(size_t)15);
         const size_t lds2 = q.lds_brick_offset + (size_t)kLdsBrickCap * 128 + sizeof(LdsRegion) + 12 * sizeof(float) + 2 * sizeof(int) + 16;
-        auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, true>;
-        if ((e = set_lds(kern, lds2)) != hipSuccess) return e;
-        if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds2, stream, q);
+        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, true>, lds2, q)) != hipSuccess) return e;
         launched = true;
       }
     }
     if (!launched) {
       bool with_material = false;
       if (p.clip_on) { // a committed clip box (box_test): the clipped instantiation - where the march shades, of the material variant
-        auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, SHADE != 0, true>;
-        if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-        if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, SHADE != 0, true>, lds, p)) != hipSuccess) return e;
         with_material = true;
       }
       else if constexpr (SHADE != 0) {
         if (!reference_material(p)) { // a material or intensity of the caller's (shade_light)
-          auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, true>;
-          if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-          if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+          if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, true>, lds, p)) != hipSuccess) return e;
           with_material = true;
         }
       }
       if (!with_material) {
-        auto kern = raymarch_kernel<VT, SHADE, AM, false, SKIP>;
-        if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-        if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, p);
+        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP>, lds, p)) != hipSuccess) return e;
       }
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -2061,16 +2059,12 @@ inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const
         bool launched = false;
         if constexpr (!SKIP && (AM <= 1 || AM == 4)) {
           if (use_deep_rounds(p) && !p.clip_on) { // (a clipped frame takes the plain rounds: the same frame, and no third set of pooled kernels) a small image shard: the longest ray's chain of rounds is the floor - deeper rounds
-            auto kern = raymarch_kernel<VT, SH, AM, true, SKIP, false, true>;
-            if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-            if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, q);
+            if ((e = march(raymarch_kernel<VT, SH, AM, true, SKIP, false, true>, lds, q)) != hipSuccess) return e;
             launched = true;
           }
         }
         if (!launched) {
-          auto kern = p.clip_on ? raymarch_kernel<VT, SH, AM, true, SKIP, false, false, false, true> : raymarch_kernel<VT, SH, AM, true, SKIP>;
-          if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-          if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds, stream, q);
+          if ((e = march(p.clip_on ? raymarch_kernel<VT, SH, AM, true, SKIP, false, false, false, true> : raymarch_kernel<VT, SH, AM, true, SKIP>, lds, q)) != hipSuccess) return e;
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
       }
@@ -2105,14 +2099,21 @@ inline hipError_t launch_vsb(const RayMarchParams& p, hipStream_t stream, const 
   return launch_vsbs<VT, SHADE, AM, false>(p, stream, ev);
 }
 
+// the addressing mode (below) of this launch
+inline int march_addressing_mode(const RayMarchParams& p)
+{
+  int am = addressing_mode(p.vol, p.n_color, p.n_alpha);
+  if (const char* f = getenv("OVR_HIP_ADDRESSING")) am = std::max(am, atoi(f)); // diagnostic: a more general mode than needed (tests)
+  return am;
+}
+
 template <int VT, int SHADE>
 inline hipError_t launch_vs(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
 {
   // addressing mode: 0 = 32-bit byte offsets (volume <= 4 GiB; largest byte offset = bytes - sizeof(voxel)),
   //                  1 = 32-bit element offsets (< 2^32 stored voxels), 2 = 64-bit z table in LDS,
   //                  3 = 64-bit, computed (axis tables would not fit in LDS next to the queues: a dimension beyond ~8000)
-  int am = addressing_mode(p.vol, p.n_color, p.n_alpha);
-  if (const char* f = getenv("OVR_HIP_ADDRESSING")) am = std::max(am, atoi(f)); // diagnostic: a more general mode than needed (tests)
+  const int am = march_addressing_mode(p);
   if (am < 3 && (!p.vol.axis_ab || !p.vol.axis_z)) return hipErrorInvalidValue; // the layout's offset tables (launch_axis_tables)
   if constexpr (sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad) {
     // mode 4 = mode 0 with the 16-bit pairs read as aligned 8-byte rows (RowLoads): layouts the caches do not serve; OVR_HIP_ROW_LOADS=0|1, read when a renderer is created, forces (tests, measurements)
@@ -2127,8 +2128,8 @@ inline hipError_t launch_vs(const RayMarchParams& p, hipStream_t stream, const h
   }
 }
 
-// one explicit instantiation per voxel type, each in its own translation unit (ovr_hip_march_*.hip): the ~60 kernel variants of
-// a type compile in parallel with the other types
+// one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~60 kernel
+// variants of a type compile in parallel with the other types
 template <int VT>
 hipError_t launch_v(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
 {

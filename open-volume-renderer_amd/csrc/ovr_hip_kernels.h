@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace ovrhip {
 
@@ -14,6 +15,56 @@ enum VoxelType : int { VOX_U8 = 0, VOX_I8 = 1, VOX_U16 = 2, VOX_I16 = 3, VOX_F32
                        VOX_U16_Q = 10, VOX_U8_Q = 11 };
 enum VolumeLayout : int { LAYOUT_GENERAL = 0, LAYOUT_THIN = 1, LAYOUT_THIN_T = 2, LAYOUT_QUAD = 3 };
 constexpr int kLayouts = 4;
+// THE list of the device voxel types: enumerator, short name (its march unit's object file, see the Makefile), base type, layout.  Everything that exists
+// once per type is generated from it or dispatched through dispatch_voxel_type; Vox<> (ovr_hip_device.h) holds a type's brick geometry.
+#define OVR_VOXEL_TYPES(X) \
+  X(VOX_U8, u8, VOX_U8, LAYOUT_GENERAL) \
+  X(VOX_I8, i8, VOX_I8, LAYOUT_GENERAL) \
+  X(VOX_U16, u16, VOX_U16, LAYOUT_GENERAL) \
+  X(VOX_I16, i16, VOX_I16, LAYOUT_GENERAL) \
+  X(VOX_F32, f32, VOX_F32, LAYOUT_GENERAL) \
+  X(VOX_F32_T, f32t, VOX_F32, LAYOUT_THIN) \
+  X(VOX_F32_TT, f32tt, VOX_F32, LAYOUT_THIN_T) \
+  X(VOX_U16_T, u16t, VOX_U16, LAYOUT_THIN) \
+  X(VOX_U16_TT, u16tt, VOX_U16, LAYOUT_THIN_T) \
+  X(VOX_F32_Q, f32q, VOX_F32, LAYOUT_QUAD) \
+  X(VOX_U16_Q, u16q, VOX_U16, LAYOUT_QUAD) \
+  X(VOX_U8_Q, u8q, VOX_U8, LAYOUT_QUAD)
+struct VoxelTypeInfo { int type; const char* name; int base; int layout; };
+#define OVR_X(E, NAME, BASE, LAYOUT) { E, #NAME, BASE, LAYOUT },
+constexpr VoxelTypeInfo kVoxelTypes[] = { OVR_VOXEL_TYPES(OVR_X) };
+#undef OVR_X
+constexpr int kVoxelTypeCount = (int)(sizeof(kVoxelTypes) / sizeof(kVoxelTypes[0]));
+constexpr bool voxel_types_match_enum()
+{
+  for (int i = 0; i < kVoxelTypeCount; ++i)
+    if (kVoxelTypes[i].type != i || kVoxelTypes[kVoxelTypes[i].base].layout != LAYOUT_GENERAL) return false;
+  return true;
+}
+static_assert(kVoxelTypeCount == 12 && VOX_U8_Q == 11 && voxel_types_match_enum(), "the list restates the VoxelType enum: entry i is the type of value i");
+// a runtime voxel type as a compile-time one: f(std::integral_constant<int, VT>{}); false - and f not called - for a value that is no VoxelType.
+// GENERAL_ONLY: nor for a replica type, and f is not instantiated for one (what exists for the five general types alone)
+template <bool GENERAL_ONLY = false, typename F>
+inline bool dispatch_voxel_type(int voxel_type, F&& f)
+{
+  switch (voxel_type) {
+#define OVR_X(E, NAME, BASE, LAYOUT) \
+  case E: \
+    if constexpr (!GENERAL_ONLY || LAYOUT == LAYOUT_GENERAL) { f(std::integral_constant<int, E>{}); return true; } \
+    else return false;
+    OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+  default: return false;
+  }
+}
+template <typename F> inline bool dispatch_general_voxel_type(int voxel_type, F&& f) { return dispatch_voxel_type<true>(voxel_type, f); }
+// the VoxelType of a layout of a (general) base type, -1 if that replica does not exist
+constexpr int replica_voxel_type(int base_voxel_type, int layout)
+{
+  for (const VoxelTypeInfo& t : kVoxelTypes)
+    if (t.base == base_voxel_type && t.layout == layout) return t.type;
+  return -1;
+}
 constexpr int kBlockCounters = 8; // per-workgroup partial counters of the march (rays, samples, shaded, shadow, active pixels, skipped, skipped shadow, hits through an ignored slab)
 
 // Volume layout in HBM ("x-apron bricks in macro blocks"):
@@ -204,6 +255,10 @@ struct RayMarchParams {
 hipError_t launch_raymarch(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev);
 size_t pool_shade_blocks();
 
+// The unshaded, non-skipping f32 march at addressing mode <= 1 has an LDS-staged variant (raymarch_kernel<.., LDSB>); this is the runtime part of
+// "the launch takes it" (launch_vsbs), and raymarch_lds_staged(p) the whole condition: what launch_raymarch(p) does
+inline bool lds_staging_applies(const RayMarchParams& p) { return p.lds_staging && !p.sparse_xy && !p.clip_on; }
+bool raymarch_lds_staged(const RayMarchParams& p);
 // dynamic LDS bytes the ray-march kernel needs for this TF (0 when the TF stays in global memory)
 size_t raymarch_lds_bytes(int n_color, int n_alpha);
 // addressing mode the march / shade kernels take for a layout (0 / 1: 32-bit offsets, 2: 64-bit z table, 3: computed, no LDS tables)
@@ -291,18 +346,23 @@ hipError_t launch_recon_scatter(const ReconParams& c, float* count, float* grad_
 hipError_t launch_reconstruct(const ReconParams& c, hipStream_t stream);
 int recon_launch_count(const ReconParams& c); // kernels launch_reconstruct enqueues
 
-// linear (x fastest) -> bricked layout; src may be any reference ValueType, dst is laid out as vd.type says (the VoxelType
-// chosen by device_voxel_type() or one of its replicas).  z0/nz_chunk allow chunked uploads from host staging.
+// linear (x fastest) -> bricked GENERAL layout; src may be any reference ValueType, vd.type is the VoxelType device_voxel_type() chooses
+// for it (hipErrorInvalidValue otherwise: the replicas are built from the general layout, launch_rebrick).  z0/nz_chunk allow chunked uploads from host staging.
 int device_voxel_type(int ovr_value_type);
-int replica_voxel_type(int base_voxel_type, int layout); // the VoxelType of a layout of a base type, -1 if that replica does not exist
-void volume_layout(int voxel_type, int nx, int ny, int nz, VolumeDesc& vd); // fills type, nx.., macros_*, macro_elems, bytes
-size_t voxel_size(int voxel_type);
+bool volume_layout(int voxel_type, int nx, int ny, int nz, VolumeDesc& vd); // fills type, nx.., macros_*, macro_elems, bytes; false - and vd untouched - for a value that is no VoxelType
+size_t voxel_size(int voxel_type); // bytes of a stored voxel (4 for a value that is no VoxelType, as ever: addressing_mode divides by it)
 // The taps add the in-plane offsets X(a) + Y(b) of a layout in 32 bits (the 64-bit addressing modes widen only the z term): one z layer of
 // macro blocks must hold fewer than 2^32 elements.  False for a slab-shaped volume of ~8192 x 8192 voxels in the quad layout (131072 elements
 // per macro block), ~16384 x 16384 in the others: such a layout is not built (replicas) or refused (the general layout).
 inline bool layout_offsets_fit(const VolumeDesc& vd)
 {
   return (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y <= 0x100000000ull;
+}
+// the two macro strides of a layout in elements: from a macro block to its +b neighbour's row of macro blocks, and to the next z layer of macro blocks
+__host__ __device__ inline unsigned int macro_stride_y(const VolumeDesc& vd) { return vd.macro_elems * (unsigned int)vd.macros_x; }
+__host__ __device__ inline unsigned long long macro_stride_z(const VolumeDesc& vd)
+{
+  return (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y;
 }
 // slices [z0, z0 + nz_chunk) of the caller's linear array into the layout vd describes.  The launches for all slices together write EVERY element
 // of the allocation (padding rows, cells and layers as zeros - never sampled, but they have to be finite -, by the launch of the last slices), so

@@ -956,18 +956,14 @@ hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, co
   return hipGetLastError();
 }
 
-extern template hipError_t launch_v<VOX_U8>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_I8>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_U16>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_I16>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_F32>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_F32_T>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_F32_TT>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_U16_T>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_U16_TT>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_F32_Q>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_U16_Q>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
-extern template hipError_t launch_v<VOX_U8_Q>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template hipError_t launch_v<E>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
+OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+
+bool raymarch_lds_staged(const RayMarchParams& p)
+{
+  return p.vol.type == VOX_F32 && p.shading == 0 && !p.majorant && march_addressing_mode(p) <= 1 && lds_staging_applies(p); // launch_vsbs
+}
 
 size_t pool_shade_blocks() { return kShadeBlocks; }
 
@@ -975,22 +971,8 @@ hipError_t launch_raymarch(const RayMarchParams& p, hipStream_t stream, const hi
 {
   // ev (optional): ev[0] before the first kernel, ev[1] after the march, ev[2] after the shade kernel (both may be null: no per-phase times), ev[3] at the end
   if (ev) (void)hipEventRecord(ev[0], stream);
-  hipError_t e;
-  switch (p.vol.type) {
-  case VOX_U8: e = launch_v<VOX_U8>(p, stream, ev); break;
-  case VOX_I8: e = launch_v<VOX_I8>(p, stream, ev); break;
-  case VOX_U16: e = launch_v<VOX_U16>(p, stream, ev); break;
-  case VOX_I16: e = launch_v<VOX_I16>(p, stream, ev); break;
-  case VOX_F32: e = launch_v<VOX_F32>(p, stream, ev); break;
-  case VOX_F32_T: e = launch_v<VOX_F32_T>(p, stream, ev); break;
-  case VOX_F32_TT: e = launch_v<VOX_F32_TT>(p, stream, ev); break;
-  case VOX_U16_T: e = launch_v<VOX_U16_T>(p, stream, ev); break;
-  case VOX_U16_TT: e = launch_v<VOX_U16_TT>(p, stream, ev); break;
-  case VOX_F32_Q: e = launch_v<VOX_F32_Q>(p, stream, ev); break;
-  case VOX_U16_Q: e = launch_v<VOX_U16_Q>(p, stream, ev); break;
-  case VOX_U8_Q: e = launch_v<VOX_U8_Q>(p, stream, ev); break;
-  default: e = hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue;
+  dispatch_voxel_type(p.vol.type, [&](auto vt) { e = launch_v<decltype(vt)::value>(p, stream, ev); });
   if (ev) (void)hipEventRecord(ev[3], stream);
   return e;
 }
@@ -998,32 +980,35 @@ hipError_t launch_raymarch(const RayMarchParams& p, hipStream_t stream, const hi
 // ------------------------------------------------------------------------------------------------------------------
 // volume relayout: linear (x fastest) -> 128-byte x-apron bricks in macro blocks
 // ------------------------------------------------------------------------------------------------------------------
+// the reference's ValueType -> (input scalar TI, stored scalar TO, general VoxelType VT): u32 / i32 -> normalized f32, f64 -> f32 at upload.
+// f(ValueTypeOf<..>{}); false - and f not called - for an unknown ValueType
+template <typename TI_, int VT_> struct ValueTypeOf { typedef TI_ TI; typedef typename Vox<VT_>::T TO; static constexpr int VT = VT_; };
+template <typename F>
+static bool dispatch_value_type(int ovr_value_type, F&& f)
+{
+  switch (ovr_value_type) {
+  case 100: f(ValueTypeOf<unsigned char, VOX_U8>{}); return true;
+  case 101: f(ValueTypeOf<signed char, VOX_I8>{}); return true;
+  case 200: f(ValueTypeOf<unsigned short, VOX_U16>{}); return true;
+  case 201: f(ValueTypeOf<short, VOX_I16>{}); return true;
+  case 300: f(ValueTypeOf<unsigned int, VOX_F32>{}); return true;
+  case 301: f(ValueTypeOf<int, VOX_F32>{}); return true;
+  case 400: f(ValueTypeOf<float, VOX_F32>{}); return true;
+  case 500: f(ValueTypeOf<double, VOX_F32>{}); return true;
+  default: return false;
+  }
+}
 int device_voxel_type(int t)
 {
-  switch (t) {
-  case 100: return VOX_U8;
-  case 101: return VOX_I8;
-  case 200: return VOX_U16;
-  case 201: return VOX_I16;
-  case 300: case 301: case 400: case 500: return VOX_F32; // u32 / i32 -> normalized f32, f64 -> f32 at upload
-  default: return -1;
-  }
+  int vt = -1;
+  dispatch_value_type(t, [&](auto v) { vt = decltype(v)::VT; });
+  return vt;
 }
 size_t voxel_size(int vt)
 {
-  switch (vt) {
-  case VOX_U8: case VOX_I8: case VOX_U8_Q: return 1;
-  case VOX_U16: case VOX_I16: case VOX_U16_T: case VOX_U16_TT: case VOX_U16_Q: return 2;
-  default: return 4;
-  }
-}
-int replica_voxel_type(int base, int layout)
-{
-  if (layout == LAYOUT_GENERAL) return base;
-  if (base == VOX_F32) return layout == LAYOUT_THIN ? VOX_F32_T : layout == LAYOUT_THIN_T ? VOX_F32_TT : layout == LAYOUT_QUAD ? VOX_F32_Q : -1;
-  if (base == VOX_U16) return layout == LAYOUT_THIN ? VOX_U16_T : layout == LAYOUT_THIN_T ? VOX_U16_TT : layout == LAYOUT_QUAD ? VOX_U16_Q : -1;
-  if (base == VOX_U8) return layout == LAYOUT_QUAD ? VOX_U8_Q : -1;
-  return -1;
+  size_t bytes = 4;
+  dispatch_voxel_type(vt, [&](auto t) { bytes = sizeof(typename Vox<decltype(t)::value>::T); });
+  return bytes;
 }
 
 template <typename TI, typename TO> struct Conv { static __device__ __forceinline__ TO cv(TI v) { return (TO)v; } };
@@ -1053,6 +1038,10 @@ template <int VTB> struct SrcBricked {
     return p[(unsigned long long)(M::X((unsigned)x + 1u) + M::Y((unsigned)y, macro_y)) + M::Zlo(z) + (unsigned long long)(z >> 5) * macro_z];
   }
 };
+template <int VTB> static SrcBricked<VTB> src_bricked(const VolumeDesc& general)
+{
+  return SrcBricked<VTB>{ (const typename Vox<VTB>::T*)general.data, macro_stride_y(general), macro_stride_z(general) };
+}
 
 // One thread per brick ROW (the SX stored voxels of one (y, z) line of a brick: 8 or 16 bytes), rows taken in the order the layout stores them:
 // a workgroup owns the 32 y x 2^bz z slab of one macro row and sweeps it along the pair axis, macro block by macro block - inside a macro block
@@ -1063,32 +1052,60 @@ template <int VTB> struct SrcBricked {
 template <typename TI, int N> struct __attribute__((packed, aligned(sizeof(TI)))) RowIn { TI v[N]; };
 template <typename TO, int N> struct alignas(sizeof(TO) * N) RowOut { TO v[N]; };
 
+// The addressing of that sweep, shared by relayout_kernel and its box-restricted sibling update_rows_kernel (an update has to reproduce a fresh
+// upload bit for bit).  layout axes (a, b, z): a = pair axis = x (y in a transposed replica), b = the other one.
+// (The clamped gather of a row stays written out in both kernels: as a function the compiler simplifies it before it is inlined, without the
+// caller's v0, and every kernel's instructions change - profiles/r11_voxel_types.md.)
+template <int VT> struct RowSweep {
+  typedef BrickMap<VT> M;
+  typedef Vox<VT> V;
+  static constexpr unsigned SX = M::SX, RB = 1u << (V::by + V::bz);   // stored voxels per row, rows per brick
+  static constexpr unsigned ROWS = M::sbz / SX;                        // rows of the slab inside one macro block
+  static constexpr unsigned LZ = 32u >> V::bz;                         // z layers per macro block
+  static_assert(ROWS * SX == M::sbz && ROWS == (32u >> V::by) * V::mbx * RB, "the slab is the layout's z-layer stride");
+  // element offset of the slab of (macro row my, z layer)
+  static __device__ __forceinline__ unsigned long long slab(unsigned my, unsigned layer, unsigned int macro_y, unsigned long long macro_z)
+  {
+    return (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * M::sbz + (unsigned long long)(layer / LZ) * macro_z;
+  }
+  // sweep index g (of a sweep that starts at macro block macro_lo) -> macro block along a, row in the slab, the row's b and z, its brick along a
+  // (the row's stored positions br * cx ... br * cx + SX - 1 = voxels br * cx - 1 ...: clamp addressing is baked into the data, position 0 is a
+  // copy of voxel 0, positions beyond the grid replicate the last voxel)
+  struct Row { unsigned mx, i, b, z, br; };
+  static __device__ __forceinline__ Row decode(unsigned g, unsigned macro_lo, unsigned my, unsigned layer)
+  {
+    const unsigned ml = g / ROWS, i = g - ml * ROWS, mx = macro_lo + ml;
+    const unsigned rr = i & (RB - 1u), bi = i / RB;
+    const unsigned ybk = bi / V::mbx, bm = bi - ybk * V::mbx;
+    const unsigned b = my * 32u + (ybk << V::by) + (rr & ((1u << V::by) - 1u));
+    const unsigned z = (layer << V::bz) + (rr >> V::by);
+    return Row{ mx, i, b, z, mx * V::mbx + bm };
+  }
+  template <typename TO> static __device__ __forceinline__ RowOut<TO, SX>* row(TO* dst, unsigned long long slab_offset, const Row& r)
+  {
+    return reinterpret_cast<RowOut<TO, SX>*>(dst + slab_offset + (unsigned long long)r.mx * M::MV) + r.i;
+  }
+};
+
 template <typename SRC, typename TO, int VT>
 __global__ __launch_bounds__(256) void relayout_kernel(const SRC src, TO* __restrict__ dst, int nx, int ny, int macros_a, unsigned int macro_y,
                                                       unsigned long long macro_z, int z0, int nz_chunk, int nz)
 {
   typedef typename SRC::value_type TI;
-  // layout axes (a, b, z): a = pair axis = x (y in a transposed replica), b = the other one
   // grid: x = macro rows along b, y = z layers (2^bz slices each) that meet [z0, z0 + nz_chunk) - and, in the launch of the volume's last
   // slices, the padding layers up to the end of the allocation ; src holds slices [z0, z0 + nz_chunk)
-  typedef BrickMap<VT> M;
+  typedef RowSweep<VT> S;
   typedef Vox<VT> V;
   constexpr bool TR = V::kTransposed;
-  constexpr unsigned SX = M::SX, RB = 1u << (V::by + V::bz);   // stored voxels per row, rows per brick
-  constexpr unsigned ROWS = M::sbz / SX;                        // rows of the slab inside one macro block
-  constexpr unsigned LZ = 32u >> V::bz;                         // z layers per macro block
-  static_assert(ROWS * SX == M::sbz && ROWS == (32u >> V::by) * V::mbx * RB, "the slab is the layout's z-layer stride");
+  constexpr unsigned SX = S::SX;
   const int na = TR ? ny : nx, nb = TR ? nx : ny;
   const unsigned my = blockIdx.x, layer = ((unsigned)z0 >> V::bz) + blockIdx.y;
-  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * M::sbz + (unsigned long long)(layer / LZ) * macro_z;
-  const unsigned total = (unsigned)macros_a * ROWS;
+  const unsigned long long slab = S::slab(my, layer, macro_y, macro_z);
+  const unsigned total = (unsigned)macros_a * S::ROWS;
   for (unsigned g = threadIdx.x; g < total; g += 256u) {
-    const unsigned mx = g / ROWS, i = g - mx * ROWS;
-    const unsigned rr = i & (RB - 1u), bi = i / RB;
-    const unsigned ybk = bi / V::mbx, bm = bi - ybk * V::mbx;
-    const unsigned b = my * 32u + (ybk << V::by) + (rr & ((1u << V::by) - 1u));
-    const unsigned z = (layer << V::bz) + (rr >> V::by);
-    RowOut<TO, SX>* const row = reinterpret_cast<RowOut<TO, SX>*>(dst + slab + (unsigned long long)mx * M::MV + (unsigned long long)i * SX);
+    const typename S::Row r = S::decode(g, 0u, my, layer);
+    const unsigned b = r.b, z = r.z;
+    RowOut<TO, SX>* const row = S::row(dst, slab, r);
     if (b >= (unsigned)nb || z >= (unsigned)nz) { // a padding row: never sampled, but finite (the allocation needs no memset)
       if (z >= (unsigned)z0) {                    // ... written once: by the launch whose slices the row's layer belongs to (or the last one)
         RowOut<TO, SX> zero;
@@ -1099,9 +1116,7 @@ __global__ __launch_bounds__(256) void relayout_kernel(const SRC src, TO* __rest
       continue;
     }
     if (z < (unsigned)z0 || z >= (unsigned)(z0 + nz_chunk)) continue; // another launch's slices
-    // the row's stored positions a0 ... a0 + SX - 1 = voxels a0 - 1 ... (clamp addressing baked into the data: position 0 is a copy of voxel 0,
-    // positions beyond the grid replicate the last voxel)
-    const int v0 = (int)((mx * V::mbx + bm) * V::cx) - 1;
+    const int v0 = (int)(r.br * V::cx) - 1;
     TI in[SX];
     bool done = false;
     if constexpr (SRC::kLinear && !TR) {
@@ -1130,27 +1145,40 @@ __global__ __launch_bounds__(256) void relayout_kernel(const SRC src, TO* __rest
 // grid replaced by the last voxel (clamp-to-edge addressing).  Cells in storage order, like relayout_kernel's rows: a workgroup owns the
 // 32 cells (y) x 2^lz slices slab of one macro row - inside a macro block one contiguous 32 KiB piece - and sweeps it along x, so every
 // 128-byte line is written whole (the thread-per-cell-along-x form of round 3 built C3's 17 GB replica in 40 ms), padding cells as zeros.
+// (the constants and the slab offset of that sweep, shared with the box-restricted sibling update_quad_kernel; the decode of the sweep index, the cell
+// pointer and the cell's gather are written out in both: shared as RowSweep's are, they changed the kernels' instructions - profiles/r11_voxel_types.md)
+template <int VT> struct QuadSweep {
+  typedef BrickMap<VT> M;
+  typedef Vox<VT> V;
+  typedef typename V::T TO;
+  typedef typename V::Q Q;
+  static constexpr unsigned CB = 1u << (V::lx + V::ly + V::lz);          // cells per brick
+  static constexpr unsigned LAYER = M::bx_ * M::by_ * M::BV;             // elements of one z layer (2^lz slices) of a macro block
+  static constexpr unsigned CELLS = M::bx_ * M::by_ * CB;                // ... and its cells
+  static constexpr unsigned LZ = 32u >> V::lz;
+  static_assert(CB * 4u == M::BV && CELLS * 4u == LAYER, "a brick is CB cells of 4 elements");
+  static __device__ __forceinline__ unsigned long long slab(unsigned my, unsigned layer, unsigned int macro_y, unsigned long long macro_z)
+  {
+    return (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * LAYER + (unsigned long long)(layer / LZ) * macro_z;
+  }
+};
 template <typename SRC, int VT>
 __global__ __launch_bounds__(256) void relayout_quad_kernel(const SRC src, typename Vox<VT>::T* __restrict__ dst, int nx, int ny, int macros_x, unsigned int macro_y,
                                                            unsigned long long macro_z, int z0, int nz_chunk, int nz)
 {
   typedef typename SRC::value_type TI;
+  typedef QuadSweep<VT> S;
   typedef BrickMap<VT> M;
   typedef Vox<VT> V;
   typedef typename V::T TO;
   typedef typename V::Q Q;
-  constexpr unsigned CB = 1u << (V::lx + V::ly + V::lz);          // cells per brick
-  constexpr unsigned LAYER = M::bx_ * M::by_ * M::BV;             // elements of one z layer (2^lz slices) of a macro block
-  constexpr unsigned CELLS = M::bx_ * M::by_ * CB;                // ... and its cells
-  constexpr unsigned LZ = 32u >> V::lz;
-  static_assert(CB * 4u == M::BV && CELLS * 4u == LAYER, "a brick is CB cells of 4 elements");
   // grid: x = macro rows along y, y = z layers that meet [z0, z0 + nz_chunk) (+ the padding layers, in the launch of the last slices)
   const unsigned my = blockIdx.x, layer = ((unsigned)z0 >> V::lz) + blockIdx.y;
-  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * LAYER + (unsigned long long)(layer / LZ) * macro_z;
-  const unsigned total = (unsigned)macros_x * CELLS;
+  const unsigned long long slab = S::slab(my, layer, macro_y, macro_z);
+  const unsigned total = (unsigned)macros_x * S::CELLS;
   for (unsigned g = threadIdx.x; g < total; g += 256u) {
-    const unsigned mx = g / CELLS, i = g - mx * CELLS;
-    const unsigned j = i & (CB - 1u), brick = i / CB;
+    const unsigned mx = g / S::CELLS, i = g - mx * S::CELLS;
+    const unsigned j = i & (S::CB - 1u), brick = i / S::CB;
     // cell (u, v) = (x + 1, y + 1), x in [-1, nx - 1], y in [-1, ny - 1]
     const int u = (int)(mx * 32u + ((brick & (M::bx_ - 1u)) << V::lx) + (j & ((1u << V::lx) - 1u)));
     const int v = (int)(my * 32u + ((brick / M::bx_) << V::ly) + ((j >> V::lx) & ((1u << V::ly) - 1u)));
@@ -1175,14 +1203,9 @@ static hipError_t relayout_quad_s(const SRC& src, void* dst, const VolumeDesc& v
   if (nzc <= 0) return hipSuccess;
   const unsigned last = z0 + nzc >= vd.nz ? (unsigned)vd.macros_z * (32u >> Vox<VT>::lz) - 1u : (unsigned)(z0 + nzc - 1) >> Vox<VT>::lz;
   dim3 grid((unsigned)vd.macros_y, last - ((unsigned)z0 >> Vox<VT>::lz) + 1u);
-  hipLaunchKernelGGL((relayout_quad_kernel<SRC, VT>), grid, dim3(256), 0, stream, src, (typename Vox<VT>::T*)dst, vd.nx, vd.ny, vd.macros_x, vd.macro_elems * (unsigned)vd.macros_x,
-                     (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, z0, nzc, vd.nz);
+  hipLaunchKernelGGL((relayout_quad_kernel<SRC, VT>), grid, dim3(256), 0, stream, src, (typename Vox<VT>::T*)dst, vd.nx, vd.ny, vd.macros_x, macro_stride_y(vd),
+                     macro_stride_z(vd), z0, nzc, vd.nz);
   return hipGetLastError();
-}
-template <typename TI, int VT>
-static hipError_t relayout_quad_t(const void* src, void* dst, const VolumeDesc& vd, int z0, int nzc, hipStream_t stream)
-{
-  return relayout_quad_s<SrcLinear<TI>, VT>(SrcLinear<TI>{ (const TI*)src, vd.nx, vd.ny, z0 }, dst, vd, z0, nzc, stream);
 }
 
 template <typename SRC, typename TO, int VT>
@@ -1193,14 +1216,9 @@ static hipError_t relayout_s(const SRC& src, void* dst, const VolumeDesc& vd, in
   const unsigned last = z0 + nzc >= vd.nz ? (unsigned)vd.macros_z * (32u >> Vox<VT>::bz) - 1u : (unsigned)(z0 + nzc - 1) >> Vox<VT>::bz;
   const unsigned layers = last - ((unsigned)z0 >> Vox<VT>::bz) + 1u;
   dim3 grid((unsigned)vd.macros_y, layers);
-  hipLaunchKernelGGL((relayout_kernel<SRC, TO, VT>), grid, dim3(256), 0, stream, src, (TO*)dst, vd.nx, vd.ny, vd.macros_x,
-                     vd.macro_elems * (unsigned)vd.macros_x, (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, z0, nzc, vd.nz);
+  hipLaunchKernelGGL((relayout_kernel<SRC, TO, VT>), grid, dim3(256), 0, stream, src, (TO*)dst, vd.nx, vd.ny, vd.macros_x, macro_stride_y(vd), macro_stride_z(vd), z0, nzc,
+                     vd.nz);
   return hipGetLastError();
-}
-template <typename TI, typename TO, int VT>
-static hipError_t relayout_t(const void* src, void* dst, const VolumeDesc& vd, int z0, int nzc, hipStream_t stream)
-{
-  return relayout_s<SrcLinear<TI>, TO, VT>(SrcLinear<TI>{ (const TI*)src, vd.nx, vd.ny, z0 }, dst, vd, z0, nzc, stream);
 }
 
 // layout constants the host needs to size the allocation (vd.type, nx, ny, nz and the macro-block geometry of that layout)
@@ -1216,60 +1234,24 @@ static void volume_layout_t(int nx, int ny, int nz, VolumeDesc& vd)
   vd.macro_elems = M::MV;
   vd.bytes = (unsigned long long)vd.macros_x * vd.macros_y * vd.macros_z * M::MV * sizeof(typename Vox<VT>::T);
 }
-void volume_layout(int voxel_type, int nx, int ny, int nz, VolumeDesc& vd)
+bool volume_layout(int voxel_type, int nx, int ny, int nz, VolumeDesc& vd)
 {
-  vd.type = voxel_type;
-  vd.nx = nx; vd.ny = ny; vd.nz = nz;
-  switch (voxel_type) {
-  case VOX_U8: volume_layout_t<VOX_U8>(nx, ny, nz, vd); break;
-  case VOX_I8: volume_layout_t<VOX_I8>(nx, ny, nz, vd); break;
-  case VOX_U16: volume_layout_t<VOX_U16>(nx, ny, nz, vd); break;
-  case VOX_I16: volume_layout_t<VOX_I16>(nx, ny, nz, vd); break;
-  case VOX_F32_T: volume_layout_t<VOX_F32_T>(nx, ny, nz, vd); break;
-  case VOX_F32_TT: volume_layout_t<VOX_F32_TT>(nx, ny, nz, vd); break;
-  case VOX_U16_T: volume_layout_t<VOX_U16_T>(nx, ny, nz, vd); break;
-  case VOX_U16_TT: volume_layout_t<VOX_U16_TT>(nx, ny, nz, vd); break;
-  case VOX_F32_Q: volume_layout_t<VOX_F32_Q>(nx, ny, nz, vd); break;
-  case VOX_U16_Q: volume_layout_t<VOX_U16_Q>(nx, ny, nz, vd); break;
-  case VOX_U8_Q: volume_layout_t<VOX_U8_Q>(nx, ny, nz, vd); break;
-  default: volume_layout_t<VOX_F32>(nx, ny, nz, vd); break;
-  }
-}
-
-template <typename TI>
-static hipError_t relayout_f32(const void* src, void* dst, const VolumeDesc& vd, int z0, int nzc, hipStream_t stream)
-{
-  switch (vd.type) {
-  case VOX_F32: return relayout_t<TI, float, VOX_F32>(src, dst, vd, z0, nzc, stream);
-  case VOX_F32_T: return relayout_t<TI, float, VOX_F32_T>(src, dst, vd, z0, nzc, stream);
-  case VOX_F32_TT: return relayout_t<TI, float, VOX_F32_TT>(src, dst, vd, z0, nzc, stream);
-  case VOX_F32_Q: return relayout_quad_t<TI, VOX_F32_Q>(src, dst, vd, z0, nzc, stream);
-  default: return hipErrorInvalidValue;
-  }
+  return dispatch_voxel_type(voxel_type, [&](auto vt) {
+    vd.type = voxel_type;
+    vd.nx = nx; vd.ny = ny; vd.nz = nz;
+    volume_layout_t<decltype(vt)::value>(nx, ny, nz, vd);
+  });
 }
 
 hipError_t launch_relayout(const void* src, int vt, void* dst, const VolumeDesc& vd, int z0, int nzc, hipStream_t stream)
 {
-  switch (vt) {
-  case 100:
-    if (vd.type == VOX_U8_Q) return relayout_quad_t<unsigned char, VOX_U8_Q>(src, dst, vd, z0, nzc, stream);
-    return relayout_t<unsigned char, unsigned char, VOX_U8>(src, dst, vd, z0, nzc, stream);
-  case 101: return relayout_t<signed char, signed char, VOX_I8>(src, dst, vd, z0, nzc, stream);
-  case 200:
-    switch (vd.type) {
-    case VOX_U16: return relayout_t<unsigned short, unsigned short, VOX_U16>(src, dst, vd, z0, nzc, stream);
-    case VOX_U16_T: return relayout_t<unsigned short, unsigned short, VOX_U16_T>(src, dst, vd, z0, nzc, stream);
-    case VOX_U16_TT: return relayout_t<unsigned short, unsigned short, VOX_U16_TT>(src, dst, vd, z0, nzc, stream);
-    case VOX_U16_Q: return relayout_quad_t<unsigned short, VOX_U16_Q>(src, dst, vd, z0, nzc, stream);
-    default: return hipErrorInvalidValue;
-    }
-  case 201: return relayout_t<short, short, VOX_I16>(src, dst, vd, z0, nzc, stream);
-  case 300: return relayout_f32<unsigned int>(src, dst, vd, z0, nzc, stream);
-  case 301: return relayout_f32<int>(src, dst, vd, z0, nzc, stream);
-  case 400: return relayout_f32<float>(src, dst, vd, z0, nzc, stream);
-  case 500: return relayout_f32<double>(src, dst, vd, z0, nzc, stream);
-  default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue; // an unknown ValueType, or vd is not its general layout
+  dispatch_value_type(vt, [&](auto v) {
+    typedef decltype(v) V;
+    typedef SrcLinear<typename V::TI> Src;
+    if (vd.type == V::VT) e = relayout_s<Src, typename V::TO, V::VT>(Src{ (const typename V::TI*)src, vd.nx, vd.ny, z0 }, dst, vd, z0, nzc, stream);
+  });
+  return e;
 }
 
 // a replica from the resident general layout (the caller's array is gone by then: ovr_hip_set_volume does not keep it)
@@ -1277,27 +1259,19 @@ template <int VTB>
 static hipError_t rebrick_b(const VolumeDesc& g, void* dst, const VolumeDesc& vd, int z0, int nzc, hipStream_t stream)
 {
   typedef typename Vox<VTB>::T T;
-  const SrcBricked<VTB> src{ (const T*)g.data, g.macro_elems * (unsigned)g.macros_x, (unsigned long long)g.macro_elems * (unsigned long long)g.macros_x * (unsigned long long)g.macros_y };
-  constexpr int T1 = VTB == VOX_F32 ? VOX_F32_T : VOX_U16_T, T2 = VTB == VOX_F32 ? VOX_F32_TT : VOX_U16_TT;
-  constexpr int TQ = VTB == VOX_F32 ? VOX_F32_Q : VTB == VOX_U16 ? VOX_U16_Q : VOX_U8_Q;
-  if (vd.type == TQ) return relayout_quad_s<SrcBricked<VTB>, TQ>(src, dst, vd, z0, nzc, stream);
-  if constexpr (VTB != VOX_U8) {
-    if (vd.type == T1) return relayout_s<SrcBricked<VTB>, T, T1>(src, dst, vd, z0, nzc, stream);
-    if (vd.type == T2) return relayout_s<SrcBricked<VTB>, T, T2>(src, dst, vd, z0, nzc, stream);
-  }
+  typedef SrcBricked<VTB> Src;
+  constexpr int T1 = replica_voxel_type(VTB, LAYOUT_THIN), T2 = replica_voxel_type(VTB, LAYOUT_THIN_T), TQ = replica_voxel_type(VTB, LAYOUT_QUAD);
+  if constexpr (TQ >= 0) { if (vd.type == TQ) return relayout_quad_s<Src, TQ>(src_bricked<VTB>(g), dst, vd, z0, nzc, stream); }
+  if constexpr (T1 >= 0) { if (vd.type == T1) return relayout_s<Src, T, T1>(src_bricked<VTB>(g), dst, vd, z0, nzc, stream); }
+  if constexpr (T2 >= 0) { if (vd.type == T2) return relayout_s<Src, T, T2>(src_bricked<VTB>(g), dst, vd, z0, nzc, stream); }
   return hipErrorInvalidValue;
 }
 hipError_t launch_rebrick(const VolumeDesc& general, void* dst, const VolumeDesc& vd, hipStream_t stream)
 {
   for (int z0 = 0; z0 < vd.nz; z0 += 32768) { // grid.z limit
     const int nzc = std::min(32768, vd.nz - z0);
-    hipError_t e;
-    switch (general.type) {
-    case VOX_F32: e = rebrick_b<VOX_F32>(general, dst, vd, z0, nzc, stream); break;
-    case VOX_U16: e = rebrick_b<VOX_U16>(general, dst, vd, z0, nzc, stream); break;
-    case VOX_U8: e = rebrick_b<VOX_U8>(general, dst, vd, z0, nzc, stream); break;
-    default: e = hipErrorInvalidValue;
-    }
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_general_voxel_type(general.type, [&](auto vtb) { e = rebrick_b<decltype(vtb)::value>(general, dst, vd, z0, nzc, stream); });
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
@@ -1325,25 +1299,20 @@ template <typename SRC, typename TO, int VT>
 __global__ __launch_bounds__(256) void update_rows_kernel(const SRC src, TO* __restrict__ dst, int nx, int ny, unsigned int macro_y, unsigned long long macro_z, const UpdateRows u)
 {
   typedef typename SRC::value_type TI;
-  typedef BrickMap<VT> M;
+  typedef RowSweep<VT> S;
   typedef Vox<VT> V;
   constexpr bool TR = V::kTransposed;
-  constexpr unsigned SX = M::SX, RB = 1u << (V::by + V::bz);
-  constexpr unsigned ROWS = M::sbz / SX;
-  constexpr unsigned LZ = 32u >> V::bz;
+  constexpr unsigned SX = S::SX;
   const int na = TR ? ny : nx;
   const unsigned my = (unsigned)u.row_lo + blockIdx.x, layer = (unsigned)u.layer_lo + blockIdx.y;
-  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * M::sbz + (unsigned long long)(layer / LZ) * macro_z;
-  const unsigned total = (unsigned)u.macros * ROWS;
+  const unsigned long long slab = S::slab(my, layer, macro_y, macro_z);
+  const unsigned total = (unsigned)u.macros * S::ROWS;
   for (unsigned g = threadIdx.x; g < total; g += 256u) {
-    const unsigned ml = g / ROWS, i = g - ml * ROWS, mx = (unsigned)u.macro_lo + ml;
-    const unsigned rr = i & (RB - 1u), bi = i / RB;
-    const unsigned ybk = bi / V::mbx, bm = bi - ybk * V::mbx;
-    const int b = (int)(my * 32u + (ybk << V::by) + (rr & ((1u << V::by) - 1u)));
-    const int z = (int)((layer << V::bz) + (rr >> V::by));
-    const int br = (int)(mx * V::mbx + bm);
+    const typename S::Row r = S::decode(g, (unsigned)u.macro_lo, my, layer);
+    const int b = (int)r.b, z = (int)r.z;
+    const int br = (int)r.br;
     if (b < u.blo || b >= u.bhi || z < u.zlo || z >= u.zhi || br < u.brick_lo || br > u.brick_hi) continue;
-    RowOut<TO, SX>* const row = reinterpret_cast<RowOut<TO, SX>*>(dst + slab + (unsigned long long)mx * M::MV + (unsigned long long)i * SX);
+    RowOut<TO, SX>* const row = S::row(dst, slab, r);
     const int v0 = br * V::cx - 1;
     RowOut<TO, SX> out;
     if constexpr (SRC::kBox) {
@@ -1380,20 +1349,17 @@ __global__ __launch_bounds__(256) void update_quad_kernel(const SRC src, typenam
                                                          const UpdateCells c)
 {
   typedef typename SRC::value_type TI;
+  typedef QuadSweep<VT> S;
   typedef BrickMap<VT> M;
   typedef Vox<VT> V;
   typedef typename V::T TO;
   typedef typename V::Q Q;
-  constexpr unsigned CB = 1u << (V::lx + V::ly + V::lz);
-  constexpr unsigned LAYER = M::bx_ * M::by_ * M::BV;
-  constexpr unsigned CELLS = M::bx_ * M::by_ * CB;
-  constexpr unsigned LZ = 32u >> V::lz;
   const unsigned my = (unsigned)c.row_lo + blockIdx.x, layer = (unsigned)c.layer_lo + blockIdx.y;
-  const unsigned long long slab = (unsigned long long)my * macro_y + (unsigned long long)(layer & (LZ - 1u)) * LAYER + (unsigned long long)(layer / LZ) * macro_z;
-  const unsigned total = (unsigned)c.macros * CELLS;
+  const unsigned long long slab = S::slab(my, layer, macro_y, macro_z);
+  const unsigned total = (unsigned)c.macros * S::CELLS;
   for (unsigned g = threadIdx.x; g < total; g += 256u) {
-    const unsigned ml = g / CELLS, i = g - ml * CELLS, mx = (unsigned)c.macro_lo + ml;
-    const unsigned j = i & (CB - 1u), brick = i / CB;
+    const unsigned ml = g / S::CELLS, i = g - ml * S::CELLS, mx = (unsigned)c.macro_lo + ml;
+    const unsigned j = i & (S::CB - 1u), brick = i / S::CB;
     const int u = (int)(mx * 32u + ((brick & (M::bx_ - 1u)) << V::lx) + (j & ((1u << V::lx) - 1u)));
     const int v = (int)(my * 32u + ((brick / M::bx_) << V::ly) + ((j >> V::lx) & ((1u << V::ly) - 1u)));
     const int z = (int)((layer << V::lz) + (j >> (V::lx + V::ly)));
@@ -1426,8 +1392,7 @@ static hipError_t update_rows_s(const SRC& src, void* dst, const VolumeDesc& vd,
   for (int l0 = r.layer_lo; l0 <= r.layer_hi; l0 += kUpdateLayers) {
     const UpdateRows u{ box.lo[ia], box.hi[ia], box.lo[ib], box.hi[ib], box.lo[2], box.hi[2], r.brick_lo, r.brick_hi, r.macro_lo, r.macro_hi - r.macro_lo + 1, r.row_lo, l0 };
     const dim3 grid((unsigned)(r.row_hi - r.row_lo + 1), (unsigned)(std::min(r.layer_hi, l0 + kUpdateLayers - 1) - l0 + 1));
-    hipLaunchKernelGGL((update_rows_kernel<SRC, TO, VT>), grid, dim3(256), 0, stream, src, (TO*)dst, vd.nx, vd.ny, vd.macro_elems * (unsigned)vd.macros_x,
-                       (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, u);
+    hipLaunchKernelGGL((update_rows_kernel<SRC, TO, VT>), grid, dim3(256), 0, stream, src, (TO*)dst, vd.nx, vd.ny, macro_stride_y(vd), macro_stride_z(vd), u);
     if (hipError_t e = hipGetLastError()) return e;
   }
   return hipSuccess;
@@ -1439,55 +1404,38 @@ static hipError_t update_quad_s(const SRC& src, void* dst, const VolumeDesc& vd,
   for (int l0 = r.layer_lo; l0 <= r.layer_hi; l0 += kUpdateLayers) {
     const UpdateCells c{ r.u_lo, r.u_hi, r.v_lo, r.v_hi, box.lo[2], box.hi[2], r.macro_lo, r.macro_hi - r.macro_lo + 1, r.row_lo, l0 };
     const dim3 grid((unsigned)(r.row_hi - r.row_lo + 1), (unsigned)(std::min(r.layer_hi, l0 + kUpdateLayers - 1) - l0 + 1));
-    hipLaunchKernelGGL((update_quad_kernel<SRC, VT>), grid, dim3(256), 0, stream, src, (typename Vox<VT>::T*)dst, vd.nx, vd.ny, vd.macro_elems * (unsigned)vd.macros_x,
-                       (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y, c);
+    hipLaunchKernelGGL((update_quad_kernel<SRC, VT>), grid, dim3(256), 0, stream, src, (typename Vox<VT>::T*)dst, vd.nx, vd.ny, macro_stride_y(vd), macro_stride_z(vd), c);
     if (hipError_t e = hipGetLastError()) return e;
   }
   return hipSuccess;
 }
-template <typename TI, typename TO, int VT>
-static hipError_t update_general_t(const void* src, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
-{
-  if (vd.type != VT) return hipErrorInvalidValue;
-  return update_rows_s<SrcBox<TI>, TO, VT>(SrcBox<TI>{ (const TI*)src, box.lo[0], box.lo[1], box.lo[2], box.hi[0] - box.lo[0], box.hi[1] - box.lo[1] }, dst, vd, box, stream);
-}
 hipError_t launch_update_general(const void* src, int vt, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
 {
-  switch (vt) { // the reference's ValueType, as in launch_relayout: the same Conv per element
-  case 100: return update_general_t<unsigned char, unsigned char, VOX_U8>(src, dst, vd, box, stream);
-  case 101: return update_general_t<signed char, signed char, VOX_I8>(src, dst, vd, box, stream);
-  case 200: return update_general_t<unsigned short, unsigned short, VOX_U16>(src, dst, vd, box, stream);
-  case 201: return update_general_t<short, short, VOX_I16>(src, dst, vd, box, stream);
-  case 300: return update_general_t<unsigned int, float, VOX_F32>(src, dst, vd, box, stream);
-  case 301: return update_general_t<int, float, VOX_F32>(src, dst, vd, box, stream);
-  case 400: return update_general_t<float, float, VOX_F32>(src, dst, vd, box, stream);
-  case 500: return update_general_t<double, float, VOX_F32>(src, dst, vd, box, stream);
-  default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue; // as launch_relayout: the same Conv per element
+  dispatch_value_type(vt, [&](auto v) {
+    typedef decltype(v) V;
+    typedef SrcBox<typename V::TI> Src;
+    if (vd.type == V::VT)
+      e = update_rows_s<Src, typename V::TO, V::VT>(Src{ (const typename V::TI*)src, box.lo[0], box.lo[1], box.lo[2], box.hi[0] - box.lo[0], box.hi[1] - box.lo[1] }, dst, vd, box, stream);
+  });
+  return e;
 }
 template <int VTB>
 static hipError_t update_replica_b(const VolumeDesc& g, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
 {
   typedef typename Vox<VTB>::T T;
   typedef SrcBricked<VTB> Src;
-  const Src src{ (const T*)g.data, g.macro_elems * (unsigned)g.macros_x, (unsigned long long)g.macro_elems * (unsigned long long)g.macros_x * (unsigned long long)g.macros_y };
-  constexpr int T1 = VTB == VOX_F32 ? VOX_F32_T : VOX_U16_T, T2 = VTB == VOX_F32 ? VOX_F32_TT : VOX_U16_TT;
-  constexpr int TQ = VTB == VOX_F32 ? VOX_F32_Q : VTB == VOX_U16 ? VOX_U16_Q : VOX_U8_Q;
-  if (vd.type == TQ) return update_quad_s<Src, TQ>(src, dst, vd, box, stream);
-  if constexpr (VTB != VOX_U8) {
-    if (vd.type == T1) return update_rows_s<Src, T, T1>(src, dst, vd, box, stream);
-    if (vd.type == T2) return update_rows_s<Src, T, T2>(src, dst, vd, box, stream);
-  }
+  constexpr int T1 = replica_voxel_type(VTB, LAYOUT_THIN), T2 = replica_voxel_type(VTB, LAYOUT_THIN_T), TQ = replica_voxel_type(VTB, LAYOUT_QUAD);
+  if constexpr (TQ >= 0) { if (vd.type == TQ) return update_quad_s<Src, TQ>(src_bricked<VTB>(g), dst, vd, box, stream); }
+  if constexpr (T1 >= 0) { if (vd.type == T1) return update_rows_s<Src, T, T1>(src_bricked<VTB>(g), dst, vd, box, stream); }
+  if constexpr (T2 >= 0) { if (vd.type == T2) return update_rows_s<Src, T, T2>(src_bricked<VTB>(g), dst, vd, box, stream); }
   return hipErrorInvalidValue;
 }
 hipError_t launch_update_replica(const VolumeDesc& general, void* dst, const VolumeDesc& vd, const update::Box& box, hipStream_t stream)
 {
-  switch (general.type) {
-  case VOX_F32: return update_replica_b<VOX_F32>(general, dst, vd, box, stream);
-  case VOX_U16: return update_replica_b<VOX_U16>(general, dst, vd, box, stream);
-  case VOX_U8: return update_replica_b<VOX_U8>(general, dst, vd, box, stream);
-  default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue;
+  dispatch_general_voxel_type(general.type, [&](auto vtb) { e = update_replica_b<decltype(vtb)::value>(general, dst, vd, box, stream); });
+  return e;
 }
 
 // per-axis offset tables of a layout (VolumeDesc::axis_ab / axis_z), once per volume
@@ -1496,8 +1444,8 @@ __global__ __launch_bounds__(256) void axis_tables_kernel(VolumeDesc vd, unsigne
 {
   typedef BrickMap<VT> M;
   const int na = Vox<VT>::kTransposed ? vd.ny : vd.nx, nb = Vox<VT>::kTransposed ? vd.nx : vd.ny;
-  const unsigned int macro_y = vd.macro_elems * (unsigned int)vd.macros_x;
-  const unsigned long long macro_z = (unsigned long long)vd.macro_elems * (unsigned long long)vd.macros_x * (unsigned long long)vd.macros_y;
+  const unsigned int macro_y = macro_stride_y(vd);
+  const unsigned long long macro_z = macro_stride_z(vd);
   // entry i of a table belongs to voxel index i - 1 (VolumeDesc): a = -1 ... na - 1 (lower member of the pair; stored position i),
   // b and z = -1 ... n with the indices clamped into the grid; a quad replica's cells are (x + 1, y + 1), its y entry i is cell i
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
@@ -1525,21 +1473,9 @@ hipError_t launch_axis_tables(VolumeDesc& vd, void* d_tables, hipStream_t stream
   unsigned int* ab = reinterpret_cast<unsigned int*>(tz + axis_z_entries(vd.nz));
   vd.axis_z = tz;
   vd.axis_ab = ab;
-  switch (vd.type) {
-  case VOX_U8: return axis_tables_t<VOX_U8>(vd, ab, tz, stream);
-  case VOX_I8: return axis_tables_t<VOX_I8>(vd, ab, tz, stream);
-  case VOX_U16: return axis_tables_t<VOX_U16>(vd, ab, tz, stream);
-  case VOX_I16: return axis_tables_t<VOX_I16>(vd, ab, tz, stream);
-  case VOX_F32: return axis_tables_t<VOX_F32>(vd, ab, tz, stream);
-  case VOX_F32_T: return axis_tables_t<VOX_F32_T>(vd, ab, tz, stream);
-  case VOX_F32_TT: return axis_tables_t<VOX_F32_TT>(vd, ab, tz, stream);
-  case VOX_U16_T: return axis_tables_t<VOX_U16_T>(vd, ab, tz, stream);
-  case VOX_U16_TT: return axis_tables_t<VOX_U16_TT>(vd, ab, tz, stream);
-  case VOX_F32_Q: return axis_tables_t<VOX_F32_Q>(vd, ab, tz, stream);
-  case VOX_U16_Q: return axis_tables_t<VOX_U16_Q>(vd, ab, tz, stream);
-  case VOX_U8_Q: return axis_tables_t<VOX_U8_Q>(vd, ab, tz, stream);
-  default: return hipErrorInvalidValue;
-  }
+  hipError_t e = hipErrorInvalidValue;
+  dispatch_voxel_type(vd.type, [&](auto vt) { e = axis_tables_t<decltype(vt)::value>(vd, ab, tz, stream); });
+  return e;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1566,8 +1502,8 @@ __device__ __forceinline__ float2 macrocell_cell_range(const void* __restrict__ 
   constexpr unsigned AY = (W + 2 + 2 * (HY - 1) + HY - 1) / HY, AZ = (W + 2 + 2 * (HZ - 1) + HZ - 1) / HZ; // in bricks
   const int bx = max(cx * W - 1, 0), by = max(cy * W - 1, 0), bz = max(cz * W - 1, 0);
   const int ex = min(bx + W + 1, vd.nx), ey = min(by + W + 1, vd.ny), ez = min(bz + W + 1, vd.nz);
-  const unsigned macro_y = vd.macro_elems * (unsigned)vd.macros_x;
-  const unsigned long long macro_z = (unsigned long long)vd.macro_elems * vd.macros_x * vd.macros_y;
+  const unsigned macro_y = macro_stride_y(vd);
+  const unsigned long long macro_z = macro_stride_z(vd);
   const T* base = static_cast<const T*>(vol);
   // voxel x is stored at position x + 1: brick (x + 1) / cx, whose row holds the voxels brick * cx - 1 ... brick * cx + cx - 1
   const unsigned b0 = M::div_cx((unsigned)bx + 1u), nbx = M::div_cx((unsigned)ex) - b0 + 1u; // the bricks along x that hold voxels bx ... ex - 1
@@ -1653,13 +1589,10 @@ hipError_t launch_macrocell_ranges(const VolumeDesc& vd, float* out_minmax, hipS
   const int mcx = (vd.nx + 15) / 16, mcy = (vd.ny + 15) / 16, mcz = (vd.nz + 15) / 16;
   const unsigned long long cells = (unsigned long long)mcx * mcy * mcz;
   const dim3 grid((unsigned)((cells + 3) / 4)), block(256);
-  switch (vd.type) {
-  case VOX_U8: hipLaunchKernelGGL(macrocell_range_kernel<VOX_U8>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
-  case VOX_I8: hipLaunchKernelGGL(macrocell_range_kernel<VOX_I8>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
-  case VOX_U16: hipLaunchKernelGGL(macrocell_range_kernel<VOX_U16>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
-  case VOX_I16: hipLaunchKernelGGL(macrocell_range_kernel<VOX_I16>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
-  default: hipLaunchKernelGGL(macrocell_range_kernel<VOX_F32>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax); break;
-  }
+  if (!dispatch_general_voxel_type(vd.type, [&](auto vt) {
+        hipLaunchKernelGGL(macrocell_range_kernel<decltype(vt)::value>, grid, block, 0, stream, vd.data, vd, mcx, mcy, mcz, (float2*)out_minmax);
+      }))
+    return hipErrorInvalidValue; // the macrocells are computed from the general layout
   return hipGetLastError();
 }
 
@@ -1670,15 +1603,10 @@ hipError_t launch_macrocell_ranges_box(const VolumeDesc& vd, float* out_minmax, 
   if (c.lo[0] < 0 || c.lo[1] < 0 || c.lo[2] < 0 || nx < 1 || ny < 1 || nz < 1 || c.hi[0] >= mcx || c.hi[1] >= mcy || c.hi[2] >= mcz) return hipErrorInvalidValue;
   const unsigned long long cells = (unsigned long long)nx * ny * nz;
   const dim3 grid((unsigned)((cells + 3) / 4)), block(256);
-#define OVR_MC_BOX(VT) hipLaunchKernelGGL(macrocell_range_box_kernel<VT>, grid, block, 0, stream, vd.data, vd, mcx, mcy, c.lo[0], c.lo[1], c.lo[2], nx, ny, nz, (float2*)out_minmax)
-  switch (vd.type) {
-  case VOX_U8: OVR_MC_BOX(VOX_U8); break;
-  case VOX_I8: OVR_MC_BOX(VOX_I8); break;
-  case VOX_U16: OVR_MC_BOX(VOX_U16); break;
-  case VOX_I16: OVR_MC_BOX(VOX_I16); break;
-  default: OVR_MC_BOX(VOX_F32); break;
-  }
-#undef OVR_MC_BOX
+  if (!dispatch_general_voxel_type(vd.type, [&](auto vt) {
+        hipLaunchKernelGGL(macrocell_range_box_kernel<decltype(vt)::value>, grid, block, 0, stream, vd.data, vd, mcx, mcy, c.lo[0], c.lo[1], c.lo[2], nx, ny, nz, (float2*)out_minmax);
+      }))
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // ovr_hip_update.h - launch interface of ovr_hip_update_volume's kernels: the box-restricted siblings of launch_relayout,
-// launch_rebrick and launch_macrocell_ranges (ovr_hip_kernels.h; the kernels stand next to the ones they mirror in ovr_hip_kernels.hip).
+// launch_rebrick and launch_macrocell_ranges (ovr_hip_kernels.h; the kernels stand next to the ones they mirror in ovr_hip_kernels.hip and share
+// their addressing with them: RowSweep / QuadSweep, src_bricked, dispatch_value_type).
 // Internal to libovr_hip.so.
 #pragma once
 

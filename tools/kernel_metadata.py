@@ -2,8 +2,10 @@
 DESIGN.md section 12 and profiles/r09_clipping.md.
 
     python tools/kernel_metadata.py LIB                   one line per raymarch_kernel / shade_pool_kernel instantiation
-    python tools/kernel_metadata.py LIB --against PARENT  every instantiation of PARENT must be in LIB with the same VGPRs, SGPRs, spilled scalars and
-                                                          scratch (exit status 1 otherwise); the instantiations only LIB has are summarised
+    python tools/kernel_metadata.py LIB --against PARENT  every instantiation of PARENT must be in LIB with the same VGPRs, SGPRs, spilled scalars,
+                                                          scratch and LDS (exit status 1 otherwise); the instantiations only LIB has are summarised
+    --all                                                 every kernel of the library, not only the march / shade kernels; with --against the
+                                                          kernels only PARENT has are listed by name (--removed N: exactly N of them are expected)
 
 A template parameter appended behind the existing ones with the value `false` (how MAT and CLIP were added) renames every kernel: names are compared
 with trailing `false` parameters removed."""
@@ -16,11 +18,11 @@ import sys
 import tempfile
 
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
-FIELDS = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size")
+FIELDS = (".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
-def read(lib):
-    """mangled kernel name -> {field: value} for the march / shade kernels of lib"""
+def read(lib, every=False):
+    """mangled kernel name -> {field: value} for the march / shade kernels of lib, or for every kernel"""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         shutil.copy(lib, os.path.join(tmp, "lib.so"))
@@ -39,7 +41,7 @@ def read(lib):
                     for k in FIELDS:
                         if line.startswith(k + ":"):
                             out[name][k] = int(line.split(":")[1])
-    return {n: k for n, k in out.items() if "raymarch_kernel" in n or "shade_pool_kernel" in n}
+    return {n: k for n, k in out.items() if every or "raymarch_kernel" in n or "shade_pool_kernel" in n}
 
 
 def key(name):
@@ -67,21 +69,31 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("lib")
     ap.add_argument("--against")
+    ap.add_argument("--all", action="store_true")
+    ap.add_argument("--removed", type=int, default=0)
     a = ap.parse_args()
-    mine = {key(n): k for n, k in read(a.lib).items()}
+    mine = {key(n): k for n, k in read(a.lib, a.all).items()}
     if not a.against:
         for n in sorted(mine):
             print(n, " ".join(f"{f[1:]}={mine[n].get(f, 0)}" for f in FIELDS))
         return 0
-    parent = {key(n): k for n, k in read(a.against).items()}
-    changed = [n for n in parent if n not in mine or mine[n] != parent[n]]
+    parent = {key(n): k for n, k in read(a.against, a.all).items()}
+    removed = sorted(n for n in parent if n not in mine) if a.all else []
+    changed = [n for n in parent if n not in removed and (n not in mine or mine[n] != parent[n])]
     new = sorted(set(mine) - set(parent))
-    print(f"{len(parent)} instantiations in the parent, {len(parent) - len(changed)} with identical metadata here, {len(changed)} changed or missing")
+    print(f"{len(parent)} instantiations in the parent, {len(parent) - len(changed) - len(removed)} with identical metadata here, {len(changed)} changed or missing")
     for n in changed:
         print("  CHANGED", n, parent[n], "->", mine.get(n))
+    if a.all:
+        print(f"{len(removed)} kernels of the parent are not here ({a.removed} expected)")
+        for n in removed:
+            print("  REMOVED", n)
     print(f"{len(new)} new instantiations; using scratch: {sum(1 for n in new if mine[n].get('.private_segment_fixed_size', 0) > 0)}")
     groups = {}
     for n in new:
+        if "raymarch_kernel" not in n and "shade_pool_kernel" not in n:
+            print("  NEW", n, mine[n])
+            continue
         kern, p = params(n)
         p = p + [0] * (9 - len(p))
         g = (kern, p[1], "pooled" if kern == "raymarch_kernel" and p[3] else "", p[4] if kern == "raymarch_kernel" else p[3])
@@ -93,7 +105,7 @@ def main():
     for n in new:
         if mine[n].get(".private_segment_fixed_size", 0) > 0:
             print("  SCRATCH", n, mine[n])
-    return 1 if changed else 0
+    return 1 if changed or len(removed) != a.removed or (a.all and new) else 0
 
 
 if __name__ == "__main__":

@@ -287,7 +287,7 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.world = r->shard.current.world;
   P.tile_w = r->shard.current.tw;
   P.tile_h = r->shard.current.th;
-  P.lds_staging = P.clip_on ? 0 : r->lds_staging.current; // a clipped frame takes the ordinary march: the same frame, lds_rounds == 0
+  P.lds_staging = r->lds_staging.current;
   P.lds_brick_offset = 0;
   P.jitter_mode = r->jitter.current;
   P.jitter_noise = r->d_noise;
@@ -531,7 +531,8 @@ static int launch_frame(ovr_hip_renderer* r)
   const bool phases = r->phase_timing.load();
   hipEvent_t evs[4] = { r->ev[0], phases ? r->ev[1] : nullptr, phases ? r->ev[2] : nullptr, r->ev[3] };
   r->frame_phase_timed = phases;
-  HIP_TRY(launch_raymarch(r->P, st, evs));
+  r->plan = plan_raymarch(r->P);
+  HIP_TRY(launch_raymarch(r->P, r->plan, st, evs));
   r->frame_words_dirty = false;
   if (r->conv.frame) { // behind the frame's last kernel and its last event: kernel_ms stays the frame's own time
     ConvergenceParams c{};
@@ -637,7 +638,7 @@ static int read_frame_stats(ovr_hip_renderer* r)
   if (r->h_counters[7] > 0) r->outside_hits = true;
   if (r->outside_hits) r->map_whole_set(r->frame_set);
   r->stats.lds_fallback_taps = r->stats.lds_unstaged_rounds = r->stats.lds_rounds = 0;
-  if (raymarch_lds_staged(r->P)) {
+  if (r->plan.march.lds_staged) {
     // the unshaded f32 march ran its LDS-staged variant: the two skip counters carried its diagnostics
     r->stats.lds_fallback_taps = r->h_counters[5];
     r->stats.lds_unstaged_rounds = r->h_counters[6];

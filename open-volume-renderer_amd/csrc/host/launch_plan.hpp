@@ -1,0 +1,171 @@
+// launch_plan.hpp - which march and shade kernel a frame takes and what each launch needs, as a pure function of a few facts about the frame:
+// the ONLY statement of the variant rules.  Nothing here calls HIP or knows RayMarchParams: plan_raymarch (ovr_hip_kernels.hip) fills the facts
+// and reads the environment switches, frame_kernels<VT> (ovr_hip_device.h) turns a plan into the two kernels, launch_raymarch launches them, the
+// kernels' static_asserts ask march_variant_exists / shade_variant_exists - and tests/test_launch_plan.py drives the same code on a machine without
+// a GPU.  Every variant renders the same frame bit for bit, so a wrong choice here shows as speed alone: hence the tables of that test.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+
+namespace ovrhip {
+
+// ---- the sizes the decision needs (the device code includes this header for them)
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int request_queue_entries(int shade, bool pooled) { return shade == 0 ? 0 : (pooled ? 128 : 256); } // per wave; pooled: spills after every instruction
+template <int SHADE, bool POOLED> struct QCfg {
+  static constexpr int K = POOLED ? 4 : (SHADE == 0 ? 4 : 3);   // instructions (x4 steps) per round
+  static constexpr int QCAP = request_queue_entries(SHADE, POOLED);
+};
+constexpr int kShadeReqBytes = 32;                      // sizeof(ShadeReq)
+constexpr int kLdsBrickCap = 384;                       // LDS-staged bricks: 48 KiB of bricks per workgroup, two workgroups per CU
+constexpr int kLdsRegionBytes = 32;                     // sizeof(LdsRegion)
+constexpr int kShadeBlocks = 1024; // persistent shade grid: at most 4 workgroups per CU (size of the shade_counters workspace)
+// The deep variant of the pooled march (6 instead of 4 instructions per round, 2 instead of 3 waves per SIMD) pays when the launch is
+// bound by its longest ray's chain of dependent rounds rather than by throughput: image shards with few blocks.  Measured
+// (profiles/r02_ab/r02b_deep.txt, march ms plain -> deep): C3 4-way 0.443 -> 0.422, 8-way 0.288 -> 0.254, 2-way (16 200 blocks) equal;
+// but C5 (4K: 16 200 blocks even 8-way, throughput-bound) 0.508 -> 0.607 and C4 8-way (64-bit addressing) 0.604 -> 0.632: so only
+// shards of at most 10 000 blocks with 32-bit addressing take it.
+constexpr unsigned int kDeepMaxBlocks = 10000;
+// ovr_hip_kernels.h's kBlockCounters and axis_a / b / z_entries, restated (that header needs the HIP runtime); ovr_hip_kernels.hip asserts that they agree
+constexpr int kCounterWords = 8;
+constexpr int kAxisAbExtra = 3, kAxisZExtra = 2; // table entries beyond nx + ny (a: n + 1, b: n + 2, whichever of x / y is the pair axis) and beyond nz
+
+// ---- which instantiations exist: raymarch_kernel<VT, shade, am, pooled, skip, lds_staged, deep, material, clipped> (f32_general: VT is the general f32
+// layout) and shade_pool_kernel<VT, shade, am, skip, material, clipped>; am == 4 only for the layouts row_load_layout names
+constexpr bool row_load_layout(int elem_bytes, bool quad) { return elem_bytes <= 2 && !quad; } // the 16-bit pairs (and 8-bit ones) as aligned 8-byte rows
+constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, bool lds_staged, bool deep, bool material, bool clipped, bool f32_general)
+{
+  if (shade < 0 || shade > 2 || am < 0 || am > 4 || (f32_general && am == 4)) return false;
+  if (pooled && shade == 0) return false;                                      // nothing to shade: the in-place march is the only pipeline
+  if (lds_staged) return f32_general && shade == 0 && !skip && am <= 1 && !deep && !material && !clipped; // the unshaded in-place march only
+  if (deep) return pooled && !skip && (am <= 1 || am == 4) && !material && !clipped; // the plain pooled march with 32-bit addressing
+  if (material && (shade == 0 || pooled)) return false;                        // where the march shades: in place (pooled: shade_pool_kernel)
+  if (clipped && !pooled && material != (shade != 0)) return false;            // the clipped in-place march rides on the material variant where it shades
+  return true;
+}
+constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material, bool clipped)
+{
+  if (shade < 1 || shade > 2 || am < 0 || am > 4) return false;
+  (void)skip;
+  return !clipped || (shade == 2 && material); // clipped where the shade kernel marches shadow rays, on the material variant
+}
+
+// ---- LDS arithmetic
+// the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
+// (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
+constexpr size_t tf_lds_bytes(int n_color, int n_alpha)
+{
+  const size_t need = (size_t)n_color * 16 + (size_t)n_alpha * 4 + 32;
+  return need <= 96 * 1024 ? need : 0;
+}
+// the per-axis offset tables as the kernels stage them (stage_tables): modes 0 / 1 / 4 hold 32-bit entries, 2 a 64-bit z table, 3 none
+constexpr size_t axis_table_bytes(int nx, int ny, int nz, int am)
+{
+  const size_t ab = (size_t)(nx + ny + kAxisAbExtra), ez = (size_t)(nz + kAxisZExtra);
+  return am == 3 ? 0 : am == 2 ? ez * 8 + ab * 4 : (ab + ez) * 4;
+}
+constexpr size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// Addressing mode of a volume layout: 0 = 32-bit byte offsets (<= 4 GiB), 1 = 32-bit element offsets (< 2^32 stored voxels), 2 = 64-bit z
+// table, 3 = computed 64-bit offsets, no tables.  Modes 0-2 keep the per-axis tables in LDS next to the transfer function and the request
+// queues (32 KiB in the in-place march): a volume with one very long axis - small in bytes, tens of thousands of voxels long - whose
+// tables do not fit in the 160 KiB of a CU takes mode 3 whatever its size.
+constexpr int addressing_mode(unsigned long long stored_bytes, int elem_bytes, int nx, int ny, int nz, int n_color, int n_alpha)
+{
+  const int am = stored_bytes <= 0x100000000ull ? 0 : (stored_bytes / (unsigned long long)elem_bytes < 0xffffffffull) ? 1 : 2;
+  const size_t tables = axis_table_bytes(nx, ny, nz, am);
+  const size_t fixed = tf_lds_bytes(n_color, n_alpha) + (size_t)kWaves * request_queue_entries(1, false) * kShadeReqBytes + 1024; // TF + the largest request queues + slack
+  return ((am == 2 && tables > 64 * 1024) || tables + 16 + fixed > 160 * 1024) ? 3 : am;
+}
+
+// ---- facts -> plan
+struct LaunchFacts {
+  int elem_bytes = 4;                 // of a stored voxel
+  bool quad = false, f32_general = false;
+  int nx = 1, ny = 1, nz = 1;
+  unsigned long long stored_bytes = 0;
+  bool tables = true;                 // the layout's axis tables are present
+  int n_color = 1, n_alpha = 1, shading = 0;
+  bool pool = false, skipping = false, sparse = false; // request pool / majorant grid / sample list present
+  unsigned long long sparse_hint_pixels = 0;
+  int world = 1;
+  unsigned int n_blocks_owned = 0, n_schedule = 0;
+  bool schedule = true;               // the dense frame's block list is present
+  bool clip_on = false, lds_staging = false;
+  int row_loads = 0;                  // 0 = by the layout's size, 1 = never, 2 = always
+  int shade_blocks = 0;               // 0 = the default
+  bool reference_material = true, shade_order = false; // the material is the reference's; the pool has an order buffer
+};
+// the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
+struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
+
+struct LaunchPlan {
+  int shading = 0;                    // 0, 1 or 2: the kernels' SHADE
+  int am = 0;                         // 0 ... 3 above; 4 = mode 0 with the 16-bit pairs read as aligned 8-byte rows (RowLoads)
+  bool pooled = false, skip = false;
+  struct March { bool lds_staged = false, deep = false, material = false, clipped = false; } march;
+  struct Shade { bool material = false, clipped = false; } shade;
+  bool shade_order = false;           // the shade kernel meets the runs sorted by light beam (PoolDesc::order)
+  size_t march_lds_bytes = 0, shade_lds_bytes = 0;
+  unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
+  int shade_grid_blocks = 0;
+  bool error = false;                 // the frame cannot be launched (hipErrorInvalidValue)
+};
+
+// the deep rounds' rule without the kernel's own conditions
+inline bool deep_rounds_pay(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  if (o.deep >= 0) return o.deep != 0;
+  // sparse (foveated) frames: the kept rays are few and concentrated where the rays are long - the same floor (march 1.12 -> 1.01 ms at the
+  // app's default focus); the host passes the previous frame's pixel count, the list's length is only known on the device
+  if (f.sparse) return f.world == 1 && f.sparse_hint_pixels > 0 && f.sparse_hint_pixels <= 64ull * kDeepMaxBlocks;
+  // (the threshold was measured on the number of blocks a shard OWNS, launched or not)
+  return f.world > 1 && f.n_blocks_owned <= kDeepMaxBlocks;
+}
+
+inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
+{
+  LaunchPlan pl;
+  pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  const int sh = pl.shading;
+  // addressing: the layout's mode, a more general one on request, then the row loads on mode 0
+  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
+  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
+  const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+  if ((am < 3 && !f.tables) || tf == 0 || (!f.sparse && f.n_schedule > 0 && !f.schedule)) { pl.error = true; return pl; }
+  // mode 4: layouts the caches do not serve (by size), or forced either way
+  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
+  pl.am = am;
+  pl.skip = f.skipping;
+  pl.pooled = sh != 0 && f.pool;
+  const size_t tables = align16(axis_table_bytes(f.nx, f.ny, f.nz, am));
+  const size_t queues = (size_t)kWaves * request_queue_entries(sh, pl.pooled) * kShadeReqBytes;
+  if (!pl.pooled) {
+    pl.march_lds_bytes = std::max<size_t>(tf + tables + queues, (size_t)kWaves * kCounterWords * 4); // the counter reduction reuses it
+    // a clipped frame takes the ordinary march (the same frame, and no further set of kernels), and where that shades, its material variant
+    if (f.f32_general && sh == 0 && !f.skipping && am <= 1 && f.lds_staging && !f.sparse && !f.clip_on) {
+      pl.march.lds_staged = true; // [.. tables, TF ..][bricks][region descriptor][corner rays 4 x float3][t range]
+      pl.lds_brick_offset = (unsigned int)align16(pl.march_lds_bytes);
+      pl.march_lds_bytes = pl.lds_brick_offset + (size_t)kLdsBrickCap * 128 + kLdsRegionBytes + 12 * 4 + 2 * 4 + 16;
+    }
+    else {
+      pl.march.clipped = f.clip_on;
+      pl.march.material = sh != 0 && (f.clip_on || !f.reference_material);
+    }
+    return pl;
+  }
+  pl.march_lds_bytes = queues + tables + (size_t)f.n_alpha * 4 + 64;
+  pl.march.clipped = f.clip_on;
+  pl.march.deep = !f.skipping && (am <= 1 || am == 4) && !f.clip_on && deep_rounds_pay(f, o); // a small image shard: the longest ray's chain of rounds is the floor
+  pl.shade.clipped = sh == 2 && f.clip_on; // shadow rays are clipped too; without them the shade kernel never tests the box
+  pl.shade.material = pl.shade.clipped || !f.reference_material;
+  pl.shade_order = sh == 2 && f.shade_order; // no shadow rays: creation order (its tickets' batches, profiles/r02_notes.md section 11)
+  pl.shade_lds_bytes = std::max<size_t>(tf + tables, 64);
+  const int blocks = o.shade_blocks > 0 ? o.shade_blocks : f.shade_blocks;
+  pl.shade_grid_blocks = blocks > 0 ? std::min(blocks, kShadeBlocks) : kShadeBlocks;
+  return pl;
+}
+
+} // namespace ovrhip

@@ -304,6 +304,7 @@ struct ovr_hip_renderer {
   unsigned int* h_ctrl = nullptr; // pinned copy of pool.ctrl
 
   ovrhip::RayMarchParams P{};
+  ovrhip::LaunchPlan plan{}; // of the frame in flight (launch_frame): which kernel variants P was launched with
   ovr_hip_stats stats{};
   double render_time_ms = 0.0;
   bool async_pending = false;

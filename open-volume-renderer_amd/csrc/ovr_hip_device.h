@@ -1,6 +1,7 @@
 // ovr_hip_device.h - device code of the ray-march path that depends on the voxel type: helpers, the bricked voxel access,
-// raymarch_kernel / shade_pool_kernel and their launch dispatch.  Included by ovr_hip_kernels.hip (type-independent kernels
-// and the launch interface) and by ovr_hip_march.hip (one explicit instantiation of launch_v, compiled once per voxel type).
+// raymarch_kernel / shade_pool_kernel and frame_kernels, the lookup from a launch plan (host/launch_plan.hpp) to its two kernels.  Included by
+// ovr_hip_kernels.hip (type-independent kernels, the launch sequence) and by ovr_hip_march.hip (one explicit instantiation of frame_kernels, compiled
+// once per voxel type).
 // See ovr_hip_kernels.hip for the overview.
 #pragma once
 #include "ovr_hip_kernels.h"
@@ -350,7 +351,7 @@ __device__ __forceinline__ unsigned int tap_cell(const VolConsts& vc, const Tap&
 // a 512^3 u16 volume at 512^2 0.353 -> 0.335; the 8-bit layouts' 2-byte pairs likewise (a 1024^3 u8 volume at C3's settings 1.80 -> 1.70 ms, front view 1.085 ->
 // 0.97) - where the layout is large: C1 (256^3 u8) is bound by vector issue and the shifts cost it 3 % (0.183 -> 0.188 ms), see RowLoads.
 // Which launches take the row loads: the 16-bit and 8-bit volumes whose layout is too large for the caches to serve (addressing modes 1 and 2, and mode 4 = mode 0's
-// 32-bit byte offsets + row loads: launch_vs upgrades a 16-bit or 8-bit layout of more than 128 MB).  Small 16-bit volumes are bound by vector issue and keep the
+// 32-bit byte offsets + row loads: plan_launch upgrades a 16-bit or 8-bit layout of more than 128 MB).  Small 16-bit volumes are bound by vector issue and keep the
 // 4-byte loads (a 256 x 256 x 226 u16 volume, all samples shaded in place: 0.88 -> 1.08 ms WITH the row loads; the 1024 x 1024 x 1080 one 34 -> 24 ms).
 template <int VT, int AM> struct RowLoads { static constexpr bool on = sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad && (AM == 1 || AM == 2 || AM == 4); };
 template <int VT, int AM, typename B>
@@ -814,9 +815,7 @@ __device__ __forceinline__ float march_shadow(const RayMarchParams& P, const Vol
 //                                    a third kernel walks each tile's chunks in order and composites.
 //  * counters: per-workgroup partial sums, reduced by a tiny kernel (no same-address atomics).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-
+// (kBlock = 256 threads, kWaves = 4: host/launch_plan.hpp, with the other sizes the launch decision reads)
 constexpr int kShadowTaps = 4; // shadow-march taps in flight per lane
 // chunks a tile reserves at a time: consecutive chunks of one tile are shaded by ONE workgroup, one chunk per wave
 // (L1/L2 reuse: measured 2.4 -> 1.5 ms for the shading kernel at C3; 8 / 16 / 32 are slower - imbalance)
@@ -833,6 +832,7 @@ struct ShadeReq { // 32 bytes; after shading the same slot holds the result (cx,
   float a;          // corrected opacity
   int next;         // stream position of the owner's next request (valid once that request exists)
 };
+static_assert(sizeof(ShadeReq) == kShadeReqBytes, "launch_plan.hpp restates the request's size");
 
 __device__ __forceinline__ float bperm(int src_lane, float x)
 {
@@ -899,28 +899,6 @@ __device__ __forceinline__ size_t stage_tables(const RayMarchParams& P, unsigned
   vc.tab_x = tx + 1; vc.tab_y = tx + ea + 1; vc.tab_z = tz + 1;
   return (size_t)(nab + ez) * sizeof(unsigned int);
 }
-// Addressing mode of a volume layout: 0 = 32-bit byte offsets (<= 4 GiB), 1 = 32-bit element offsets (< 2^32 stored voxels), 2 = 64-bit z
-// table, 3 = computed 64-bit offsets, no tables.  Modes 0-2 keep the per-axis tables in LDS next to the transfer function and the request
-// queues (32 KiB in the in-place march): a volume with one very long axis - small in bytes, tens of thousands of voxels long - whose
-// tables do not fit in the 160 KiB of a CU takes mode 3 whatever its size (before round 3 only mode 2 fell back, and such a volume was
-// accepted by ovr_hip_set_volume and failed at its first launch).
-__host__ inline int addressing_mode(const VolumeDesc& vd, int n_color, int n_alpha)
-{
-  int am = vd.bytes <= 0x100000000ull ? 0 : (vd.bytes / voxel_size(vd.type) < 0xffffffffull) ? 1 : 2;
-  const size_t ab = (size_t)(vd.nx + vd.ny + 3), ez = (size_t)axis_z_entries(vd.nz); // a: n + 1 entries, b: n + 2 (whichever of x / y is the pair axis)
-  const size_t tables = am == 2 ? ez * sizeof(unsigned long long) + ab * sizeof(unsigned int) : (ab + ez) * sizeof(unsigned int);
-  const size_t fixed = raymarch_lds_bytes(n_color, n_alpha) + (size_t)kWaves * 256 * 32 + 1024; // TF + the largest request queues + slack
-  if ((am == 2 && tables > 64 * 1024) || tables + 16 + fixed > 160 * 1024) am = 3;
-  return am;
-}
-__host__ inline size_t table_lds_bytes(const RayMarchParams& p, int am)
-{
-  if (am == 3) return 0;
-  const size_t ab = (size_t)(p.vol.nx + p.vol.ny + 3), ez = (size_t)axis_z_entries(p.vol.nz);
-  if (am == 2) return (ez * sizeof(unsigned long long) + ab * sizeof(unsigned int) + 15) & ~(size_t)15;
-  return ((ab + ez) * sizeof(unsigned int) + 15) & ~(size_t)15;
-}
-
 // stage the transfer function in LDS (all threads of the workgroup); color may be skipped by alpha-only kernels
 __device__ __forceinline__ void stage_tf(const RayMarchParams& P, unsigned char* tf_base, bool with_color, TfConsts& tf)
 {
@@ -1214,11 +1192,6 @@ __device__ __forceinline__ SkipSpan skip_interval(const VolConsts& vc, f3 oo, f3
   return sp;
 }
 
-template <int SHADE, bool POOLED> struct QCfg {
-  static constexpr int K = POOLED ? 4 : (SHADE == 0 ? 4 : 3);   // instructions (x4 steps) per round
-  static constexpr int QCAP = SHADE == 0 ? 0 : (POOLED ? 128 : 256);       // pooled: spills after every instruction
-};
-
 // Register budget: at most 3 waves per SIMD (up to 168 VGPRs).  Left alone the compiler squeezes the kernel into 128 VGPRs
 // for a 4th wave by serialising the K tap groups it is supposed to keep in flight - measured 1.98 instead of 1.53 ms on C3.
 constexpr int kMarchWavesPerEu = 3;
@@ -1228,12 +1201,13 @@ constexpr int kMarchWavesPerEu = 3;
 // round's taps read LDS (ds_read2_b32 pairs) instead of going through the texture addresser.  A round whose box exceeds the LDS
 // budget, and a tap that falls outside the staged box, take the ordinary path - the result is bit-identical either way.
 // Built for the in-place, unshaded march of the general f32 layout (BASELINE C2, where rays are denser than voxels).
-constexpr int kLdsBrickCap = 384;                       // 48 KiB of bricks per workgroup: two workgroups per CU
+// (kLdsBrickCap bricks per workgroup, QCfg: host/launch_plan.hpp)
 struct LdsRegion { int bx0, by0, bz0, ebx, eby, ebz, nbr, ok; };
+static_assert(sizeof(LdsRegion) == kLdsRegionBytes, "launch_plan.hpp restates the region descriptor's size");
 // DEEP = true (plain pooled march only): 6 instead of 4 instructions (x 4 steps) per round - 24 pair loads in flight per lane at 2
 // waves per SIMD (198 VGPRs) instead of 16 at 3.  On a full frame the two are within 1 % of each other (and 4 is better with dense
 // transfer functions and on axis views), but a ray's chain of dependent rounds is the floor of an image SHARD's march, and there 6
-// wins: 8-way shard of C3 0.295 -> 0.250 ms, 4-way 0.451 -> 0.423 (profiles/r02_notes.md).  launch_vsbs picks it for small shards (use_deep_rounds).
+// wins: 8-way shard of C3 0.295 -> 0.250 ms, 4-way 0.451 -> 0.423 (profiles/r02_notes.md).  plan_launch picks it for small shards (deep_rounds_pay).
 constexpr int kDeepK = 6;
 // (the skipping pooled march sits at the edge of the 3-waves budget: 169 VGPRs - one too many - cost it 15 %; it is pinned to 3)
 constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scratch under the pin
@@ -1242,11 +1216,8 @@ constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scrat
 template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
-  static_assert(!LDSB || (SHADE == 0 && !POOLED && !SKIP && AM <= 1 && !Vox<VT>::kTransposed), "LDS-staged bricks: unshaded in-place march only");
+  static_assert(march_variant_exists(SHADE, AM, POOLED, SKIP, LDSB, DEEP, MAT, CLIP, VT == VOX_F32), "no such variant of the march (host/launch_plan.hpp)");
   using Cfg = QCfg<SHADE, POOLED>;
-  static_assert(!DEEP || (POOLED && !SKIP && !LDSB), "the deep variant exists for the plain pooled march");
-  static_assert(!MAT || (SHADE != 0 && !POOLED), "the material variant exists where the march shades: in place (pooled: shade_pool_kernel)");
-  static_assert(!CLIP || (!LDSB && !DEEP && (MAT || SHADE == 0 || POOLED)), "the clipped variant: the ordinary march, with the material variant where it shades");
   constexpr int K = DEEP ? kDeepK : Cfg::K;
   constexpr int QCAP = Cfg::QCAP;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1815,7 +1786,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
 template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false>
 __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams P)
 {
-  static_assert(!CLIP || (SHADE == 2 && MAT), "the clipped variant exists where the shade kernel marches shadow rays, on the material variant");
+  static_assert(shade_variant_exists(SHADE, AM, SKIP, MAT, CLIP), "no such variant of the shade kernel (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   TfConsts tf;
@@ -1939,206 +1910,74 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
 }
 
 
-constexpr int kReduceBlocks = 64;
+// ------------------------------------------------------------------------------------------------------------------
+// a launch plan's two kernels.  SHADE and AM come from a switch each, the plan's flags become template arguments through ONE constant, a set of
+// bits: every combination for which march_variant_exists / shade_variant_exists (host/launch_plan.hpp) holds is instantiated, and nothing else
+// ------------------------------------------------------------------------------------------------------------------
+typedef void (*FrameKernel)(const RayMarchParams);
+struct FrameKernels { FrameKernel march = nullptr, shade = nullptr; }; // shade: pooled plans only; march == nullptr: no such variant of this type
+enum VariantBits : unsigned { kBitPooled = 1, kBitSkip = 2, kBitLdsStaged = 4, kBitDeep = 8, kBitMaterial = 16, kBitClipped = 32, kVariantBitsEnd = 64 };
+constexpr unsigned kShadeBits = kBitSkip | kBitMaterial | kBitClipped; // the flags shade_pool_kernel has
 
-// the two kernels of the pooled pipeline that do not depend on the voxel type live in ovr_hip_kernels.hip
-hipError_t launch_composite(const RayMarchParams& q, dim3 grid, hipStream_t stream);
-hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream);
-hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, const unsigned int* shade_partials, int n_shade_blocks,
-                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream,
-                                  unsigned int* conv_asked = nullptr);
-
-inline dim3 raymarch_grid(const RayMarchParams& p)
+template <int VT, int SHADE, int AM, unsigned BITS>
+constexpr FrameKernel march_variant()
 {
-  return dim3((unsigned)raymarch_grid_blocks(p));
+  constexpr bool pooled = BITS & kBitPooled, skip = BITS & kBitSkip, lds_staged = BITS & kBitLdsStaged, deep = BITS & kBitDeep, material = BITS & kBitMaterial,
+                 clipped = BITS & kBitClipped;
+  if constexpr (march_variant_exists(SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, VT == VOX_F32))
+    return raymarch_kernel<VT, SHADE, AM, pooled, skip, lds_staged, deep, material, clipped>;
+  else return nullptr;
 }
-
-template <typename KernT>
-inline hipError_t set_lds(KernT kern, size_t lds)
+template <int VT, int SHADE, int AM, unsigned BITS>
+constexpr FrameKernel shade_variant()
 {
-  if (lds > 64 * 1024) return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  return hipSuccess;
+  constexpr bool skip = BITS & kBitSkip, material = BITS & kBitMaterial, clipped = BITS & kBitClipped;
+  if constexpr ((BITS & ~kShadeBits) == 0 && shade_variant_exists(SHADE, AM, skip, material, clipped)) return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped>;
+  else return nullptr;
 }
-
-constexpr int kShadeBlocks = 1024; // persistent shade grid: at most 4 workgroups per CU (size of the shade_counters workspace)
-// workgroups of the persistent shade kernel for this frame; OVR_HIP_SHADE_BLOCKS overrides it (measurements)
-inline int shade_grid_blocks(const RayMarchParams& p)
+template <int VT, int SHADE, int AM, unsigned... BITS>
+inline FrameKernels variants_of(unsigned march_bits, unsigned shade_bits, std::integer_sequence<unsigned, BITS...>)
 {
-  static const int forced = getenv("OVR_HIP_SHADE_BLOCKS") ? atoi(getenv("OVR_HIP_SHADE_BLOCKS")) : 0;
-  if (forced > 0) return std::min(forced, kShadeBlocks);
-  return p.shade_blocks > 0 ? std::min(p.shade_blocks, kShadeBlocks) : kShadeBlocks;
-}
-
-// The deep variant of the pooled march (6 instead of 4 instructions per round, 2 instead of 3 waves per SIMD) pays when the launch is
-// bound by its longest ray's chain of dependent rounds rather than by throughput: image shards with few blocks.  Measured
-// (profiles/r02_ab/r02b_deep.txt, march ms plain -> deep): C3 4-way 0.443 -> 0.422, 8-way 0.288 -> 0.254, 2-way (16 200 blocks) equal;
-// but C5 (4K: 16 200 blocks even 8-way, throughput-bound) 0.508 -> 0.607 and C4 8-way (64-bit addressing) 0.604 -> 0.632: so only
-// shards of at most 10 000 blocks with 32-bit addressing take it.  OVR_HIP_DEEP=0|1 overrides the choice (measurements).
-constexpr unsigned int kDeepMaxBlocks = 10000;
-inline bool use_deep_rounds(const RayMarchParams& p)
-{
-  static const int forced = getenv("OVR_HIP_DEEP") ? atoi(getenv("OVR_HIP_DEEP")) : -1;
-  if (forced >= 0) return forced != 0;
-  // sparse (foveated) frames: the kept rays are few and concentrated where the rays are long - the same floor (round 3: march 1.12 ->
-  // 1.01 ms at the app's default focus); the host passes the previous frame's pixel count, the list's length is only known on the device
-  if (p.sparse_xy) return p.world == 1 && p.sparse_hint_pixels > 0 && p.sparse_hint_pixels <= 64ull * kDeepMaxBlocks;
-  // (the threshold was measured on the number of blocks a shard OWNS, launched or not: n_blocks_owned - n_schedule may be smaller since
-  // round 4, when blocks none of whose rays hits the box are no longer launched)
-  return p.world > 1 && p.n_blocks_owned <= kDeepMaxBlocks;
-}
-
-template <int VT, int SHADE, int AM, bool SKIP>
-inline hipError_t launch_vsbs(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
-{
-  const size_t tf_lds = raymarch_lds_bytes(p.n_color, p.n_alpha);
-  if (tf_lds == 0) return hipErrorInvalidValue;
-  if (!p.sparse_xy && p.n_schedule > 0 && !p.schedule) return hipErrorInvalidValue;
-  const dim3 grid = raymarch_grid(p), block(kBlock);
-  hipError_t e;
-  // a march variant's launch: its LDS limit, then the kernel unless no block of this renderer's has a hit
-  auto march = [&](auto kern, size_t lds_bytes, const RayMarchParams& prm) -> hipError_t {
-    if (hipError_t err = set_lds(kern, lds_bytes)) return err;
-    if (grid.x > 0) hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, prm);
-    return hipSuccess;
-  };
-  const bool pooled = (SHADE != 0) && p.pool.reqs != nullptr;
-  if (!pooled) {
-    const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM) + (size_t)kWaves * QCfg<SHADE, false>::QCAP * sizeof(ShadeReq), (size_t)kWaves * kNC * sizeof(unsigned int)); // the counter reduction reuses it
-    bool launched = false;
-    if constexpr (VT == VOX_F32 && SHADE == 0 && AM <= 1 && !SKIP) {
-      if (lds_staging_applies(p)) { // LDS-staged bricks (see raymarch_kernel): the bricks follow the tables and the TF
-        RayMarchParams q = p;
-        q.lds_brick_offset = (unsigned int)((lds + 15) & ~(size_t)15);
-        const size_t lds2 = q.lds_brick_offset + (size_t)kLdsBrickCap * 128 + sizeof(LdsRegion) + 12 * sizeof(float) + 2 * sizeof(int) + 16;
-        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, true>, lds2, q)) != hipSuccess) return e;
-        launched = true;
-      }
-    }
-    if (!launched) {
-      bool with_material = false;
-      if (p.clip_on) { // a committed clip box (box_test): the clipped instantiation - where the march shades, of the material variant
-        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, SHADE != 0, true>, lds, p)) != hipSuccess) return e;
-        with_material = true;
-      }
-      else if constexpr (SHADE != 0) {
-        if (!reference_material(p)) { // a material or intensity of the caller's (shade_light)
-          if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP, false, false, true>, lds, p)) != hipSuccess) return e;
-          with_material = true;
-        }
-      }
-      if (!with_material) {
-        if ((e = march(raymarch_kernel<VT, SHADE, AM, false, SKIP>, lds, p)) != hipSuccess) return e;
-      }
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev && ev[1] && ev[2]) { (void)hipEventRecord(ev[1], stream); (void)hipEventRecord(ev[2], stream); }
-    if (p.block_counters && p.counters) {
-      if (!p.publish || p.zero_first)
-        if ((e = hipMemsetAsync(p.counters, 0, 8 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
-      if ((e = launch_reduce_counters(p.block_counters, (int)raymarch_grid_blocks(p), nullptr, 0, p.counters, nullptr, p.publish, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e;
-    }
-    return hipGetLastError();
+  FrameKernels k;
+  if constexpr (AM != 4 || row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) { // (mode 4 is RowLoads' own)
+    static_assert(AM != 4 || RowLoads<VT, 4>::on, "row_load_layout (host/launch_plan.hpp) names the layouts RowLoads is on for");
+    static constexpr FrameKernel march[] = { march_variant<VT, SHADE, AM, BITS>()... }, shade[] = { shade_variant<VT, SHADE, AM, BITS>()... };
+    k.march = march[march_bits];
+    k.shade = shade[shade_bits];
   }
-  if constexpr (SHADE != 0) { // (no pooled kernels are built for SHADE == 0: the in-place march above is its only pipeline)
-    // ---- pooled pipeline: march -> shade -> composite, once per sample-per-pixel generation
-    // (the last frame's final reduction left the control words and the counters zeroed - RayMarchParams::publish)
-    const bool self_cleaning = p.publish && p.block_counters && p.counters && !p.zero_first;
-    if (!self_cleaning) {
-      if ((e = hipMemsetAsync(p.pool.ctrl, 0, (size_t)kPoolCtrlWords * sizeof(unsigned int), stream)) != hipSuccess) return e;
-      if (p.block_counters && p.counters)
-        if ((e = hipMemsetAsync(p.counters, 0, 8 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
-    }
-    RayMarchParams q = p;
-    if (SHADE != 2) q.pool.order = nullptr; // no shadow rays: creation order (its tickets' batches, profiles/r02_notes.md section 11)
-    for (int g = 0; g < p.spp; ++g) {
-      q.spp_index = g;
-      if (g > 0 && (e = hipMemsetAsync(p.pool.ctrl, 0, (size_t)32 * (kPoolSubs + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e; // all but the frame's maximum
-      {
-        constexpr int SH = SHADE;
-        const size_t lds = (size_t)kWaves * QCfg<SH, true>::QCAP * sizeof(ShadeReq) + table_lds_bytes(p, AM) + (size_t)p.n_alpha * sizeof(float) + 64;
-        bool launched = false;
-        if constexpr (!SKIP && (AM <= 1 || AM == 4)) {
-          if (use_deep_rounds(p) && !p.clip_on) { // (a clipped frame takes the plain rounds: the same frame, and no third set of pooled kernels) a small image shard: the longest ray's chain of rounds is the floor - deeper rounds
-            if ((e = march(raymarch_kernel<VT, SH, AM, true, SKIP, false, true>, lds, q)) != hipSuccess) return e;
-            launched = true;
-          }
-        }
-        if (!launched) {
-          if ((e = march(p.clip_on ? raymarch_kernel<VT, SH, AM, true, SKIP, false, false, false, true> : raymarch_kernel<VT, SH, AM, true, SKIP>, lds, q)) != hipSuccess) return e;
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-      }
-      if (ev && ev[1] && g == p.spp - 1) (void)hipEventRecord(ev[1], stream);
-      if (q.pool.order && (e = launch_shade_order(q, stream)) != hipSuccess) return e; // runs sorted by light beam (PoolDesc)
-      {
-        const size_t lds = std::max<size_t>(tf_lds + table_lds_bytes(p, AM), 64);
-        auto kern = reference_material(p) ? shade_pool_kernel<VT, SHADE, AM, SKIP, false> : shade_pool_kernel<VT, SHADE, AM, SKIP, true>;
-        if constexpr (SHADE == 2) { // shadow rays are clipped too; without them (SHADE == 1) the shade kernel never tests the box
-          if (p.clip_on) kern = shade_pool_kernel<VT, SHADE, AM, SKIP, true, true>;
-        }
-        if ((e = set_lds(kern, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)shade_grid_blocks(p)), block, lds, stream, q);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-      }
-      if (ev && ev[2] && g == p.spp - 1) (void)hipEventRecord(ev[2], stream);
-      if (grid.x > 0 && (e = launch_composite(q, grid, stream)) != hipSuccess) return e;
-      if (p.block_counters && p.counters)
-        if ((e = launch_reduce_counters(p.block_counters, (int)raymarch_grid_blocks(p), (const unsigned int*)p.pool.shade_counters, shade_grid_blocks(p), p.counters,
-                                        p.pool.ctrl, g == p.spp - 1 ? p.publish : nullptr, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e; // the frame's last generation publishes
-    }
-    return hipGetLastError();
-  }
-  else return hipErrorInvalidValue;
+  return k;
 }
-
-template <int VT, int SHADE, int AM>
-inline hipError_t launch_vsb(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
-{
-  // empty-space skipping is a separate instantiation: the non-skipping kernels stay exactly as they are
-  if (p.majorant) return launch_vsbs<VT, SHADE, AM, true>(p, stream, ev);
-  return launch_vsbs<VT, SHADE, AM, false>(p, stream, ev);
-}
-
-// the addressing mode (below) of this launch
-inline int march_addressing_mode(const RayMarchParams& p)
-{
-  int am = addressing_mode(p.vol, p.n_color, p.n_alpha);
-  if (const char* f = getenv("OVR_HIP_ADDRESSING")) am = std::max(am, atoi(f)); // diagnostic: a more general mode than needed (tests)
-  return am;
-}
-
 template <int VT, int SHADE>
-inline hipError_t launch_vs(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
+inline FrameKernels variants_of(int am, unsigned march_bits, unsigned shade_bits)
 {
-  // addressing mode: 0 = 32-bit byte offsets (volume <= 4 GiB; largest byte offset = bytes - sizeof(voxel)),
-  //                  1 = 32-bit element offsets (< 2^32 stored voxels), 2 = 64-bit z table in LDS,
-  //                  3 = 64-bit, computed (axis tables would not fit in LDS next to the queues: a dimension beyond ~8000)
-  const int am = march_addressing_mode(p);
-  if (am < 3 && (!p.vol.axis_ab || !p.vol.axis_z)) return hipErrorInvalidValue; // the layout's offset tables (launch_axis_tables)
-  if constexpr (sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad) {
-    // mode 4 = mode 0 with the 16-bit pairs read as aligned 8-byte rows (RowLoads): layouts the caches do not serve; OVR_HIP_ROW_LOADS=0|1, read when a renderer is created, forces (tests, measurements)
-    const int forced = p.row_loads - 1; // RayMarchParams::row_loads: 0 = by size, 1 = never, 2 = always
-    if (am == 0 && (forced >= 0 ? forced != 0 : p.vol.bytes > (128ull << 20))) return launch_vsb<VT, SHADE, 4>(p, stream, ev);
-  }
+  const auto all = std::make_integer_sequence<unsigned, kVariantBitsEnd>();
   switch (am) {
-  case 0: return launch_vsb<VT, SHADE, 0>(p, stream, ev);
-  case 1: return launch_vsb<VT, SHADE, 1>(p, stream, ev);
-  case 2: return launch_vsb<VT, SHADE, 2>(p, stream, ev);
-  default: return launch_vsb<VT, SHADE, 3>(p, stream, ev);
+  case 0: return variants_of<VT, SHADE, 0>(march_bits, shade_bits, all);
+  case 1: return variants_of<VT, SHADE, 1>(march_bits, shade_bits, all);
+  case 2: return variants_of<VT, SHADE, 2>(march_bits, shade_bits, all);
+  case 3: return variants_of<VT, SHADE, 3>(march_bits, shade_bits, all);
+  case 4: return variants_of<VT, SHADE, 4>(march_bits, shade_bits, all);
+  default: return FrameKernels();
   }
 }
 
-// one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~60 kernel
+// one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~160 kernel
 // variants of a type compile in parallel with the other types
 template <int VT>
-hipError_t launch_v(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
+FrameKernels frame_kernels(const LaunchPlan& pl)
 {
-  switch (p.shading) {
-  case 0: return launch_vs<VT, 0>(p, stream, ev);
-  case 1: return launch_vs<VT, 1>(p, stream, ev);
-  default: return launch_vs<VT, 2>(p, stream, ev);
+  const unsigned flags = (pl.skip ? kBitSkip : 0u) | (pl.pooled ? kBitPooled : 0u) | (pl.march.lds_staged ? kBitLdsStaged : 0u) | (pl.march.deep ? kBitDeep : 0u);
+  const unsigned march_bits = flags | (pl.march.material ? kBitMaterial : 0u) | (pl.march.clipped ? kBitClipped : 0u);
+  const unsigned shade_bits = (flags & kBitSkip) | (pl.shade.material ? kBitMaterial : 0u) | (pl.shade.clipped ? kBitClipped : 0u);
+  FrameKernels k;
+  if (pl.error) return k;
+  switch (pl.shading) {
+  case 0: k = variants_of<VT, 0>(pl.am, march_bits, shade_bits); break;
+  case 1: k = variants_of<VT, 1>(pl.am, march_bits, shade_bits); break;
+  case 2: k = variants_of<VT, 2>(pl.am, march_bits, shade_bits); break;
   }
+  if (!pl.pooled) k.shade = nullptr;
+  return k;
 }
-
 
 } // namespace ovrhip

@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "host/launch_plan.hpp"
+
 namespace ovrhip {
 
 // device-resident scalar types of the bricked volume (u32/i32/f64 inputs are converted at upload, see relayout)
@@ -114,9 +116,9 @@ struct VolumeDesc {
   const unsigned long long* axis_z;  // [nz + 2]
 };
 // entries of the per-axis tables (a = pair axis: lower members -1 ... n - 1; b, z: -1 ... n)
-__host__ __device__ inline int axis_a_entries(int na) { return na + 1; }
-__host__ __device__ inline int axis_b_entries(int nb) { return nb + 2; }
-__host__ __device__ inline int axis_z_entries(int nz) { return nz + 2; }
+__host__ __device__ constexpr int axis_a_entries(int na) { return na + 1; }
+__host__ __device__ constexpr int axis_b_entries(int nb) { return nb + 2; }
+__host__ __device__ constexpr int axis_z_entries(int nz) { return nz + 2; }
 
 struct float3_ { float x, y, z; };
 
@@ -182,7 +184,7 @@ struct RayMarchParams {
   int accumulate;
   int spp;
   int spp_index;        // pooled pipeline: the sample-per-pixel generation this launch renders
-  int row_loads;        // 16-bit layouts' aligned 8-byte pair loads (launch_vs): 0 = by the layout's size, 1 = never, 2 = always
+  int row_loads;        // 16-bit layouts' aligned 8-byte pair loads (plan_launch): 0 = by the layout's size, 1 = never, 2 = always
   float* spp_sum_rgba;  // pooled pipeline, spp > 1: per-pixel sums over the generations (W*H*4, W*H*3)
   float* spp_sum_grad;
   // camera (params.h:65-70), basis from device_impl.cpp:125-144
@@ -251,17 +253,16 @@ struct RayMarchParams {
   int clip_on;
 };
 
-// returns hipSuccess or the launch error; ev = 4 events (start, after march, after shade, end) or null
-hipError_t launch_raymarch(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev);
+// which kernel variants the frame p describes takes and what their launches need (host/launch_plan.hpp: plan_launch is the rules; this fills its facts from
+// p and reads the environment switches) - made once per frame, handed to launch_raymarch, and what the frame's statistics say was launched
+LaunchPlan plan_raymarch(const RayMarchParams& p);
+// returns hipSuccess or the launch error (hipErrorInvalidValue for a plan with `error`); ev = 4 events (start, after march, after shade, end) or null
+hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipStream_t stream, const hipEvent_t* ev);
 size_t pool_shade_blocks();
-
-// The unshaded, non-skipping f32 march at addressing mode <= 1 has an LDS-staged variant (raymarch_kernel<.., LDSB>); this is the runtime part of
-// "the launch takes it" (launch_vsbs), and raymarch_lds_staged(p) the whole condition: what launch_raymarch(p) does
-inline bool lds_staging_applies(const RayMarchParams& p) { return p.lds_staging && !p.sparse_xy && !p.clip_on; }
-bool raymarch_lds_staged(const RayMarchParams& p);
 // dynamic LDS bytes the ray-march kernel needs for this TF (0 when the TF stays in global memory)
 size_t raymarch_lds_bytes(int n_color, int n_alpha);
-// addressing mode the march / shade kernels take for a layout (0 / 1: 32-bit offsets, 2: 64-bit z table, 3: computed, no LDS tables)
+// addressing mode the march / shade kernels take for a layout (0 / 1: 32-bit offsets, 2: 64-bit z table, 3: computed, no LDS tables): launch_plan.hpp's
+// addressing_mode, the one plan_launch starts from, without the environment's override
 int volume_addressing_mode(const VolumeDesc& vd, int n_color, int n_alpha);
 // number of workgroups launch_raymarch will use (size of the block_counters workspace / kBlockCounters)
 size_t raymarch_grid_blocks(const RayMarchParams& p);

@@ -837,15 +837,15 @@ hipError_t launch_reconstruct(const ReconParams& c, hipStream_t stream)
   return hipGetLastError();
 }
 
-size_t raymarch_lds_bytes(int n_color, int n_alpha)
-{
-  // the transfer function always lives in LDS; 0 = does not fit next to the request queues (caller reports an error)
-  // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
-  const size_t need = (size_t)n_color * sizeof(float4) + (size_t)n_alpha * sizeof(float) + 32;
-  return need <= 96 * 1024 ? need : 0;
-}
+static_assert(kCounterWords == kBlockCounters && axis_a_entries(0) + axis_b_entries(0) == kAxisAbExtra && axis_z_entries(0) == kAxisZExtra
+                && axis_a_entries(7) + axis_b_entries(9) == 7 + 9 + kAxisAbExtra && axis_z_entries(5) == 5 + kAxisZExtra,
+              "launch_plan.hpp restates ovr_hip_kernels.h: the counters of a workgroup and the entries of the axis tables that stage_tables copies into LDS");
+size_t raymarch_lds_bytes(int n_color, int n_alpha) { return tf_lds_bytes(n_color, n_alpha); }
 
-int volume_addressing_mode(const VolumeDesc& vd, int n_color, int n_alpha) { return addressing_mode(vd, n_color, n_alpha); }
+int volume_addressing_mode(const VolumeDesc& vd, int n_color, int n_alpha)
+{
+  return addressing_mode(vd.bytes, (int)voxel_size(vd.type), vd.nx, vd.ny, vd.nz, n_color, n_alpha);
+}
 
 size_t raymarch_grid_blocks(const RayMarchParams& p)
 {
@@ -853,7 +853,7 @@ size_t raymarch_grid_blocks(const RayMarchParams& p)
   return p.n_schedule;
 }
 
-hipError_t launch_composite(const RayMarchParams& q, dim3 grid, hipStream_t stream)
+static hipError_t launch_composite(const RayMarchParams& q, dim3 grid, hipStream_t stream)
 {
   hipLaunchKernelGGL(composite_kernel, grid, dim3(kBlock), 0, stream, q);
   return hipGetLastError();
@@ -933,7 +933,7 @@ __global__ __launch_bounds__(256) void shade_order_kernel(const RayMarchParams P
   }
 }
 
-hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream)
+static hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream)
 {
   const unsigned int slots = q.pool.capacity / (unsigned int)kRun;
   const dim3 grid((slots + 256u * kOrderSlots - 1u) / (256u * kOrderSlots));
@@ -947,32 +947,112 @@ hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, const unsigned int* shade_partials, int n_shade_blocks,
-                                  unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream,
-                                  unsigned int* conv_asked)
+constexpr int kReduceBlocks = 64;
+static hipError_t launch_reduce_counters(const unsigned int* partials, int n_blocks, const unsigned int* shade_partials, int n_shade_blocks,
+                                         unsigned long long* counters, unsigned int* pool_ctrl, unsigned long long* publish, unsigned int* done, hipStream_t stream,
+                                         unsigned int* conv_asked)
 {
   hipLaunchKernelGGL(reduce_counters_kernel, dim3(kReduceBlocks), dim3(256), 0, stream, partials, n_blocks, shade_partials, n_shade_blocks, counters, pool_ctrl,
                      done ? publish : nullptr, done, conv_asked);
   return hipGetLastError();
 }
 
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template hipError_t launch_v<E>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template FrameKernels frame_kernels<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 #undef OVR_X
 
-bool raymarch_lds_staged(const RayMarchParams& p)
-{
-  return p.vol.type == VOX_F32 && p.shading == 0 && !p.majorant && march_addressing_mode(p) <= 1 && lds_staging_applies(p); // launch_vsbs
-}
-
 size_t pool_shade_blocks() { return kShadeBlocks; }
 
-hipError_t launch_raymarch(const RayMarchParams& p, hipStream_t stream, const hipEvent_t* ev)
+// the facts of a frame's launch, and the environment switches: OVR_HIP_ADDRESSING=k is read with every plan (a more general addressing mode than needed:
+// tests change it between renderers), OVR_HIP_DEEP=0|1 and OVR_HIP_SHADE_BLOCKS=n once per process (measurements)
+LaunchPlan plan_raymarch(const RayMarchParams& p)
+{
+  static const int deep = getenv("OVR_HIP_DEEP") ? atoi(getenv("OVR_HIP_DEEP")) : -1;
+  static const int shade_blocks = getenv("OVR_HIP_SHADE_BLOCKS") ? atoi(getenv("OVR_HIP_SHADE_BLOCKS")) : 0;
+  LaunchOverrides o;
+  if (const char* a = getenv("OVR_HIP_ADDRESSING")) o.addressing = atoi(a);
+  o.deep = deep;
+  o.shade_blocks = shade_blocks;
+  LaunchFacts f;
+  f.elem_bytes = (int)voxel_size(p.vol.type);
+  f.quad = p.vol.type >= 0 && p.vol.type < kVoxelTypeCount && kVoxelTypes[p.vol.type].layout == LAYOUT_QUAD;
+  f.f32_general = p.vol.type == VOX_F32;
+  f.nx = p.vol.nx; f.ny = p.vol.ny; f.nz = p.vol.nz;
+  f.stored_bytes = p.vol.bytes;
+  f.tables = p.vol.axis_ab && p.vol.axis_z;
+  f.n_color = p.n_color; f.n_alpha = p.n_alpha; f.shading = p.shading;
+  f.pool = p.pool.reqs != nullptr; f.skipping = p.majorant != nullptr; f.sparse = p.sparse_xy != nullptr;
+  f.sparse_hint_pixels = p.sparse_hint_pixels;
+  f.world = p.world;
+  f.n_blocks_owned = p.n_blocks_owned; f.n_schedule = p.n_schedule; f.schedule = p.schedule != nullptr;
+  f.clip_on = p.clip_on != 0; f.lds_staging = p.lds_staging != 0;
+  f.row_loads = p.row_loads; f.shade_blocks = p.shade_blocks;
+  f.reference_material = reference_material(p); f.shade_order = p.pool.order != nullptr;
+  return plan_launch(f, o);
+}
+
+// a launch needing more than 64 KiB of LDS raises the kernel's limit first (per launch: the attribute belongs to the current device's copy of the kernel)
+static hipError_t launch_variant(FrameKernel kern, dim3 grid, size_t lds, hipStream_t stream, const RayMarchParams& prm)
+{
+  if (lds > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  if (grid.x > 0) hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, stream, prm);
+  return hipSuccess;
+}
+
+// the frame's kernels between its first and last event: in place march -> reduction; pooled, once per sample-per-pixel generation,
+// march -> (order) -> shade -> composite -> reduction
+static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& plan, const FrameKernels& k, hipStream_t stream, const hipEvent_t* ev)
+{
+  const dim3 grid((unsigned)raymarch_grid_blocks(p)); // (no march or composite workgroup when no block of this renderer's has a hit)
+  hipError_t e;
+  if (!plan.pooled) {
+    RayMarchParams q = p;
+    if (plan.march.lds_staged) q.lds_brick_offset = plan.lds_brick_offset; // the bricks follow the tables and the TF
+    if ((e = launch_variant(k.march, grid, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev && ev[1] && ev[2]) { (void)hipEventRecord(ev[1], stream); (void)hipEventRecord(ev[2], stream); }
+    if (p.block_counters && p.counters) {
+      if (!p.publish || p.zero_first)
+        if ((e = hipMemsetAsync(p.counters, 0, 8 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+      if ((e = launch_reduce_counters(p.block_counters, (int)grid.x, nullptr, 0, p.counters, nullptr, p.publish, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e;
+    }
+    return hipGetLastError();
+  }
+  // (the last frame's final reduction left the control words and the counters zeroed - RayMarchParams::publish)
+  const bool self_cleaning = p.publish && p.block_counters && p.counters && !p.zero_first;
+  if (!self_cleaning) {
+    if ((e = hipMemsetAsync(p.pool.ctrl, 0, (size_t)kPoolCtrlWords * sizeof(unsigned int), stream)) != hipSuccess) return e;
+    if (p.block_counters && p.counters)
+      if ((e = hipMemsetAsync(p.counters, 0, 8 * sizeof(unsigned long long), stream)) != hipSuccess) return e;
+  }
+  RayMarchParams q = p;
+  if (!plan.shade_order) q.pool.order = nullptr;
+  for (int g = 0; g < p.spp; ++g) {
+    q.spp_index = g;
+    if (g > 0 && (e = hipMemsetAsync(p.pool.ctrl, 0, (size_t)32 * (kPoolSubs + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e; // all but the frame's maximum
+    if ((e = launch_variant(k.march, grid, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev && ev[1] && g == p.spp - 1) (void)hipEventRecord(ev[1], stream);
+    if (q.pool.order && (e = launch_shade_order(q, stream)) != hipSuccess) return e; // runs sorted by light beam (PoolDesc)
+    if ((e = launch_variant(k.shade, dim3((unsigned)plan.shade_grid_blocks), plan.shade_lds_bytes, stream, q)) != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (ev && ev[2] && g == p.spp - 1) (void)hipEventRecord(ev[2], stream);
+    if (grid.x > 0 && (e = launch_composite(q, grid, stream)) != hipSuccess) return e;
+    if (p.block_counters && p.counters)
+      if ((e = launch_reduce_counters(p.block_counters, (int)grid.x, (const unsigned int*)p.pool.shade_counters, plan.shade_grid_blocks, p.counters, p.pool.ctrl,
+                                      g == p.spp - 1 ? p.publish : nullptr, p.reduce_done, stream, p.conv_asked)) != hipSuccess) return e; // the frame's last generation publishes
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipStream_t stream, const hipEvent_t* ev)
 {
   // ev (optional): ev[0] before the first kernel, ev[1] after the march, ev[2] after the shade kernel (both may be null: no per-phase times), ev[3] at the end
   if (ev) (void)hipEventRecord(ev[0], stream);
-  hipError_t e = hipErrorInvalidValue;
-  dispatch_voxel_type(p.vol.type, [&](auto vt) { e = launch_v<decltype(vt)::value>(p, stream, ev); });
+  FrameKernels k;
+  dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
+  const hipError_t e = k.march && (k.shade || !plan.pooled) ? launch_sequence(p, plan, k, stream, ev) : hipErrorInvalidValue;
   if (ev) (void)hipEventRecord(ev[3], stream);
   return e;
 }
@@ -1906,7 +1986,7 @@ __global__ void shade_floats_kernel(const RayMarchParams P, const float* normal_
 hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n, hipStream_t stream)
 {
   if (n <= 0) return hipSuccess;
-  auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as launch_vsbs picks the frame's kernels
+  auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as plan_launch picks the frame's kernels
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, normal_w, pos, shadow, out, (long long)n);
   return hipGetLastError();
 }
@@ -1930,7 +2010,7 @@ __global__ void clip_intervals_kernel(const RayMarchParams P, const float* org, 
 hipError_t launch_clip_intervals(const RayMarchParams& p, const float* org, const float* dir, float* t0t1hit, int64_t n, hipStream_t stream)
 {
   if (n <= 0) return hipSuccess;
-  auto kern = p.clip_on ? clip_intervals_kernel<true> : clip_intervals_kernel<false>; // as launch_vsbs picks the frame's kernels
+  auto kern = p.clip_on ? clip_intervals_kernel<true> : clip_intervals_kernel<false>; // as plan_launch picks the frame's kernels
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, org, dir, t0t1hit, (long long)n);
   return hipGetLastError();
 }

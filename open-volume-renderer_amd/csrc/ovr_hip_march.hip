@@ -7,5 +7,5 @@
 #endif
 
 namespace ovrhip {
-template hipError_t launch_v<OVR_MARCH_VT>(const RayMarchParams&, hipStream_t, const hipEvent_t*);
+template FrameKernels frame_kernels<OVR_MARCH_VT>(const LaunchPlan&);
 }

@@ -31,16 +31,20 @@ def read(lib, every=False):
             if "gfx950" not in f:
                 continue
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=tmp, capture_output=True, text=True, check=True).stdout
-            name = None
-            for line in notes.splitlines():
-                line = line.strip()
-                if line.startswith(".name:"):
-                    name = line.split(":", 1)[1].strip()
-                    out[name] = {}
-                elif name:
+            # one list item of amdhsa.kernels per kernel, its keys in alphabetical order: .group_segment_fixed_size stands BEFORE .name
+            for item in re.split(r"^  - (?=\.)", notes, flags=re.M)[1:]:
+                name, fields = None, {}
+                for line in item.splitlines():
+                    if not line.startswith("    ."):
+                        line = "    " + line if line.startswith(".") else ""  # (the item's first key follows its dash)
+                    line = line[4:]
+                    if line.startswith(".name:"):
+                        name = line.split(":", 1)[1].strip()
                     for k in FIELDS:
                         if line.startswith(k + ":"):
-                            out[name][k] = int(line.split(":")[1])
+                            fields[k] = int(line.split(":")[1])
+                if name:
+                    out[name] = fields
     return {n: k for n, k in out.items() if every or "raymarch_kernel" in n or "shade_pool_kernel" in n}
 
 
@@ -73,11 +77,16 @@ def main():
     ap.add_argument("--removed", type=int, default=0)
     a = ap.parse_args()
     mine = {key(n): k for n, k in read(a.lib, a.all).items()}
+    # (the parser goes by the layout of llvm-readelf's output: a library that yields no kernel, or kernels without registers, was not understood)
+    if not mine or any(".vgpr_count" not in k for k in mine.values()):
+        raise SystemExit(f"{a.lib}: no kernel metadata understood ({len(mine)} names)")
     if not a.against:
         for n in sorted(mine):
             print(n, " ".join(f"{f[1:]}={mine[n].get(f, 0)}" for f in FIELDS))
         return 0
     parent = {key(n): k for n, k in read(a.against, a.all).items()}
+    if not parent or any(".vgpr_count" not in k for k in parent.values()):
+        raise SystemExit(f"{a.against}: no kernel metadata understood ({len(parent)} names)")
     removed = sorted(n for n in parent if n not in mine) if a.all else []
     changed = [n for n in parent if n not in removed and (n not in mine or mine[n] != parent[n])]
     new = sorted(set(mine) - set(parent))

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""launch_states.py - one 96 x 64 frame of a 24^3 volume per named state, one state per kernel variant rule of csrc/host/launch_plan.hpp (24^3 spans
+two macrocells per axis: the skipping kernels have work).  Every variant renders the same frame, so what a state LAUNCHES is only visible from outside:
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/launch_states.py
+
+once with this tree's library and once with another build's (OVR_HIP_LIBRARY=...), then `python tools/launch_states.py --compare DIR_A DIR_B`: the two
+traces must agree line for line, in dispatch order, on kernel name, grid size, workgroup size and LDS size.  Prints nothing but the state names."""
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+INF = float("inf")
+N, SIZE = 24, (96, 64)
+
+# name -> (environment, settings): dtype, shading, pipeline (1 in place, 2 pooled), skip, material, clip, spp, shard, sparse, lds, layout
+STATES = [
+    ("unshaded_f32_lds_staged", {}, dict(shading=0, lds=True)),
+    ("unshaded_f32_plain", {}, dict(shading=0, lds=False)),
+    ("unshaded_f32_clipped", {}, dict(shading=0, lds=True, clip=True)),
+]
+for _s in (1, 2):
+    STATES += [
+        (f"shading{_s}_inplace_reference_material", {}, dict(shading=_s, pipeline=1)),
+        (f"shading{_s}_inplace_other_material", {}, dict(shading=_s, pipeline=1, material=True)),
+        (f"shading{_s}_inplace_clipped", {}, dict(shading=_s, pipeline=1, clip=True)),
+        (f"shading{_s}_pooled", {}, dict(shading=_s, pipeline=2)),
+        (f"shading{_s}_pooled_skipping", {}, dict(shading=_s, pipeline=2, skip=True)),
+        (f"shading{_s}_pooled_other_material", {}, dict(shading=_s, pipeline=2, material=True)),
+        (f"shading{_s}_pooled_clipped", {}, dict(shading=_s, pipeline=2, clip=True)),
+        (f"shading{_s}_pooled_skipping_clipped", {}, dict(shading=_s, pipeline=2, skip=True, clip=True)),
+        (f"shading{_s}_pooled_spp2", {}, dict(shading=_s, pipeline=2, spp=2)),
+    ]
+STATES += [
+    ("shard_rank0_of_2_pooled", {}, dict(shading=2, pipeline=2, shard=(0, 2))),
+    ("sparse_after_sparse", {}, dict(shading=2, pipeline=2, sparse=True)),
+    ("addressing1", {"OVR_HIP_ADDRESSING": "1"}, dict(shading=2, pipeline=2)),
+    ("addressing2", {"OVR_HIP_ADDRESSING": "2"}, dict(shading=2, pipeline=2)),
+    ("addressing3", {"OVR_HIP_ADDRESSING": "3"}, dict(shading=2, pipeline=2)),
+    ("addressing1_unshaded_lds_staged", {"OVR_HIP_ADDRESSING": "1"}, dict(shading=0, lds=True)),
+    ("addressing2_unshaded", {"OVR_HIP_ADDRESSING": "2"}, dict(shading=0, lds=True)),
+    ("u16_general", {}, dict(dtype="uint16", shading=2, pipeline=2)),
+    ("u8_general", {}, dict(dtype="uint8", shading=2, pipeline=2)),
+    ("u16_row_loads", {"OVR_HIP_ROW_LOADS": "1"}, dict(dtype="uint16", shading=2, pipeline=2)),
+    ("u16_row_loads_addressing1", {"OVR_HIP_ROW_LOADS": "1", "OVR_HIP_ADDRESSING": "1"}, dict(dtype="uint16", shading=2, pipeline=2)),
+    ("u16_row_loads_shard", {"OVR_HIP_ROW_LOADS": "1"}, dict(dtype="uint16", shading=2, pipeline=2, shard=(0, 2))),
+    ("f32_thin_layout", {}, dict(shading=2, pipeline=2, layout=1)),
+    ("u16_quad_layout", {}, dict(dtype="uint16", shading=2, pipeline=1, layout=3)),
+]
+ENV_KEYS = ("OVR_HIP_ADDRESSING", "OVR_HIP_ROW_LOADS")
+
+
+def run_state(ovr, np, name, env, s):
+    for k in ENV_KEYS:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    vol = ovr.synth.make_volume(N, dtype=np.dtype(s.get("dtype", "float32")))
+    colors, alphas, vr = ovr.synth.make_tfn("sparse", 256)
+    ren = ovr.create_renderer("hip", 0)
+    ren.set_fbsize(SIZE)
+    ren.set_frame_accumulation(True)
+    ren.set_transfer_function(colors, alphas, vr)
+    ren.set_shading(s["shading"])
+    ren.set_shading_pipeline(s.get("pipeline", 0))
+    ren.set_empty_space_skipping(bool(s.get("skip", False)))
+    ren.set_lds_staging(bool(s.get("lds", False)))
+    ren.set_sample_per_pixel(s.get("spp", 1))
+    if "layout" in s:
+        ren.set_volume_layouts(2)
+        ren.set_layout_choice(s["layout"])
+    else:
+        ren.set_volume_layouts(0)
+        ren.set_layout_choice(0)
+    if s.get("material"):
+        ren.set_material(0.3, 0.6, 0.4, 12.0)
+    if s.get("sparse"):
+        ren.set_noise_tile(ovr.synth.make_noise_tile(16))
+        ren.set_focus((0.5, 0.45), 0.35, 0.15)
+        ren.set_sparse_sampling(True)
+    if s.get("shard"):
+        ren.set_image_shard(*s["shard"])
+    ren.init(ovr.Scene(volume=vol, transfer_function=None), ovr.Camera(*ovr.synth.make_camera("oblique", N)))
+    if s.get("clip"):
+        ren.set_clip_box((-INF, -INF, -INF), (N / 2.0, INF, INF))
+    ren.commit()
+    for _ in range(2 if s.get("sparse") else 1):
+        ren.render()
+    ren.close()
+    print(name, flush=True)
+
+
+def trace_rows(directory):
+    files = sorted(glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True))
+    if len(files) != 1:
+        raise SystemExit(f"{directory}: expected one *kernel_trace.csv, found {len(files)}")
+    with open(files[0]) as f:
+        rows = sorted(csv.DictReader(f), key=lambda r: int(r["Dispatch_Id"]))
+    return [(r["Kernel_Name"], r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"], r["Workgroup_Size_X"], r["Workgroup_Size_Y"], r["Workgroup_Size_Z"],
+             r["LDS_Block_Size"] if "LDS_Block_Size" in r else r["Group_Segment_Size"]) for r in rows]
+
+
+def compare(a, b):
+    ra, rb = trace_rows(a), trace_rows(b)
+    bad = [(i, x, y) for i, (x, y) in enumerate(zip(ra, rb)) if x != y]
+    for i, x, y in bad[:10]:
+        print(f"dispatch {i}:\n  {x}\n  {y}")
+    march = sum("raymarch_kernel" in r[0] for r in ra)
+    print(f"{len(ra)} / {len(rb)} dispatches ({march} of raymarch_kernel, {len(set(r[0] for r in ra))} distinct kernels), {len(bad)} differ")
+    return 0 if ra and len(ra) == len(rb) and not bad else 1
+
+
+def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        return compare(sys.argv[2], sys.argv[3])
+    os.environ["OVR_HIP_TUNE"] = "0"  # the rules alone: nothing a state launches depends on a measured time
+    import numpy as np
+    import ovr_amd as ovr
+    for name, env, s in STATES:
+        run_state(ovr, np, name, env, s)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -78,6 +78,22 @@ int free_reconstruction(ovr_hip_renderer* r)
   return 0;
 }
 
+// everything the shadow cache holds on the device (the counters of ovr_hip_get_shadow_cache stay)
+void free_shadow_cache(ovr_hip_renderer* r)
+{
+  ShadowCacheState& c = r->shadow_cache;
+  if (c.d_built) (void)hipFree(c.d_built);
+  if (c.d_supplied) (void)hipFree(c.d_supplied);
+  if (c.d_iterations) (void)hipFree(c.d_iterations);
+  for (int i = 0; i < 2; ++i) if (c.ev[i]) (void)hipEventDestroy(c.ev[i]);
+  c.d_built = c.d_supplied = nullptr;
+  c.d_iterations = nullptr;
+  c.ev[0] = c.ev[1] = nullptr;
+  c.built_cap = 0;
+  c.built_valid = false;
+  for (int k = 0; k < 3; ++k) c.built_dims[k] = c.supplied_dims[k] = 0;
+}
+
 int ensure_reconstruction(ovr_hip_renderer* r)
 {
   const size_t n = std::max<size_t>(r->fb_pixels, 1);

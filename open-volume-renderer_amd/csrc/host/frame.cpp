@@ -453,6 +453,124 @@ static int prepare_pool(ovr_hip_renderer* r, const FrameSetup& f)
   return 0;
 }
 
+// ---- shadow cache (ovr_hip_set_shadow_cache)
+int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3])
+{
+  const int n[3] = { r->vd.nx, r->vd.ny, r->vd.nz };
+  long long nodes = 1;
+  for (int k = 0; k < 3; ++k) {
+    const long long nk = policy::shadow_cache_nodes(n[k], std::max(cell, 1));
+    nodes = nodes > 0x7fffffffll / nk ? 0x80000000ll : nodes * nk;
+    dims[k] = (int)std::min<long long>(nk, 0x7fffffffll);
+  }
+  if (nodes > 0x7fffffffll) return fail(OVR_HIP_EINVAL, "[hip] shadow cache: a lattice of more than 2^31 - 1 nodes (take a larger cell)");
+  return 0;
+}
+
+// what the shadow march reads beyond the committed volume transform, light and clip box, as a frame sets it: the sampling rate's constants, the transfer
+// function's tables and the GENERAL layout - always resident, and what ovr_hip_update_volume rewrites
+void fill_shadow_params(ovr_hip_renderer* r, RayMarchParams& q)
+{
+  q.step = 1.f / r->rate.current;
+  q.base = 1.f;
+  q.shadow_stride = (q.step * 10.f) * q.step;
+  q.tf_color = r->d_tf_color; q.tf_alpha = r->d_tf_alpha;
+  q.n_color = r->n_color; q.n_alpha = r->n_alpha;
+  const float vs = q.vol.value_scale, vm = q.vol.value_min_clamp;
+  q.vol = r->vd_replica[LAYOUT_GENERAL];
+  q.vol.value_scale = vs;
+  q.vol.value_min_clamp = vm;
+  q.grad = nullptr;
+}
+
+// nodes' positions: origin + u * (spacing * extent), the extent of update_volume_params
+static void shadow_lattice_frame(const ovr_hip_renderer* r, ShadowBuildArgs& a)
+{
+  const bool vertex = r->grid_convention.current == OVR_HIP_GRID_VERTEX_CENTRED;
+  const int n[3] = { r->vd.nx, r->vd.ny, r->vd.nz };
+  for (int k = 0; k < 3; ++k) {
+    const float ext = vertex ? (float)(n[k] - 1) : (float)n[k];
+    a.sc[k] = r->spacing[k] * ext;
+    a.origin[k] = r->origin[k];
+  }
+}
+
+// binds the lattice the committed mode reads into q (null in mode MARCHED); mode CACHED builds it first when it is stale.  The build runs on st in front
+// of whatever follows and is waited for: its time and iterations are the build's own (ovr_hip_get_shadow_cache), never part of a frame's kernel_ms
+int ensure_shadow_cache(ovr_hip_renderer* r, RayMarchParams& q, hipStream_t st)
+{
+  ShadowCacheState& c = r->shadow_cache;
+  const ShadowP& sp = r->shadow.current;
+  q.shadow_lattice = nullptr;
+  q.shadow_n1[0] = q.shadow_n1[1] = q.shadow_n1[2] = 1;
+  if (sp.mode == OVR_HIP_SHADOWS_MARCHED) return 0;
+  if (sp.mode == OVR_HIP_SHADOWS_SUPPLIED) {
+    if (!c.d_supplied) return fail(OVR_HIP_ESTATE, "[hip] shadow cache: mode SUPPLIED without values (ovr_hip_set_shadow_cache_values)");
+    q.shadow_lattice = c.d_supplied;
+    for (int k = 0; k < 3; ++k) q.shadow_n1[k] = c.supplied_dims[k] - 1;
+    return 0;
+  }
+  if (!c.built_valid) {
+    if (!r->have_volume || !r->have_tfn) return fail(OVR_HIP_ESTATE, "[hip] shadow cache: the build needs a volume and a transfer function");
+    int dims[3];
+    if (int e = shadow_lattice_dims(r, sp.cell, dims)) return e;
+    const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+    if (nodes > c.built_cap) { // the new buffer first: a failed allocation leaves the old one in place
+      float* d = nullptr;
+      if (hipMalloc((void**)&d, nodes * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OVR_HIP_EDEVICE, "[hip] shadow cache: the lattice of " + std::to_string(nodes) + " nodes could not be allocated");
+      }
+      if (c.d_built) HIP_TRY(hipFree(c.d_built));
+      c.d_built = d;
+      c.built_cap = nodes;
+    }
+    if (!c.d_iterations) HIP_TRY(hipMalloc((void**)&c.d_iterations, sizeof(unsigned long long)));
+    for (int i = 0; i < 2; ++i)
+      if (!c.ev[i]) HIP_TRY(hipEventCreate(&c.ev[i]));
+    RayMarchParams b = r->P;
+    fill_shadow_params(r, b);
+    ShadowBuildArgs a{};
+    a.out = c.d_built;
+    a.n = (long long)nodes;
+    a.nx = dims[0]; a.ny = dims[1]; a.nz = dims[2];
+    shadow_lattice_frame(r, a);
+    a.iterations = c.d_iterations;
+    if (r->tf_copy_pending) { HIP_TRY(hipStreamWaitEvent(st, r->ev_tf, 0)); r->tf_copy_pending = false; }
+    HIP_TRY(hipMemsetAsync(c.d_iterations, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipEventRecord(c.ev[0], st));
+    HIP_TRY(launch_shadow_cache(b, a, st));
+    HIP_TRY(hipEventRecord(c.ev[1], st));
+    unsigned long long it = 0;
+    HIP_TRY(hipMemcpyAsync(&it, c.d_iterations, sizeof(it), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    for (int k = 0; k < 3; ++k) c.built_dims[k] = dims[k];
+    c.built_valid = true;
+    c.builds++;
+    c.build_samples = it;
+    c.build_ms = ms;
+  }
+  q.shadow_lattice = c.d_built;
+  for (int k = 0; k < 3; ++k) q.shadow_n1[k] = c.built_dims[k] - 1;
+  return 0;
+}
+
+// the nodes' world positions of an nx x ny x nz lattice over the resident volume, as the build kernel forms them (ovr_hip_get_shadow_cache_values)
+int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st)
+{
+  RayMarchParams b = r->P;
+  fill_shadow_params(r, b);
+  ShadowBuildArgs a{};
+  a.pos_out = d_pos;
+  a.n = (long long)dims[0] * dims[1] * dims[2];
+  a.nx = dims[0]; a.ny = dims[1]; a.nz = dims[2];
+  shadow_lattice_frame(r, a);
+  HIP_TRY(launch_shadow_cache(b, a, st));
+  return 0;
+}
+
 // Impl::render up to and including the launch (device_impl.cpp:199-262); no host synchronisation
 int enqueue_frame(ovr_hip_renderer* r)
 {
@@ -485,6 +603,10 @@ int enqueue_frame(ovr_hip_renderer* r)
   choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
+  // the shadow cache: a frame with full shading reads the lattice of a mode other than MARCHED (built here, in front of the frame, when it is stale)
+  r->P.shadow_lattice = nullptr;
+  if (r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
+    if (int e = ensure_shadow_cache(r, r->P, st)) return e;
   f.conv_on = r->convergence.current.mode != OVR_HIP_CONVERGENCE_OFF && f.accumulate && !f.sparse;
   r->P.accum_half = nullptr; // (before launch_clear_blocks: H is cleared with A)
   r->P.conv_asked = nullptr;

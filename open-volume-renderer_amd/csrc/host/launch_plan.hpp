@@ -32,11 +32,15 @@ constexpr unsigned int kDeepMaxBlocks = 10000;
 constexpr int kCounterWords = 8;
 constexpr int kAxisAbExtra = 3, kAxisZExtra = 2; // table entries beyond nx + ny (a: n + 1, b: n + 2, whichever of x / y is the pair axis) and beyond nz
 
-// ---- which instantiations exist: raymarch_kernel<VT, shade, am, pooled, skip, lds_staged, deep, material, clipped> (f32_general: VT is the general f32
-// layout) and shade_pool_kernel<VT, shade, am, skip, material, clipped>; am == 4 only for the layouts row_load_layout names
+// ---- which instantiations exist: raymarch_kernel<VT, shade, am, pooled, skip, lds_staged, deep, material, clipped, cached> (f32_general: VT is the general f32
+// layout) and shade_pool_kernel<VT, shade, am, skip, material, clipped, cached>; am == 4 only for the layouts row_load_layout names.
+// cached (the shadow cache): the shadow term is one tap into a lattice instead of a march - on the kernels that shade without a
+// shadow march (shade 1), riding on the material variant like the clipped ones; the pooled march does not shade and has no cached twin
 constexpr bool row_load_layout(int elem_bytes, bool quad) { return elem_bytes <= 2 && !quad; } // the 16-bit pairs (and 8-bit ones) as aligned 8-byte rows
-constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, bool lds_staged, bool deep, bool material, bool clipped, bool f32_general)
+constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, bool lds_staged, bool deep, bool material, bool clipped, bool f32_general,
+                                    bool cached = false)
 {
+  if (cached && !(shade == 1 && material && !pooled)) return false;           // where the march shades, without a shadow march, on the material variant
   if (shade < 0 || shade > 2 || am < 0 || am > 4 || (f32_general && am == 4)) return false;
   if (pooled && shade == 0) return false;                                      // nothing to shade: the in-place march is the only pipeline
   if (lds_staged) return f32_general && shade == 0 && !skip && am <= 1 && !deep && !material && !clipped; // the unshaded in-place march only
@@ -45,9 +49,10 @@ constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, b
   if (clipped && !pooled && material != (shade != 0)) return false;            // the clipped in-place march rides on the material variant where it shades
   return true;
 }
-constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material, bool clipped)
+constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material, bool clipped, bool cached = false)
 {
   if (shade < 1 || shade > 2 || am < 0 || am > 4) return false;
+  if (cached && !(shade == 1 && material)) return false;
   (void)skip;
   return !clipped || (shade == 2 && material); // clipped where the shade kernel marches shadow rays, on the material variant
 }
@@ -97,6 +102,7 @@ struct LaunchFacts {
   int row_loads = 0;                  // 0 = by the layout's size, 1 = never, 2 = always
   int shade_blocks = 0;               // 0 = the default
   bool reference_material = true, shade_order = false; // the material is the reference's; the pool has an order buffer
+  bool shadow_cache = false;          // a valid shadow lattice is bound (RayMarchParams::shadow_lattice): a frame with full shading reads it
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -108,6 +114,7 @@ struct LaunchPlan {
   struct March { bool lds_staged = false, deep = false, material = false, clipped = false; } march;
   struct Shade { bool material = false, clipped = false; } shade;
   bool shade_order = false;           // the shade kernel meets the runs sorted by light beam (PoolDesc::order)
+  bool cached = false;                // the kernels that shade take the shadow term from the lattice: SHADE 1, material, no box test while shading
   size_t march_lds_bytes = 0, shade_lds_bytes = 0;
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
@@ -129,6 +136,10 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 {
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  // the shadow cache: full shading without the shadow march is the gradient-shaded kernel plus one tap - everything below follows from SHADE 1 (no clipped
+  // shade kernel: the clip is baked into the lattice; no shade order: there are no light beams to sort by) but the material flag, which the cached variants ride on
+  pl.cached = pl.shading == 2 && f.shadow_cache;
+  if (pl.cached) pl.shading = 1;
   const int sh = pl.shading;
   // addressing: the layout's mode, a more general one on request, then the row loads on mode 0
   int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
@@ -152,7 +163,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
     }
     else {
       pl.march.clipped = f.clip_on;
-      pl.march.material = sh != 0 && (f.clip_on || !f.reference_material);
+      pl.march.material = sh != 0 && (f.clip_on || !f.reference_material || pl.cached);
     }
     return pl;
   }
@@ -160,7 +171,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   pl.march.clipped = f.clip_on;
   pl.march.deep = !f.skipping && (am <= 1 || am == 4) && !f.clip_on && deep_rounds_pay(f, o); // a small image shard: the longest ray's chain of rounds is the floor
   pl.shade.clipped = sh == 2 && f.clip_on; // shadow rays are clipped too; without them the shade kernel never tests the box
-  pl.shade.material = pl.shade.clipped || !f.reference_material;
+  pl.shade.material = pl.shade.clipped || !f.reference_material || pl.cached;
   pl.shade_order = sh == 2 && f.shade_order; // no shadow rays: creation order (its tickets' batches, profiles/r02_notes.md section 11)
   pl.shade_lds_bytes = std::max<size_t>(tf + tables, 64);
   const int blocks = o.shade_blocks > 0 ? o.shade_blocks : f.shade_blocks;

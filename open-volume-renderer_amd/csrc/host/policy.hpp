@@ -306,6 +306,25 @@ inline int shade_blocks(bool use_skip, size_t prev_pool_chunks)
   return (!use_skip && prev_pool_chunks > 0 && prev_pool_chunks <= (size_t)64 * 1024 * 4) ? 768 : 1024;
 }
 
+// The shadow cache (ovr_hip_set_shadow_cache): a built lattice holds the shadow march's values at its nodes, so it is stale after a
+// change of anything that march reads or the lattice is laid out by - and of nothing else: the shadow term of a directional light is view-independent.
+// What changed since the lattice was built, as the commit and the volume calls see it:
+struct ShadowCacheChange {
+  // stale after any of these
+  bool volume = false, volume_update = false, transfer_function = false, sampling_rate = false, light_direction = false, clip_box = false, grid_convention = false,
+       cell = false, mode = false;
+  // not after these
+  bool camera = false, framebuffer = false, spp = false, jitter = false, material = false, light_intensity = false, accumulation = false, sparse = false,
+       convergence = false, reconstruction = false, layout_choice = false, pipeline = false, skipping = false;
+};
+inline bool shadow_cache_stale(const ShadowCacheChange& c)
+{
+  return c.volume || c.volume_update || c.transfer_function || c.sampling_rate || c.light_direction || c.clip_box || c.grid_convention || c.cell || c.mode;
+}
+// nodes per axis of the lattice over dim voxels at a cell size >= 1: ceil(dim / cell) + 1
+inline long long shadow_cache_nodes(int dim, int cell) { return ((long long)dim + cell - 1) / cell + 1; }
+constexpr int kShadowCacheDefaultCell = 4; // a guess: unmeasured until tools/shadow_cache_bench.py has run
+
 // a pixel's ray is known to the schedule kernels when it has one sample and no jitter: blocks without a hit are found exactly (1); with
 // several samples or jitter its rays lie within half a pixel of the centre: blocks whose widened cone misses the box are found (2);
 // 0 = every block is launched

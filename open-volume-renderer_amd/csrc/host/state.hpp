@@ -72,6 +72,22 @@ struct MaterialP { float ambient = 0.5f, diffuse = 0.5f, specular = 0.f, shinine
 // ovr_hip_set_clip_box: the world box as given (-inf / +inf: open on that side).  The object box the kernels test is derived from it and the volume
 // (apply_clip_box)
 struct ClipP { int enabled = 0; float lower[3] = { -INFINITY, -INFINITY, -INFINITY }, upper[3] = { INFINITY, INFINITY, INFINITY }; };
+// ovr_hip_set_shadow_cache: the mode and the cell size in voxels (0 resolved to the default by the setter)
+struct ShadowP { int mode = OVR_HIP_SHADOWS_MARCHED; int cell = ovrhip::policy::kShadowCacheDefaultCell; };
+
+// ---- shadow cache (ovr_hip_set_shadow_cache).  No buffer exists until a mode other than MARCHED needs one.
+struct ShadowCacheState {
+  float* d_built = nullptr;          // mode CACHED: the lattice of the shadow march's values
+  size_t built_cap = 0;              // nodes d_built holds
+  int built_dims[3] = { 0, 0, 0 };
+  bool built_valid = false;          // d_built is current (policy::shadow_cache_stale clears it)
+  float* d_supplied = nullptr;       // mode SUPPLIED: the caller's lattice (ovr_hip_set_shadow_cache_values)
+  int supplied_dims[3] = { 0, 0, 0 };
+  unsigned long long* d_iterations = nullptr; // the build's iteration counter
+  hipEvent_t ev[2] = { nullptr, nullptr };
+  uint64_t builds = 0, build_samples = 0;
+  double build_ms = 0.0;
+};
 
 // the frame words on the device (ovr_hip_renderer::d_counters): 8 counters, the pool's control words from byte 128, the reduction's ticket word behind them
 constexpr size_t kFrameWordsBytes = 128 + (size_t)ovrhip::kPoolCtrlWords * sizeof(unsigned int) + 128;
@@ -190,6 +206,7 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (apply_lighting)
   Queued<ovrhip::host::MaterialP> material;
   Queued<ovrhip::host::ClipP> clip;          // the world box: the object box follows the volume (apply_clip_box)
+  Queued<ovrhip::host::ShadowP> shadow;      // the shadow cache's mode and cell size
   Queued<ovrhip::host::ConvP> convergence;
   Queued<int> reconstruction;
   Queued<int> layouts;      // ovr_hip_set_volume_layouts: which replicas the next ovr_hip_set_volume plans (2: builds at once)
@@ -274,6 +291,7 @@ struct ovr_hip_renderer {
 
   ovrhip::host::ConvergenceState conv;
   ovrhip::host::ReconstructionState recon;
+  ovrhip::host::ShadowCacheState shadow_cache;
 
   // sparse sampling
   float* d_noise = nullptr;
@@ -340,6 +358,7 @@ int free_framebuffers(ovr_hip_renderer* r);
 int resize_framebuffers(ovr_hip_renderer* r, int w, int h);
 int ensure_pool(ovr_hip_renderer* r, size_t chunks);
 int ensure_sparse_buffers(ovr_hip_renderer* r);
+void free_shadow_cache(ovr_hip_renderer* r);
 
 // volume.cpp: what a commit or an upload derives from camera, volume, transfer function and light; the replicas
 void update_camera(ovr_hip_renderer* r);
@@ -359,6 +378,12 @@ ovrhip::SparseMaskParams make_mask_params(ovr_hip_renderer* r, int frame_index, 
 int refresh_mirror(ovr_hip_renderer* r, float* host, const float* dev, int channels, const int dev_rect[4], int last[4], hipStream_t st);
 int enqueue_frame(ovr_hip_renderer* r);
 int finish_frame_one(ovr_hip_renderer* r);
+// the shadow cache: the parameters the shadow march reads as the next frame would set them (general layout, sampling rate, transfer function) into q; the lattice
+// the next cached frame reads bound into q - mode CACHED builds it first if it is stale, on st, and waits for it
+void fill_shadow_params(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
+int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
+int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
+int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);
 
 // group.cpp: the device group
 enum { GW_NONE = 0, GW_COMMIT, GW_RENDER, GW_SHIP, GW_FINISH, GW_SWAP, GW_CALL, GW_QUIT };

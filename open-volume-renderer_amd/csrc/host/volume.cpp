@@ -504,6 +504,7 @@ static int set_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, i
   std::memcpy(r->spacing, grid_spacing, sizeof(r->spacing));
   r->have_volume = true;
   r->mc_ranges_valid = r->mc_majorant_valid = false;
+  { policy::ShadowCacheChange ch; ch.volume = true; if (policy::shadow_cache_stale(ch)) r->shadow_cache.built_valid = false; }
   update_volume_params(r);
   // load_from_array3d_scalar (volume.cpp:181-191, 234-237): the macrocell value ranges and, from them, the data range the
   // reference finds with compute_scalar_range (array.cpp:27-66,297) - it is the transfer-function range until a valid one is set
@@ -615,6 +616,7 @@ static int update_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind
     return e;
   }
   r->mc_majorant_valid = false; // rebuilt whole with the next frame that skips; restarts the adaptive-skipping probe (policy::Skip)
+  { policy::ShadowCacheChange ch; ch.volume_update = true; if (policy::shadow_cache_stale(ch)) r->shadow_cache.built_valid = false; } // a whole rebuild
   r->fb_reset = true;
   r->conv.valid = false; r->conv.retired = 0; r->conv.active = r->sched.n_work; // what a commit does with a pending reset
   r->tune.state = 0;

@@ -115,6 +115,7 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_sparse_count) (void)hipFree(r->d_sparse_count);
   if (r->d_data_range) (void)hipFree(r->d_data_range);
   if (r->d_update_stage) (void)hipFree(r->d_update_stage);
+  free_shadow_cache(r);
   if (r->h_counters) (void)hipHostFree(r->h_counters);
   if (r->conv.h_publish) (void)hipHostFree(r->conv.h_publish);
   if (r->recon.h_publish) (void)hipHostFree(r->recon.h_publish);
@@ -328,6 +329,144 @@ int ovr_hip_get_clip_box(const ovr_hip_renderer* r, ovr_hip_clip_box* out)
   return 0;
 }
 
+int ovr_hip_set_shadow_cache(ovr_hip_renderer* r, int32_t mode, int32_t cell_voxels)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (mode != OVR_HIP_SHADOWS_MARCHED && mode != OVR_HIP_SHADOWS_CACHED && mode != OVR_HIP_SHADOWS_SUPPLIED)
+    return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache: unknown mode");
+  if (cell_voxels < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache: the cell size must be at least 1 voxel (0 = the default)");
+  ShadowP p;
+  p.mode = mode;
+  p.cell = cell_voxels > 0 ? cell_voxels : policy::kShadowCacheDefaultCell;
+  if (mode == OVR_HIP_SHADOWS_CACHED && r->have_volume) {
+    int dims[3];
+    if (shadow_lattice_dims(r, p.cell, dims)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache: a lattice of more than 2^31 - 1 nodes (take a larger cell)");
+  }
+  if (mode == OVR_HIP_SHADOWS_SUPPLIED && !r->shadow_cache.d_supplied)
+    return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_set_shadow_cache: mode SUPPLIED needs values first (ovr_hip_set_shadow_cache_values)");
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->shadow.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_shadow_cache(m, mode, cell_voxels));
+  return 0;
+}
+
+} // extern "C"
+namespace {
+// one renderer's copy of the caller's lattice, from host memory: the new buffer first, so that a failed allocation leaves the previous values in place
+int set_shadow_values_one(ovr_hip_renderer* r, const float* host, const int32_t dims[3])
+{
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame_one(r)) return e;
+  const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+  float* d = nullptr;
+  if (hipMalloc((void**)&d, nodes * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(OVR_HIP_EDEVICE, "[hip] ovr_hip_set_shadow_cache_values: the lattice of " + std::to_string(nodes) + " nodes could not be allocated");
+  }
+  if (hipMemcpy(d, host, nodes * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipFree(d);
+    return fail(OVR_HIP_EDEVICE, "[hip] ovr_hip_set_shadow_cache_values: the copy to the device failed");
+  }
+  HIP_TRY(hipDeviceSynchronize()); // no frame reads the old values any more
+  ShadowCacheState& c = r->shadow_cache;
+  if (c.d_supplied) HIP_TRY(hipFree(c.d_supplied));
+  c.d_supplied = d;
+  for (int k = 0; k < 3; ++k) c.supplied_dims[k] = dims[k];
+  if (r->shadow.current.mode == OVR_HIP_SHADOWS_SUPPLIED) r->fb_reset = true; // another shadow term: the accumulation starts over
+  return 0;
+}
+} // namespace
+extern "C" {
+
+int ovr_hip_set_shadow_cache_values(ovr_hip_renderer* r, const float* values, int mem_kind, const int32_t dims[3])
+{
+  if (!r || !values || !dims) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache_values: null argument");
+  if (mem_kind != OVR_HIP_MEM_HOST && mem_kind != OVR_HIP_MEM_DEVICE) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache_values: bad mem_kind");
+  long long nodes = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (dims[k] < 2) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache_values: a lattice has at least 2 nodes per axis");
+    nodes = nodes > 0x7fffffffll / dims[k] ? 0x80000000ll : nodes * dims[k];
+  }
+  if (nodes > 0x7fffffffll) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache_values: more than 2^31 - 1 nodes");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  // validated once, on the host, on the handle the caller holds; every member of a device group then uploads the same host copy
+  std::vector<float> stage;
+  const float* host = values;
+  if (mem_kind == OVR_HIP_MEM_DEVICE) {
+    stage.resize((size_t)nodes);
+    HIP_TRY(hipMemcpy(stage.data(), values, (size_t)nodes * sizeof(float), hipMemcpyDeviceToHost));
+    host = stage.data();
+  }
+  for (long long i = 0; i < nodes; ++i)
+    if (!std::isfinite(host[i])) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_shadow_cache_values: value " + std::to_string(i) + " is not finite");
+  const int32_t d3[3] = { dims[0], dims[1], dims[2] };
+  if (r->group.members.size() <= 1) return set_shadow_values_one(r, host, d3);
+  GroupLock gl(r);
+  return group_call(r, [=](ovr_hip_renderer* m) { return set_shadow_values_one(m, host, d3); }, [&] { return set_shadow_values_one(r, host, d3); });
+}
+
+int ovr_hip_get_shadow_cache(const ovr_hip_renderer* r, ovr_hip_shadow_cache* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_shadow_cache: null argument");
+  const ShadowCacheState& c = r->shadow_cache;
+  const ShadowP& p = r->shadow.current;
+  *out = ovr_hip_shadow_cache{};
+  out->mode = p.mode;
+  out->cell = p.cell;
+  const int* dims = p.mode == OVR_HIP_SHADOWS_SUPPLIED ? c.supplied_dims : c.built_dims;
+  const bool have = p.mode == OVR_HIP_SHADOWS_SUPPLIED ? c.d_supplied != nullptr : p.mode == OVR_HIP_SHADOWS_CACHED && c.d_built != nullptr && c.built_dims[0] > 0;
+  if (have) {
+    for (int k = 0; k < 3; ++k) out->dims[k] = dims[k];
+    out->bytes = (uint64_t)dims[0] * dims[1] * dims[2] * sizeof(float);
+    out->valid = p.mode == OVR_HIP_SHADOWS_SUPPLIED || c.built_valid ? 1 : 0;
+  }
+  out->builds = c.builds;
+  out->build_shadow_samples = c.build_samples;
+  out->build_ms = c.build_ms;
+  return 0;
+}
+
+int ovr_hip_get_shadow_cache_values(ovr_hip_renderer* r, int32_t member, int32_t dims[3], float* values_host, float* positions_host, size_t capacity_nodes)
+{
+  if (!r || !dims) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_shadow_cache_values: null argument");
+  const size_t members = std::max<size_t>(r->group.members.size(), 1);
+  if (member < 0 || (size_t)member >= members) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_shadow_cache_values: no such member");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  ovr_hip_renderer* m = members > 1 ? r->group.members[(size_t)member] : r;
+  if (m->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_shadow_cache_values: the committed mode is MARCHED - there is no lattice");
+  auto read = [&]() -> int {
+    if (int e = set_device(m)) return e;
+    hipStream_t st = m->stream();
+    RayMarchParams q = m->P;
+    if (int e = ensure_shadow_cache(m, q, st)) return e;
+    for (int k = 0; k < 3; ++k) dims[k] = q.shadow_n1[k] + 1;
+    const size_t nodes = (size_t)dims[0] * dims[1] * dims[2];
+    if (!values_host && !positions_host) return 0;
+    if (capacity_nodes < nodes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_shadow_cache_values: output too small");
+    if (values_host) HIP_TRY(hipMemcpyAsync(values_host, q.shadow_lattice, nodes * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (positions_host) {
+      if (!m->have_volume || !m->have_tfn) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_shadow_cache_values: the nodes' positions need a volume and a transfer function");
+      float* d_pos = nullptr;
+      HIP_TRY(hipMalloc((void**)&d_pos, nodes * 3 * sizeof(float)));
+      const int d3[3] = { dims[0], dims[1], dims[2] };
+      int e = shadow_lattice_positions(m, d3, d_pos, st);
+      hipError_t err = e ? hipSuccess : hipMemcpyAsync(positions_host, d_pos, nodes * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+      if (err == hipSuccess) err = hipStreamSynchronize(st);
+      (void)hipFree(d_pos);
+      if (e) return e;
+      if (err != hipSuccess) return fail(OVR_HIP_EDEVICE, std::string("[hip] ovr_hip_get_shadow_cache_values: ") + hipGetErrorString(err));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+  };
+  const int e = read();
+  (void)set_device(r);
+  return e;
+}
+
 int ovr_hip_set_reconstruction(ovr_hip_renderer* r, int32_t mode)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -405,7 +544,8 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
          && std::memcmp(&a->focus.current, &b->focus.current, sizeof(FocusP)) == 0 && a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw
          && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn && a->convergence.current.mode == b->convergence.current.mode
          && a->convergence.current.threshold == b->convergence.current.threshold && std::memcmp(&a->light.current, &b->light.current, sizeof(LightP)) == 0
-         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0 && std::memcmp(&a->clip.current, &b->clip.current, sizeof(ClipP)) == 0;
+         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0 && std::memcmp(&a->clip.current, &b->clip.current, sizeof(ClipP)) == 0
+         && a->shadow.current.mode == b->shadow.current.mode && a->shadow.current.cell == b->shadow.current.cell;
 }
 } // namespace
 extern "C" {
@@ -448,9 +588,11 @@ int commit_one(ovr_hip_renderer* r)
   const bool reset_pending = r->fb_reset; // (without accumulation the flag is never consumed)
   r->fb_reset = false;
   bool fb_size_updated = false, camera_changed = false;
+  policy::ShadowCacheChange shadow_change; // what this commit changes, as the shadow cache's staleness rule reads it (policy::shadow_cache_stale)
   if (r->fbsize.update()) { // device_impl.cpp:116-122
     if (int e = resize_framebuffers(r, r->fbsize.current.w, r->fbsize.current.h)) return e;
     fb_size_updated = true;
+    shadow_change.framebuffer = true;
     r->fb_reset = true;
   }
   if (r->camera.update() || fb_size_updated || r->camera_dirty) { // :125-144
@@ -461,6 +603,7 @@ int commit_one(ovr_hip_renderer* r)
     r->sched.dirty = true;
     r->fb_reset = true;
     camera_changed = !fb_size_updated;
+    shadow_change.camera = true;
   }
   const bool only_camera_so_far = camera_changed;
   if (camera_changed) r->fb_reset = false; // (restored below: the flag doubles as "something besides the camera changed")
@@ -468,24 +611,27 @@ int commit_one(ovr_hip_renderer* r)
     if (int e = upload_tfn(r)) return e;
     update_tfn_range(r);
     r->mc_majorant_valid = false;
+    shadow_change.transfer_function = true;
     r->fb_reset = true;
   }
   if (r->grid_convention.update()) {
+    shadow_change.grid_convention = true;
     if (r->have_volume) update_volume_params(r);
     r->sched.dirty = true;
     r->fb_reset = true;
   }
   if (r->focus.update()) r->fb_reset = true;      // :155-168
-  if (r->spp.update()) { r->fb_reset = true; r->sched.dirty = true; }        // :170-173 (one sample per pixel: the schedule knows every ray)
-  if (r->sparse.update()) r->fb_reset = true;     // :180-183
-  if (r->accumulate.update()) r->fb_reset = true; // :185-188
-  if (r->rate.update()) r->fb_reset = true;       // :190-196
+  if (r->spp.update()) { r->fb_reset = true; r->sched.dirty = true; shadow_change.spp = true; }        // :170-173 (one sample per pixel: the schedule knows every ray)
+  if (r->sparse.update()) { r->fb_reset = true; shadow_change.sparse = true; }           // :180-183
+  if (r->accumulate.update()) { r->fb_reset = true; shadow_change.accumulation = true; } // :185-188
+  { const float before = r->rate.current; if (r->rate.update()) { r->fb_reset = true; shadow_change.sampling_rate = r->rate.current != before; } } // :190-196
   if (r->shading.update()) r->fb_reset = true;
-  if (r->jitter.update()) { r->fb_reset = true; r->sched.dirty = true; }
+  if (r->jitter.update()) { r->fb_reset = true; r->sched.dirty = true; shadow_change.jitter = true; }
   {
     const int before = r->convergence.current.mode;
     if (r->convergence.update()) { // any call resets the accumulation: retired blocks come back, the estimate starts over
       r->fb_reset = true;
+      shadow_change.convergence = true;
       if (r->convergence.current.mode != before) { // OFF keeps no buffer; the other two allocate what they need with their next frame
         HIP_TRY(hipDeviceSynchronize());
         if (int e = free_convergence(r)) return e;
@@ -496,6 +642,7 @@ int commit_one(ovr_hip_renderer* r)
     const int before = r->reconstruction.current;
     if (r->reconstruction.update()) { // any call resets the accumulation; OFF keeps no buffer, FILL allocates with its next sparse frame
       r->fb_reset = true;
+      shadow_change.reconstruction = true;
       if (r->reconstruction.current != before) {
         HIP_TRY(hipDeviceSynchronize());
         if (int e = free_reconstruction(r)) return e;
@@ -510,7 +657,11 @@ int commit_one(ovr_hip_renderer* r)
     const MaterialP mb = r->material.current;
     const bool lu = r->light.update(), mu = r->material.update();
     if (lu || mu) {
+      const float3_ dir = r->P.light;
       apply_lighting(r);
+      shadow_change.light_direction = std::memcmp(&dir, &r->P.light, sizeof(dir)) != 0; // the unit vector the shadow march runs along
+      shadow_change.light_intensity = lb.intensity != r->light.current.intensity;
+      shadow_change.material = std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0;
       if (std::memcmp(&lb, &r->light.current, sizeof(LightP)) != 0 || std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0) r->fb_reset = true;
     }
   }
@@ -520,15 +671,35 @@ int commit_one(ovr_hip_renderer* r)
     const ClipP cb = r->clip.current;
     if (r->clip.update()) {
       apply_clip_box(r);
-      if (std::memcmp(&cb, &r->clip.current, sizeof(ClipP)) != 0) { r->fb_reset = true; r->sched.dirty = true; }
+      if (std::memcmp(&cb, &r->clip.current, sizeof(ClipP)) != 0) { r->fb_reset = true; r->sched.dirty = true; shadow_change.clip_box = true; }
     }
   }
+  // shadow cache: a changed mode or cell resets the accumulation like a changed light - another shadow term - and, below, a changed mode voids the tuner's
+  // measurement (a cached frame is another workload); the same value again resets nothing.  MARCHED keeps no buffer; the caller's values are kept until the
+  // mode leaves SUPPLIED
+  bool shadow_mode_changed = false;
+  {
+    const ShadowP sb = r->shadow.current;
+    if (r->shadow.update()) {
+      shadow_change.mode = shadow_mode_changed = sb.mode != r->shadow.current.mode;
+      shadow_change.cell = sb.cell != r->shadow.current.cell;
+      if (shadow_change.mode || shadow_change.cell) r->fb_reset = true;
+      if (shadow_change.mode && (sb.mode == OVR_HIP_SHADOWS_SUPPLIED || r->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED)) {
+        HIP_TRY(hipDeviceSynchronize());
+        ShadowCacheState& c = r->shadow_cache;
+        if (sb.mode == OVR_HIP_SHADOWS_SUPPLIED && c.d_supplied) { HIP_TRY(hipFree(c.d_supplied)); c.d_supplied = nullptr; c.supplied_dims[0] = c.supplied_dims[1] = c.supplied_dims[2] = 0; }
+        if (r->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED && c.d_built) { HIP_TRY(hipFree(c.d_built)); c.d_built = nullptr; c.built_cap = 0; c.built_dims[0] = c.built_dims[1] = c.built_dims[2] = 0; }
+      }
+    }
+  }
+  if (policy::shadow_cache_stale(shadow_change)) r->shadow_cache.built_valid = false;
   (void)r->lds_staging.update(); // same frame either way
   // every layout and both pipelines give the same frame: no accumulation reset - but what was measured under the old setting is void
   // (a probe must not override a layout forced meanwhile; forced -> automatic has to measure again)
   bool tune_void = false;
-  { const int before = r->layout_choice.current; if (r->layout_choice.update() && r->layout_choice.current != before) tune_void = true; }
-  { const int before = r->pipeline.current; if (r->pipeline.update() && r->pipeline.current != before) tune_void = true; }
+  { const int before = r->layout_choice.current; if (r->layout_choice.update() && r->layout_choice.current != before) { tune_void = true; shadow_change.layout_choice = true; } }
+  { const int before = r->pipeline.current; if (r->pipeline.update() && r->pipeline.current != before) { tune_void = true; shadow_change.pipeline = true; } }
+  if (shadow_mode_changed) tune_void = true;
   if (r->skipping.update()) r->skip.restart(); // skipping does not change the frame either
   if (r->shard.update()) {
     r->sched.list_dirty = true;
@@ -991,6 +1162,32 @@ int ovr_hip_clip_intervals(ovr_hip_renderer* r, const float* org, const float* d
   if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_clip_intervals: no volume was set");
   HIP_TRY(launch_clip_intervals(r->P, org, dir, t0t1hit, n, r->stream())); // the committed volume transform and clip box
   HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_shadow_floats(ovr_hip_renderer* r, const float* pos, float* out, int64_t n, int32_t which)
+{
+  if (!r || !pos || !out || n < 0 || (which != 0 && which != 1)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_shadow_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume || !r->have_tfn) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_shadow_floats: needs a volume and a transfer function");
+  hipStream_t st = r->stream();
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate, transfer function and the general layout, as a frame sets them
+  if (which == 0) {
+    if (r->tf_copy_pending) { HIP_TRY(hipStreamWaitEvent(st, r->ev_tf, 0)); r->tf_copy_pending = false; }
+    ShadowBuildArgs a{};
+    a.out = out;
+    a.pos = pos;
+    a.n = n;
+    HIP_TRY(launch_shadow_cache(q, a, st));
+  }
+  else {
+    if (r->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_shadow_floats: the committed mode is MARCHED - there is no lattice to look up");
+    if (int e = ensure_shadow_cache(r, q, st)) return e;
+    HIP_TRY(launch_shadow_lookup(q, pos, out, n, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
 

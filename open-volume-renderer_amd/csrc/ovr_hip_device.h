@@ -988,9 +988,27 @@ __device__ __forceinline__ float shade_light(const RayMarchParams& P, f3 light, 
 template <bool MAT>
 __device__ __forceinline__ float shade_factor(const RayMarchParams& P, float lit, float shadow) { return (MAT ? P.mat_ka : 0.5f) + lit * (1.f - shadow); }
 
+// The shadow cache's lookup (include/ovr_hip.h ovr_hip_set_shadow_cache; open-volume-renderer_amd/shadow_cache.py is the normative arithmetic): the shadow
+// term of a sample at the object position po as one trilinear tap into the lattice of march_shadow's values - eight scalar loads and seven lerps, along x,
+// then y, then z, whatever the voxel type, layout or addressing mode.  The lattice and its dimensions are kernel arguments behind every other one
+// (RayMarchParams::shadow_lattice / shadow_n1): only the cached instantiations read them.  The result is not clamped.
+__device__ __forceinline__ float shadow_lookup(const RayMarchParams& P, f3 po)
+{
+  const int nx1 = P.shadow_n1[0], ny1 = P.shadow_n1[1], nz1 = P.shadow_n1[2]; // N - 1 per axis (>= 1)
+  const float gx = clamp01(po.x) * (float)nx1, gy = clamp01(po.y) * (float)ny1, gz = clamp01(po.z) * (float)nz1;
+  const int ix = min((int)floorf(gx), nx1 - 1), iy = min((int)floorf(gy), ny1 - 1), iz = min((int)floorf(gz), nz1 - 1);
+  const float fx = gx - (float)ix, fy = gy - (float)iy, fz = gz - (float)iz;
+  const size_t sy = (size_t)nx1 + 1, sz = sy * ((size_t)ny1 + 1);
+  const float* __restrict__ c = P.shadow_lattice + ((size_t)ix + sy * (size_t)iy + sz * (size_t)iz);
+  const float v000 = c[0], v100 = c[1], v010 = c[sy], v110 = c[sy + 1], v001 = c[sz], v101 = c[sz + 1], v011 = c[sz + sy], v111 = c[sz + sy + 1];
+  const float c00 = lerpf(v000, v100, fx), c10 = lerpf(v010, v110, fx), c01 = lerpf(v001, v101, fx), c11 = lerpf(v011, v111, fx);
+  return lerpf(lerpf(c00, c10, fy), lerpf(c01, c11, fy), fz);
+}
+
 // shade one request: gradient (shaders_common.h:195-215), normals, shadow march, shade factor
 // (shaders_raymarching.cu:124-158).  Writes the result over the request.
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false>
+// CACHED: the shadow term is shadow_lookup's tap instead of a march (SHADE == 1: the kernel has no shadow march)
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false>
 __device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r,
                                               unsigned int& n_shadow, unsigned int& n_shadow_skipped)
 {
@@ -1028,6 +1046,7 @@ __device__ __forceinline__ void shade_request(const RayMarchParams& P, const Vol
   const float lit = shade_light<MAT>(P, mc.light, n_w, pos);
   float shadow = 0.f;
   if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP, CLIP>(P, vc, tf, mc, pos, n_shadow, n_shadow_skipped);
+  if (CACHED) shadow = shadow_lookup(P, po);
   const float shade = shade_factor<MAT>(P, lit, shadow); // shaders_raymarching.cu:156-157
   const float tr = r.tr;
   r.px = tr * clamp01(rgb.x * shade);
@@ -1213,10 +1232,11 @@ constexpr int kDeepK = 6;
 constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scratch under the pin
 // CLIP = true: the clipped march (box_test).  Where the march shades in place it rides on MAT = true - the material's values as arguments give the
 // reference state's bits when they are the reference's - so a clipped state adds one instantiation per kernel, not two
-template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false>
+// CACHED = true: the shadow cache's frame (shade_request) - SHADE == 1 and MAT = true, in place only
+template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false, bool CACHED = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
-  static_assert(march_variant_exists(SHADE, AM, POOLED, SKIP, LDSB, DEEP, MAT, CLIP, VT == VOX_F32), "no such variant of the march (host/launch_plan.hpp)");
+  static_assert(march_variant_exists(SHADE, AM, POOLED, SKIP, LDSB, DEEP, MAT, CLIP, VT == VOX_F32, CACHED), "no such variant of the march (host/launch_plan.hpp)");
   using Cfg = QCfg<SHADE, POOLED>;
   constexpr int K = DEEP ? kDeepK : Cfg::K;
   constexpr int QCAP = Cfg::QCAP;
@@ -1439,7 +1459,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
           r.px = r.py = r.pz = r.s = r.v = r.tr = r.a = 0.f; r.next = 0;
           if ((unsigned int)lane < n) {
             r = queue[(q_head + lane) & (QCAP - 1)];
-            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT, CLIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
+            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
           }
           int opend = owner ? pend : 0;
           apply_batch(r, q_head, n, lane, opend, first, color, gradient);
@@ -1783,10 +1803,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
 // ------------------------------------------------------------------------------------------------------------------
 // pooled pipeline, kernel B: persistent waves shade chunks from all tiles; one returning atomic per chunk
 // ------------------------------------------------------------------------------------------------------------------
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false>
 __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams P)
 {
-  static_assert(shade_variant_exists(SHADE, AM, SKIP, MAT, CLIP), "no such variant of the shade kernel (host/launch_plan.hpp)");
+  static_assert(shade_variant_exists(SHADE, AM, SKIP, MAT, CLIP, CACHED), "no such variant of the shade kernel (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   TfConsts tf;
@@ -1830,7 +1850,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     if ((unsigned int)lane < n) {
       ShadeReq r = Q.reqs[(size_t)c * 64 + lane];
       if (r.a > 0.f) { // a == 0: null request (a step of the quad that needs no shading)
-        shade_request<VT, SHADE, AM, SKIP, MAT, CLIP>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
+        shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
         Q.reqs[(size_t)c * 64 + lane] = r;
       }
     }
@@ -1916,23 +1936,25 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
 // ------------------------------------------------------------------------------------------------------------------
 typedef void (*FrameKernel)(const RayMarchParams);
 struct FrameKernels { FrameKernel march = nullptr, shade = nullptr; }; // shade: pooled plans only; march == nullptr: no such variant of this type
-enum VariantBits : unsigned { kBitPooled = 1, kBitSkip = 2, kBitLdsStaged = 4, kBitDeep = 8, kBitMaterial = 16, kBitClipped = 32, kVariantBitsEnd = 64 };
-constexpr unsigned kShadeBits = kBitSkip | kBitMaterial | kBitClipped; // the flags shade_pool_kernel has
+enum VariantBits : unsigned { kBitPooled = 1, kBitSkip = 2, kBitLdsStaged = 4, kBitDeep = 8, kBitMaterial = 16, kBitClipped = 32, kBitCached = 64,
+                     kVariantBitsEnd = 128 };
+constexpr unsigned kShadeBits = kBitSkip | kBitMaterial | kBitClipped | kBitCached; // the flags shade_pool_kernel has
 
 template <int VT, int SHADE, int AM, unsigned BITS>
 constexpr FrameKernel march_variant()
 {
   constexpr bool pooled = BITS & kBitPooled, skip = BITS & kBitSkip, lds_staged = BITS & kBitLdsStaged, deep = BITS & kBitDeep, material = BITS & kBitMaterial,
-                 clipped = BITS & kBitClipped;
-  if constexpr (march_variant_exists(SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, VT == VOX_F32))
-    return raymarch_kernel<VT, SHADE, AM, pooled, skip, lds_staged, deep, material, clipped>;
+                 clipped = BITS & kBitClipped, cached = BITS & kBitCached;
+  if constexpr (march_variant_exists(SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, VT == VOX_F32, cached))
+    return raymarch_kernel<VT, SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, cached>;
   else return nullptr;
 }
 template <int VT, int SHADE, int AM, unsigned BITS>
 constexpr FrameKernel shade_variant()
 {
-  constexpr bool skip = BITS & kBitSkip, material = BITS & kBitMaterial, clipped = BITS & kBitClipped;
-  if constexpr ((BITS & ~kShadeBits) == 0 && shade_variant_exists(SHADE, AM, skip, material, clipped)) return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped>;
+  constexpr bool skip = BITS & kBitSkip, material = BITS & kBitMaterial, clipped = BITS & kBitClipped, cached = BITS & kBitCached;
+  if constexpr ((BITS & ~kShadeBits) == 0 && shade_variant_exists(SHADE, AM, skip, material, clipped, cached))
+    return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped, cached>;
   else return nullptr;
 }
 template <int VT, int SHADE, int AM, unsigned... BITS>
@@ -1961,14 +1983,78 @@ inline FrameKernels variants_of(int am, unsigned march_bits, unsigned shade_bits
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// the shadow cache's build kernel (ShadowBuildArgs in ovr_hip_kernels.h): one lane per node, a wave = a 4 x 4 x 4 tile of nodes - neighbours in all three
+// directions, so the lanes' shadow rays sweep the same bricks -, or one lane per caller-supplied position.  Transfer function (alphas only) and axis tables
+// are staged as shade_pool_kernel stages them.  CLIP = true only: the bounds (0, 1) give the literal test's bits.  Instantiated for
+// the general layouts - the layout that is always resident and that ovr_hip_update_volume rewrites first.
+// ------------------------------------------------------------------------------------------------------------------
+template <int VT, int AM>
+__global__ __launch_bounds__(kBlock) void shadow_cache_kernel(const RayMarchParams P, const ShadowBuildArgs A)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  TfConsts tf;
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  const size_t tb = (stage_tables<VT, AM>(P, lds_raw, vc) + 15) & ~(size_t)15; // [offset tables][alphas]
+  stage_tf(P, lds_raw + tb, false, tf);
+  bool valid;
+  long long index;
+  f3 org = mk3(0.f, 0.f, 0.f);
+  if (A.pos) {
+    index = (long long)blockIdx.x * kBlock + threadIdx.x;
+    valid = index < A.n;
+    if (valid) org = mk3(A.pos[3 * index], A.pos[3 * index + 1], A.pos[3 * index + 2]);
+  }
+  else {
+    const long long tx = (A.nx + 3) / 4, ty = (A.ny + 3) / 4;
+    const long long tile = (long long)blockIdx.x * kWaves + wave;
+    const int ix = (int)(tile % tx) * 4 + (lane & 3), iy = (int)((tile / tx) % ty) * 4 + ((lane >> 2) & 3);
+    const long long izl = (tile / (tx * ty)) * 4 + (lane >> 4);
+    valid = ix < A.nx && iy < A.ny && izl < (long long)A.nz;
+    const int iz = (int)izl;
+    index = (long long)ix + (long long)A.nx * ((long long)iy + (long long)A.ny * (long long)iz);
+    const float ux = (float)ix / (float)(A.nx - 1), uy = (float)iy / (float)(A.ny - 1), uz = (float)iz / (float)(A.nz - 1);
+    org = mk3(fmaf(ux, A.sc[0], A.origin[0]), fmaf(uy, A.sc[1], A.origin[1]), fmaf(uz, A.sc[2], A.origin[2]));
+  }
+  unsigned int n_shadow = 0, n_shadow_skipped = 0;
+  if (valid) {
+    if (A.out) A.out[index] = march_shadow<VT, AM, kShadowTaps, false, true>(P, vc, tf, mc, org, n_shadow, n_shadow_skipped); // (null: the positions alone)
+    if (A.pos_out) { A.pos_out[3 * index] = org.x; A.pos_out[3 * index + 1] = org.y; A.pos_out[3 * index + 2] = org.z; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n_shadow += __shfl_down(n_shadow, off);
+  if (lane == 0 && A.iterations && n_shadow) atomicAdd(A.iterations, (unsigned long long)n_shadow);
+}
+typedef void (*ShadowCacheKernel)(const RayMarchParams, const ShadowBuildArgs);
+// the build kernel of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads)
+template <int VT>
+ShadowCacheKernel shadow_cache_kernel_of(int am)
+{
+  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
+    switch (am) {
+    case 0: return shadow_cache_kernel<VT, 0>;
+    case 1: return shadow_cache_kernel<VT, 1>;
+    case 2: return shadow_cache_kernel<VT, 2>;
+    case 3: return shadow_cache_kernel<VT, 3>;
+    case 4:
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return shadow_cache_kernel<VT, 4>;
+      else return nullptr;
+    }
+  }
+  return nullptr;
+}
+
 // one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~160 kernel
 // variants of a type compile in parallel with the other types
 template <int VT>
 FrameKernels frame_kernels(const LaunchPlan& pl)
 {
   const unsigned flags = (pl.skip ? kBitSkip : 0u) | (pl.pooled ? kBitPooled : 0u) | (pl.march.lds_staged ? kBitLdsStaged : 0u) | (pl.march.deep ? kBitDeep : 0u);
-  const unsigned march_bits = flags | (pl.march.material ? kBitMaterial : 0u) | (pl.march.clipped ? kBitClipped : 0u);
-  const unsigned shade_bits = (flags & kBitSkip) | (pl.shade.material ? kBitMaterial : 0u) | (pl.shade.clipped ? kBitClipped : 0u);
+  const unsigned march_bits = flags | (pl.march.material ? kBitMaterial : 0u) | (pl.march.clipped ? kBitClipped : 0u) | (pl.cached && !pl.pooled ? kBitCached : 0u);
+  const unsigned shade_bits = (flags & kBitSkip) | (pl.shade.material ? kBitMaterial : 0u) | (pl.shade.clipped ? kBitClipped : 0u) | (pl.cached ? kBitCached : 0u);
   FrameKernels k;
   if (pl.error) return k;
   switch (pl.shading) {

@@ -988,6 +988,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.clip_on = p.clip_on != 0; f.lds_staging = p.lds_staging != 0;
   f.row_loads = p.row_loads; f.shade_blocks = p.shade_blocks;
   f.reference_material = reference_material(p); f.shade_order = p.pool.order != nullptr;
+  f.shadow_cache = p.shadow_lattice != nullptr;
   return plan_launch(f, o);
 }
 
@@ -1988,6 +1989,56 @@ hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, c
   if (n <= 0) return hipSuccess;
   auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as plan_launch picks the frame's kernels
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, normal_w, pos, shadow, out, (long long)n);
+  return hipGetLastError();
+}
+
+// the shadow cache's build and the shadow march's known-answer entry (ShadowBuildArgs): the kernel of the general layout's type at the addressing mode the
+// frame's kernels take for that layout (plan_launch: the layout's mode, the environment's override, the row loads)
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template ShadowCacheKernel shadow_cache_kernel_of<E>(int);
+OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a, hipStream_t stream)
+{
+  if (a.n <= 0) return hipSuccess;
+  if (!a.out && !(a.pos_out && !a.pos)) return hipErrorInvalidValue; // nothing to write: out, or the nodes' positions alone
+  RayMarchParams q = p;
+  q.shading = 0; q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  q.shadow_lattice = nullptr;
+  const LaunchPlan pl = plan_raymarch(q);
+  if (pl.error) return hipErrorInvalidValue;
+  ShadowCacheKernel kern = nullptr;
+  dispatch_voxel_type(q.vol.type, [&](auto vt) { kern = shadow_cache_kernel_of<decltype(vt)::value>(pl.am); });
+  if (!kern) return hipErrorInvalidValue;
+  const size_t lds = align16(axis_table_bytes(q.vol.nx, q.vol.ny, q.vol.nz, pl.am)) + (size_t)q.n_alpha * 4 + 64;
+  if (lds > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  long long blocks;
+  if (a.pos) blocks = (a.n + kBlock - 1) / kBlock;
+  else {
+    if (a.nx < 2 || a.ny < 2 || a.nz < 2 || (long long)a.nx * a.ny * a.nz != a.n) return hipErrorInvalidValue;
+    const long long tiles = (long long)((a.nx + 3) / 4) * ((a.ny + 3) / 4) * ((a.nz + 3) / 4);
+    blocks = (tiles + kWaves - 1) / kWaves;
+  }
+  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), lds, stream, q, a);
+  return hipGetLastError();
+}
+
+// known-answer entry of the lattice lookup: to_object as shade_request forms po, then shadow_lookup exactly as the cached kernels call it
+__global__ void shadow_lookup_kernel(const RayMarchParams P, const float* pos, float* out, long long n)
+{
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  out[i] = shadow_lookup(P, to_object(mc, mk3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2])));
+}
+hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float* out, int64_t n, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if (!p.shadow_lattice) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(shadow_lookup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, pos, out, (long long)n);
   return hipGetLastError();
 }
 

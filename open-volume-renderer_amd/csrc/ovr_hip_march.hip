@@ -8,4 +8,5 @@
 
 namespace ovrhip {
 template FrameKernels frame_kernels<OVR_MARCH_VT>(const LaunchPlan&);
+template ShadowCacheKernel shadow_cache_kernel_of<OVR_MARCH_VT>(int);
 }

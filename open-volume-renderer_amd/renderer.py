@@ -281,6 +281,52 @@ class DeviceHIP:
         o = out.cpu().numpy()
         return o[:, 0].copy(), o[:, 1].copy(), o[:, 2] != 0
 
+    # the shadow cache (include/ovr_hip.h ovr_hip_set_shadow_cache; shadow_cache.py is the arithmetic): the shadow term of full shading from a lattice of the
+    # shadow march's values, one trilinear tap per shaded sample.  Queued, applied at commit; a changed mode or cell resets the accumulation.
+    def set_shadow_cache(self, mode, cell=0):
+        """mode 0 marched (the default), 1 cached, 2 supplied (set_shadow_cache_values first); cell = voxels per lattice cell, 0 = the default"""
+        L.check(self._lib.ovr_hip_set_shadow_cache(self._h, int(mode), int(cell)))
+
+    def set_shadow_cache_values(self, array):
+        """the lattice of mode 2: a (nz, ny, nx) float32 array of at least 2 nodes per axis spanning the volume; copied at once"""
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        if a.ndim != 3:
+            raise RuntimeError("set_shadow_cache_values: the lattice is a (nz, ny, nx) array")
+        dims = (C.c_int32 * 3)(a.shape[2], a.shape[1], a.shape[0])
+        L.check(self._lib.ovr_hip_set_shadow_cache_values(self._h, a.ctypes.data, L.MEM_HOST, dims))
+
+    def shadow_cache(self):
+        """ovr_hip_shadow_cache, the COMMITTED state: mode, cell, dims, valid, builds, build_shadow_samples, bytes, build_ms"""
+        c = L.ShadowCache()
+        L.check(self._lib.ovr_hip_get_shadow_cache(self._h, C.byref(c)))
+        return c
+
+    def shadow_cache_values(self, member=0, positions=False):
+        """the lattice the next cached frame reads as a (nz, ny, nx) float32 array (mode 1 builds it first if it is stale); positions=True: also the nodes'
+        world positions, (nz, ny, nx, 3)"""
+        dims = (C.c_int32 * 3)()
+        L.check(self._lib.ovr_hip_get_shadow_cache_values(self._h, int(member), dims, None, None, 0))
+        nx, ny, nz = dims[0], dims[1], dims[2]
+        values = np.empty((nz, ny, nx), np.float32)
+        pos = np.empty((nz, ny, nx, 3), np.float32) if positions else None
+        fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        L.check(self._lib.ovr_hip_get_shadow_cache_values(self._h, int(member), dims, fp(values), fp(pos), values.size))
+        return (values, pos) if positions else values
+
+    def shadow_floats(self, pos, which=0):
+        """the shadow term as the kernels evaluate it (ovr_hip_shadow_floats; known-answer tests): world positions (n, 3) -> (n,) float32.  which 0: the shadow
+        march with the committed light, sampling rate, transfer function and clip box; 1: the lattice lookup"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float32)).to(dev)
+        n = int(t.numel()) // 3
+        if t.numel() != 3 * n:
+            raise RuntimeError("shadow_floats: pos holds three floats per position")
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_shadow_floats(self._h, t.data_ptr(), out.data_ptr(), n, int(which)))
+        return out.cpu().numpy()
+
     # ---- extensions of this backend ----------------------------------------------------------------------------
     def set_shading(self, mode):
         L.check(self._lib.ovr_hip_set_shading(self._h, int(mode)))

@@ -169,6 +169,14 @@ public:
         check(ovr_hip_set_clip_box(h, lo, hi));
         if (!quiet) std::fprintf(stderr, "[hip] clip box (%g, %g, %g) .. (%g, %g, %g)\n", (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2]);
       }
+      // The shadow cache (ovr_hip_set_shadow_cache): OVR_HIP_SHADOW_CACHE=<cell> takes the shadow term of the full shading from a lattice of one node per
+      // <cell> voxels (0 = the library's default cell).  Unset: nothing is called, the frames march their shadow rays
+      if (const char* sv = std::getenv("OVR_HIP_SHADOW_CACHE")) {
+        int cell = 0;
+        if (std::sscanf(sv, "%d", &cell) != 1 || cell < 0) throw std::runtime_error("[hip] OVR_HIP_SHADOW_CACHE expects the cell size in voxels (0 = the default)");
+        check(ovr_hip_set_shadow_cache(h, OVR_HIP_SHADOWS_CACHED, cell));
+        if (!quiet) std::fprintf(stderr, "[hip] shadow cache: one node per %d voxels%s\n", cell > 0 ? cell : 4, cell > 0 ? "" : " (the default)");
+      }
     }
     commit();
   }

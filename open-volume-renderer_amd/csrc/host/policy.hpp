@@ -1,7 +1,8 @@
 // policy.hpp - the host state machine's automatic decisions as plain state and pure functions of a frame's counters: which layout of the volume
 // a frame reads, which shading pipeline it runs, whether it uses the skipping kernels, how large the request pool is.  Nothing here calls HIP or
-// knows the renderer: the callers (frame.cpp, ovr_hip_api.cpp's commit) carry out what a policy returns - "start this replica's build", "render
-// this layout" - and tests/test_host_policy.py drives the same code with scripted frames on a machine without a GPU.
+// knows the renderer: the callers (frame.cpp; volume.cpp's apply_effects for what a commit does to the tuner and the skip probe) carry out what a policy
+// returns - "start this replica's build", "render this layout" - and tests/test_host_policy.py drives the same code with scripted frames on a machine
+// without a GPU.  What a changed parameter invalidates is not a policy of a frame's counters: commit_plan.hpp states it.
 #pragma once
 
 #include <algorithm>
@@ -306,21 +307,7 @@ inline int shade_blocks(bool use_skip, size_t prev_pool_chunks)
   return (!use_skip && prev_pool_chunks > 0 && prev_pool_chunks <= (size_t)64 * 1024 * 4) ? 768 : 1024;
 }
 
-// The shadow cache (ovr_hip_set_shadow_cache): a built lattice holds the shadow march's values at its nodes, so it is stale after a
-// change of anything that march reads or the lattice is laid out by - and of nothing else: the shadow term of a directional light is view-independent.
-// What changed since the lattice was built, as the commit and the volume calls see it:
-struct ShadowCacheChange {
-  // stale after any of these
-  bool volume = false, volume_update = false, transfer_function = false, sampling_rate = false, light_direction = false, clip_box = false, grid_convention = false,
-       cell = false, mode = false;
-  // not after these
-  bool camera = false, framebuffer = false, spp = false, jitter = false, material = false, light_intensity = false, accumulation = false, sparse = false,
-       convergence = false, reconstruction = false, layout_choice = false, pipeline = false, skipping = false;
-};
-inline bool shadow_cache_stale(const ShadowCacheChange& c)
-{
-  return c.volume || c.volume_update || c.transfer_function || c.sampling_rate || c.light_direction || c.clip_box || c.grid_convention || c.cell || c.mode;
-}
+// The shadow cache (ovr_hip_set_shadow_cache).  When a built lattice is stale is a column of commit_plan.hpp's table (kLatticeStale).
 // nodes per axis of the lattice over dim voxels at a cell size >= 1: ceil(dim / cell) + 1
 inline long long shadow_cache_nodes(int dim, int cell) { return ((long long)dim + cell - 1) / cell + 1; }
 constexpr int kShadowCacheDefaultCell = 4; // a guess: unmeasured until tools/shadow_cache_bench.py has run

@@ -8,6 +8,7 @@
 #include "../ovr_hip_kernels.h"
 #include "../ovr_hip_update.h"
 #pragma GCC visibility push(hidden)
+#include "commit_plan.hpp"
 #include "policy.hpp"
 #pragma GCC visibility pop
 
@@ -55,6 +56,7 @@ inline V3 scale(float s, V3 a) { return { s * a.x, s * a.y, s * a.z }; }
 template <typename T> struct Queued { // vidi::TransactionalValue (ovr/common/vidi_transactional_value.h:26-168), minus the template
   T queued{}, current{};
   bool dirty = false;
+  void init(const T& v) { queued = current = v; } // a default: committed without a commit
   void set(const T& v) { queued = v; dirty = true; }
   bool update() { if (!dirty) return false; current = queued; dirty = false; return true; }
 };
@@ -80,7 +82,7 @@ struct ShadowCacheState {
   float* d_built = nullptr;          // mode CACHED: the lattice of the shadow march's values
   size_t built_cap = 0;              // nodes d_built holds
   int built_dims[3] = { 0, 0, 0 };
-  bool built_valid = false;          // d_built is current (policy::shadow_cache_stale clears it)
+  bool built_valid = false;          // d_built is current (commit::kLatticeStale clears it)
   float* d_supplied = nullptr;       // mode SUPPLIED: the caller's lattice (ovr_hip_set_shadow_cache_values)
   int supplied_dims[3] = { 0, 0, 0 };
   unsigned long long* d_iterations = nullptr; // the build's iteration counter
@@ -203,7 +205,7 @@ struct ovr_hip_renderer {
   Queued<int> spp, sparse, accumulate, shading, grid_convention, pipeline, skipping, jitter, lds_staging;
   Queued<float> rate;
   Queued<ovrhip::host::ShardP> shard;
-  Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (apply_lighting)
+  Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (unit_light)
   Queued<ovrhip::host::MaterialP> material;
   Queued<ovrhip::host::ClipP> clip;          // the world box: the object box follows the volume (apply_clip_box)
   Queued<ovrhip::host::ShadowP> shadow;      // the shadow cache's mode and cell size
@@ -285,7 +287,7 @@ struct ovr_hip_renderer {
   float* d_spp_grad = nullptr;
   size_t fb_pixels = 0;
   int cur = 0;
-  bool fb_reset = true;
+  bool fb_reset = true; // the accumulation starts over with the next accumulated frame: set by apply_effects alone, consumed by the frame
   int frame_index = 0;
   bool camera_dirty = true;
 
@@ -360,10 +362,14 @@ int ensure_pool(ovr_hip_renderer* r, size_t chunks);
 int ensure_sparse_buffers(ovr_hip_renderer* r);
 void free_shadow_cache(ovr_hip_renderer* r);
 
-// volume.cpp: what a commit or an upload derives from camera, volume, transfer function and light; the replicas
+// volume.cpp: what a commit or an upload derives from camera, volume, transfer function and light; the replicas.  apply_effects carries out what
+// commit_plan.hpp's plan_commit asked for: fb_reset, the schedule's flags, pool_roomy, the validity flags of macrocells, lattice and estimate and the
+// tuner's restart are written there and (beside the frame's own bookkeeping and the code that builds each of them) nowhere else
+void apply_effects(ovr_hip_renderer* r, const ovrhip::commit::Effects& fx);
 void update_camera(ovr_hip_renderer* r);
 void update_volume_params(ovr_hip_renderer* r);
 void apply_lighting(ovr_hip_renderer* r);
+V3 unit_light(const LightP& l); // the unit vector apply_lighting derives
 void apply_clip_box(ovr_hip_renderer* r);
 void update_tfn_range(ovr_hip_renderer* r);
 int upload_tfn(ovr_hip_renderer* r);

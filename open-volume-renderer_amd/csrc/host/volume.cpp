@@ -116,6 +116,8 @@ void apply_clip_box(ovr_hip_renderer* r)
   P.clip_hi = { hi[0], hi[1], hi[2] };
 }
 
+V3 unit_light(const LightP& l) { return normalize({ l.dir[0], l.dir[1], l.dir[2] }); }
+
 // the committed light and material into the frame's parameters.  The raw vector is normalised here, by the routine that normalised the reference's
 // literal when the light was one: the same raw vector gives the same unit vector as the CPU oracle's (shade_order_params reads it per frame)
 void apply_lighting(ovr_hip_renderer* r)
@@ -123,10 +125,37 @@ void apply_lighting(ovr_hip_renderer* r)
   RayMarchParams& P = r->P;
   const LightP& l = r->light.current;
   const MaterialP& m = r->material.current;
-  const V3 L = normalize({ l.dir[0], l.dir[1], l.dir[2] });
+  const V3 L = unit_light(l);
   P.light = { L.x, L.y, L.z };
   P.light_i2 = 2.f * l.intensity;
   P.mat_ka = m.ambient; P.mat_kd = m.diffuse; P.mat_ks = m.specular; P.mat_shininess = m.shininess;
+}
+
+// carries out a plan (commit_plan.hpp).  The four kFree* effects are not here: a free can fail, so the commit runs them where it consumes the value
+void apply_effects(ovr_hip_renderer* r, const commit::Effects& fx)
+{
+  using namespace commit;
+  if (fx.has(kCameraParams)) { update_camera(r); r->camera_dirty = false; }
+  if (fx.has(kVolumeParams)) update_volume_params(r); // (and the clip box: the object box follows the volume's transform)
+  if (fx.has(kLighting)) apply_lighting(r);
+  if (fx.has(kClipParams)) apply_clip_box(r);
+  if (fx.has(kResort)) r->sched.dirty = true;
+  if (fx.has(kRelist)) r->sched.list_dirty = true;
+  if (fx.has(kBumpClearGen)) r->sched.clear_gen++;
+  if (fx.has(kPoolUnproven)) r->pool_roomy = false;
+  if (fx.has(kRangesVoid)) r->mc_ranges_valid = false;
+  if (fx.has(kMajorantVoid)) r->mc_majorant_valid = false;
+  if (fx.has(kSkipRestart)) r->skip.restart();
+  if (fx.has(kLatticeStale)) r->shadow_cache.built_valid = false;
+  switch (fx.tuner) {
+  case kTunerKeeps: break;
+  case kTunerCameraMoved: r->tune.configuration_changed(true); break;
+  case kTunerStateZero: r->tune.state = 0; break;
+  case kTunerChanged: r->tune.configuration_changed(false); break;
+  case kTunerVoid: r->tune.restart(); break;
+  }
+  if (fx.has(kReset)) r->fb_reset = true;
+  if (fx.has(kEstimateVoid)) { r->conv.valid = false; r->conv.retired = 0; r->conv.active = r->sched.n_work; }
 }
 
 // StructuredRegularVolume::set_value_range (volume.cpp:131-145): a valid range replaces the one in effect, an invalid one
@@ -503,9 +532,13 @@ static int set_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, i
   std::memcpy(r->origin, grid_origin, sizeof(r->origin));
   std::memcpy(r->spacing, grid_spacing, sizeof(r->spacing));
   r->have_volume = true;
-  r->mc_ranges_valid = r->mc_majorant_valid = false;
-  { policy::ShadowCacheChange ch; ch.volume = true; if (policy::shadow_cache_stale(ch)) r->shadow_cache.built_valid = false; }
-  update_volume_params(r);
+  {
+    commit::Changes ch;
+    ch.happened(commit::kVolumeUpload);
+    commit::CommitFacts facts;
+    facts.volume = true;
+    apply_effects(r, commit::plan_commit(ch, facts)); // (a pooled frame of THIS volume has to prove the pool: ovr_hip_pack_tiles packs early only then)
+  }
   // load_from_array3d_scalar (volume.cpp:181-191, 234-237): the macrocell value ranges and, from them, the data range the
   // reference finds with compute_scalar_range (array.cpp:27-66,297) - it is the transfer-function range until a valid one is set
   if (int e = update_macrocell_ranges(r, st)) return e;
@@ -518,10 +551,6 @@ static int set_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind, i
   r->P.tf_lower = dr[0];
   r->P.tf_upper = dr[1];
   update_tfn_range(r);
-  r->sched.dirty = true;
-  r->fb_reset = true;
-  r->tune.state = 0;
-  r->pool_roomy = false; // a pooled frame of THIS volume has to prove the pool (ovr_hip_pack_tiles packs early only then)
   t.kern += ms_since(t_seg); // mode-2 replica builds, macrocell ranges, the data range
   r->upload_ms[0] = ms_since(t_call); r->upload_ms[1] = t.alloc; r->upload_ms[2] = t.copy; r->upload_ms[3] = t.kern;
   return 0;
@@ -615,12 +644,11 @@ static int update_volume_one(ovr_hip_renderer* r, const void* data, int mem_kind
     r->have_volume = false;
     return e;
   }
-  r->mc_majorant_valid = false; // rebuilt whole with the next frame that skips; restarts the adaptive-skipping probe (policy::Skip)
-  { policy::ShadowCacheChange ch; ch.volume_update = true; if (policy::shadow_cache_stale(ch)) r->shadow_cache.built_valid = false; } // a whole rebuild
-  r->fb_reset = true;
-  r->conv.valid = false; r->conv.retired = 0; r->conv.active = r->sched.n_work; // what a commit does with a pending reset
-  r->tune.state = 0;
-  r->pool_roomy = false;
+  commit::Changes ch;
+  ch.happened(commit::kVolumeUpdate); // (the majorants are rebuilt whole with the next frame that skips; that restarts the adaptive-skipping probe, policy::Skip)
+  commit::CommitFacts facts;
+  facts.volume = true;
+  apply_effects(r, commit::plan_commit(ch, facts));
   r->update_ms[0] = ms_since(t_call); r->update_ms[1] = t.alloc; r->update_ms[2] = t.copy; r->update_ms[3] = t.kern;
   return 0;
 }

@@ -1,6 +1,7 @@
 // ovr_hip_api.cpp - C ABI (include/ovr_hip.h) of the MI355X ray-marching backend: the extern "C" layer of the host-side state machine -
 // create / destroy, the queued setters, commit diffing, render / sync, mapframe, swap and the getters.  The state machine itself lives in
-// host/: state.hpp (the renderer's state), policy.hpp (the automatic decisions, free of HIP), buffers.cpp, volume.cpp, frame.cpp, group.cpp.
+// host/: state.hpp (the renderer's state), policy.hpp (the automatic decisions, free of HIP), commit_plan.hpp (what a changed parameter invalidates, free of
+// HIP), buffers.cpp, volume.cpp, frame.cpp, group.cpp.
 //
 // Mirrors the host half of the reference's GPU device (citations relative to the reference tree):
 //   queued setters + commit diffing ... ovr/renderer.h:135-285, ovr/devices/optix7/device_impl.cpp:113-197
@@ -71,15 +72,15 @@ int ovr_hip_create(ovr_hip_renderer** out, int device_id)
   if (int e = acquire()) { ovr_hip_destroy(r); return e; } // nothing half-built leaks
   std::memset(r->h_counters, 0, 8 * sizeof(unsigned long long) + (size_t)kPoolCtrlWords * sizeof(unsigned int));
   // defaults of the reference's parameter block (params.h:55-99, renderer.h:255-285)
-  r->spp.current = r->spp.queued = 1;
-  r->sparse.current = r->sparse.queued = 0;
-  r->accumulate.current = r->accumulate.queued = 0;
-  r->shading.current = r->shading.queued = OVR_HIP_SHADE_FULL;
-  r->grid_convention.current = r->grid_convention.queued = OVR_HIP_GRID_CELL_CENTRED;
-  r->rate.current = r->rate.queued = 1.f;
-  r->layouts.current = r->layouts.queued = 1;
-  r->layout_choice.current = r->layout_choice.queued = -1;
-  if (const char* f = getenv("OVR_HIP_LAYOUTS")) r->layouts.current = r->layouts.queued = atoi(f); // diagnostic override
+  r->spp.init(1);
+  r->sparse.init(0);
+  r->accumulate.init(0);
+  r->shading.init(OVR_HIP_SHADE_FULL);
+  r->grid_convention.init(OVR_HIP_GRID_CELL_CENTRED);
+  r->rate.init(1.f);
+  r->layouts.init(1);
+  r->layout_choice.init(-1);
+  if (const char* f = getenv("OVR_HIP_LAYOUTS")) r->layouts.init(atoi(f)); // diagnostic override
   if (const char* f = getenv("OVR_HIP_SKIP_ADAPTIVE")) r->skip.adaptive = atoi(f) != 0;
   if (const char* f = getenv("OVR_HIP_TUNE")) r->tune.on = atoi(f) != 0;
   if (const char* f = getenv("OVR_HIP_SHADE_ORDER")) r->shade_order_on = atoi(f) != 0;
@@ -373,7 +374,9 @@ int set_shadow_values_one(ovr_hip_renderer* r, const float* host, const int32_t 
   if (c.d_supplied) HIP_TRY(hipFree(c.d_supplied));
   c.d_supplied = d;
   for (int k = 0; k < 3; ++k) c.supplied_dims[k] = dims[k];
-  if (r->shadow.current.mode == OVR_HIP_SHADOWS_SUPPLIED) r->fb_reset = true; // another shadow term: the accumulation starts over
+  commit::Changes ch;
+  ch.note(commit::kShadowValues, true, r->shadow.current.mode == OVR_HIP_SHADOWS_SUPPLIED);
+  apply_effects(r, commit::plan_commit(ch, commit::CommitFacts()));
   return 0;
 }
 } // namespace
@@ -504,7 +507,9 @@ int ovr_hip_set_noise_tile(ovr_hip_renderer* r, const float* tile, int32_t xy)
   HIP_TRY(hipMalloc((void**)&r->d_noise, bytes));
   HIP_TRY(hipMemcpy(r->d_noise, tr.data(), bytes, hipMemcpyHostToDevice));
   r->noise_xy = xy;
-  r->fb_reset = true;
+  commit::Changes ch;
+  ch.happened(commit::kNoiseTile);
+  apply_effects(r, commit::plan_commit(ch, commit::CommitFacts()));
   if (r->group.members.size() > 1)
     if (int e = group_call(r, [=](ovr_hip_renderer* m) { return ovr_hip_set_noise_tile(m, tile, xy); })) return e;
   return 0;
@@ -537,15 +542,32 @@ int commit_one(ovr_hip_renderer* r);
 // what every member of a group must agree on after a commit (each applied its own copy of the queued values)
 bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
 {
-  return a->fbsize.current.w == b->fbsize.current.w && a->fbsize.current.h == b->fbsize.current.h && std::memcmp(&a->camera.current, &b->camera.current, sizeof(CameraP)) == 0
-         && a->spp.current == b->spp.current && a->sparse.current == b->sparse.current && a->accumulate.current == b->accumulate.current && a->shading.current == b->shading.current
-         && a->rate.current == b->rate.current && a->jitter.current == b->jitter.current && a->grid_convention.current == b->grid_convention.current
-         && a->tfn.current.lo == b->tfn.current.lo && a->tfn.current.hi == b->tfn.current.hi && a->tfn.current.colors == b->tfn.current.colors && a->tfn.current.alphas == b->tfn.current.alphas
-         && std::memcmp(&a->focus.current, &b->focus.current, sizeof(FocusP)) == 0 && a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw
-         && a->shard.current.th == b->shard.current.th && a->have_tfn == b->have_tfn && a->convergence.current.mode == b->convergence.current.mode
-         && a->convergence.current.threshold == b->convergence.current.threshold && std::memcmp(&a->light.current, &b->light.current, sizeof(LightP)) == 0
-         && std::memcmp(&a->material.current, &b->material.current, sizeof(MaterialP)) == 0 && std::memcmp(&a->clip.current, &b->clip.current, sizeof(ClipP)) == 0
-         && a->shadow.current.mode == b->shadow.current.mode && a->shadow.current.cell == b->shadow.current.cell;
+  auto same_bytes = [](const auto& x, const auto& y) { return std::memcmp(&x, &y, sizeof(x)) == 0; };
+  // one comparison per forwarded parameter, in the order of commit_plan.hpp's table
+  if (a->fbsize.current.w != b->fbsize.current.w || a->fbsize.current.h != b->fbsize.current.h) return false;
+  if (!same_bytes(a->camera.current, b->camera.current)) return false;
+  const TfnP &ta = a->tfn.current, &tb = b->tfn.current;
+  if (!(ta.lo == tb.lo && ta.hi == tb.hi && ta.colors == tb.colors && ta.alphas == tb.alphas) || a->have_tfn != b->have_tfn) return false;
+  if (a->grid_convention.current != b->grid_convention.current) return false;
+  if (!same_bytes(a->focus.current, b->focus.current)) return false;
+  if (a->spp.current != b->spp.current) return false;
+  if (a->sparse.current != b->sparse.current) return false;
+  if (a->accumulate.current != b->accumulate.current) return false;
+  if (!(a->rate.current == b->rate.current)) return false;
+  if (a->shading.current != b->shading.current) return false;
+  if (a->jitter.current != b->jitter.current) return false;
+  if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
+  // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
+  if (!same_bytes(a->light.current, b->light.current)) return false;
+  if (!same_bytes(a->material.current, b->material.current)) return false;
+  if (!same_bytes(a->clip.current, b->clip.current)) return false;
+  if (a->shadow.current.mode != b->shadow.current.mode || a->shadow.current.cell != b->shadow.current.cell) return false;
+  // (LDS staging: not compared - the frame is the same either way)
+  // (layout choice: not compared - every layout gives the same frame; a member falls back to the general layout on its own)
+  // (pipeline: not compared - both pipelines give the same frame)
+  // (skipping: not compared - the frame is the same with or without)
+  // the shard: every member has its own rank; the world and the tile size are the group's
+  return a->shard.current.world == b->shard.current.world && a->shard.current.tw == b->shard.current.tw && a->shard.current.th == b->shard.current.th;
 }
 } // namespace
 extern "C" {
@@ -574,6 +596,92 @@ int ovr_hip_commit(ovr_hip_renderer* r)
 
 } // extern "C"
 namespace {
+// consumes one queued value: true if it was set.  Recorded: that, and whether the committed value differs byte for byte from the one before
+template <typename T> bool consume(commit::Changes& ch, commit::Source s, Queued<T>& q)
+{
+  if (!q.dirty) return false;
+  const T before = q.current;
+  q.update();
+  ch.note(s, true, std::memcmp(&before, &q.current, sizeof(T)) != 0);
+  return true;
+}
+bool consume(commit::Changes& ch, commit::Source s, Queued<TfnP>& q)
+{
+  if (!q.dirty) return false;
+  const TfnP before = q.current;
+  q.update();
+  const TfnP& now = q.current;
+  ch.note(s, true, std::memcmp(&before.lo, &now.lo, sizeof(float)) != 0 || std::memcmp(&before.hi, &now.hi, sizeof(float)) != 0 || before.colors != now.colors || before.alphas != now.alphas);
+  return true;
+}
+
+// the first part of a commit: every queued value, in today's order, with the steps that can fail (or touch the device) where the value is consumed
+int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
+{
+  using namespace commit;
+  if (consume(ch, kFramebuffer, r->fbsize)) // device_impl.cpp:116-122
+    if (int e = resize_framebuffers(r, r->fbsize.current.w, r->fbsize.current.h)) return e;
+  consume(ch, kCamera, r->camera); // :125-144
+  if (consume(ch, kTransferFunction, r->tfn)) { // :146-153
+    if (int e = upload_tfn(r)) return e;
+    update_tfn_range(r);
+  }
+  consume(ch, kGridConvention, r->grid_convention);
+  consume(ch, kFocus, r->focus);           // :155-168
+  consume(ch, kSpp, r->spp);               // :170-173
+  consume(ch, kSparse, r->sparse);         // :180-183
+  consume(ch, kAccumulation, r->accumulate); // :185-188
+  consume(ch, kSamplingRate, r->rate);     // :190-196
+  consume(ch, kShading, r->shading);
+  consume(ch, kJitter, r->jitter);
+  {
+    const int before = r->convergence.current.mode;
+    ch.note(kConvergence, r->convergence.update(), r->convergence.current.mode != before);
+    if (effects_of(ch, kConvergence) & kFreeConvergence) {
+      HIP_TRY(hipDeviceSynchronize());
+      if (int e = free_convergence(r)) return e;
+    }
+  }
+  if (consume(ch, kReconstruction, r->reconstruction) && (effects_of(ch, kReconstruction) & kFreeReconstruction)) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (int e = free_reconstruction(r)) return e;
+  }
+  {
+    const LightP before = r->light.current;
+    const bool set = r->light.update();
+    const LightP& now = r->light.current;
+    const V3 ub = unit_light(before), un = unit_light(now);
+    ch.note(kLightVector, set, std::memcmp(before.dir, now.dir, sizeof(now.dir)) != 0);
+    ch.note(kLightDirection, set, std::memcmp(&ub, &un, sizeof(V3)) != 0);
+    ch.note(kLightIntensity, set, std::memcmp(&before.intensity, &now.intensity, sizeof(float)) != 0);
+  }
+  consume(ch, kMaterial, r->material);
+  consume(ch, kClipBox, r->clip);
+  {
+    const ShadowP before = r->shadow.current;
+    const bool set = r->shadow.update();
+    const ShadowP& now = r->shadow.current;
+    const bool mode = before.mode != now.mode;
+    ch.note(kShadowMode, set, mode);
+    ch.note(kShadowCell, set, before.cell != now.cell);
+    ch.note(kShadowLeavesSupplied, set, mode && before.mode == OVR_HIP_SHADOWS_SUPPLIED);
+    ch.note(kShadowEntersMarched, set, mode && now.mode == OVR_HIP_SHADOWS_MARCHED);
+    const unsigned frees = effects_of(ch, kShadowLeavesSupplied) | effects_of(ch, kShadowEntersMarched);
+    if (frees) {
+      HIP_TRY(hipDeviceSynchronize());
+      ShadowCacheState& c = r->shadow_cache;
+      if ((frees & kFreeSuppliedLattice) && c.d_supplied) { HIP_TRY(hipFree(c.d_supplied)); c.d_supplied = nullptr; c.supplied_dims[0] = c.supplied_dims[1] = c.supplied_dims[2] = 0; }
+      if ((frees & kFreeBuiltLattice) && c.d_built) { HIP_TRY(hipFree(c.d_built)); c.d_built = nullptr; c.built_cap = 0; c.built_dims[0] = c.built_dims[1] = c.built_dims[2] = 0; }
+    }
+  }
+  consume(ch, kLdsStaging, r->lds_staging);
+  consume(ch, kLayoutChoice, r->layout_choice);
+  consume(ch, kPipeline, r->pipeline);
+  consume(ch, kSkipping, r->skipping);
+  consume(ch, kShard, r->shard);
+  return 0;
+}
+
 int commit_one(ovr_hip_renderer* r)
 {
   std::lock_guard<std::mutex> lk(r->mtx);
@@ -585,136 +693,17 @@ int commit_one(ovr_hip_renderer* r)
         r->fbsize.dirty = false; // (the value is consumed, like a real failure half-way through)
         return fail(OVR_HIP_EDEVICE, "[hip] commit failed on member " + std::string(t) + " (OVR_HIP_TEST_FAIL_MEMBER)");
       }
-  const bool reset_pending = r->fb_reset; // (without accumulation the flag is never consumed)
-  r->fb_reset = false;
-  bool fb_size_updated = false, camera_changed = false;
-  policy::ShadowCacheChange shadow_change; // what this commit changes, as the shadow cache's staleness rule reads it (policy::shadow_cache_stale)
-  if (r->fbsize.update()) { // device_impl.cpp:116-122
-    if (int e = resize_framebuffers(r, r->fbsize.current.w, r->fbsize.current.h)) return e;
-    fb_size_updated = true;
-    shadow_change.framebuffer = true;
-    r->fb_reset = true;
-  }
-  if (r->camera.update() || fb_size_updated || r->camera_dirty) { // :125-144
-    if (r->fbsize.current.w > 0 && r->fbsize.current.h > 0) {
-      update_camera(r);
-      r->camera_dirty = false;
-    }
-    r->sched.dirty = true;
-    r->fb_reset = true;
-    camera_changed = !fb_size_updated;
-    shadow_change.camera = true;
-  }
-  const bool only_camera_so_far = camera_changed;
-  if (camera_changed) r->fb_reset = false; // (restored below: the flag doubles as "something besides the camera changed")
-  if (r->tfn.update()) { // :146-153
-    if (int e = upload_tfn(r)) return e;
-    update_tfn_range(r);
-    r->mc_majorant_valid = false;
-    shadow_change.transfer_function = true;
-    r->fb_reset = true;
-  }
-  if (r->grid_convention.update()) {
-    shadow_change.grid_convention = true;
-    if (r->have_volume) update_volume_params(r);
-    r->sched.dirty = true;
-    r->fb_reset = true;
-  }
-  if (r->focus.update()) r->fb_reset = true;      // :155-168
-  if (r->spp.update()) { r->fb_reset = true; r->sched.dirty = true; shadow_change.spp = true; }        // :170-173 (one sample per pixel: the schedule knows every ray)
-  if (r->sparse.update()) { r->fb_reset = true; shadow_change.sparse = true; }           // :180-183
-  if (r->accumulate.update()) { r->fb_reset = true; shadow_change.accumulation = true; } // :185-188
-  { const float before = r->rate.current; if (r->rate.update()) { r->fb_reset = true; shadow_change.sampling_rate = r->rate.current != before; } } // :190-196
-  if (r->shading.update()) r->fb_reset = true;
-  if (r->jitter.update()) { r->fb_reset = true; r->sched.dirty = true; shadow_change.jitter = true; }
-  {
-    const int before = r->convergence.current.mode;
-    if (r->convergence.update()) { // any call resets the accumulation: retired blocks come back, the estimate starts over
-      r->fb_reset = true;
-      shadow_change.convergence = true;
-      if (r->convergence.current.mode != before) { // OFF keeps no buffer; the other two allocate what they need with their next frame
-        HIP_TRY(hipDeviceSynchronize());
-        if (int e = free_convergence(r)) return e;
-      }
-    }
-  }
-  {
-    const int before = r->reconstruction.current;
-    if (r->reconstruction.update()) { // any call resets the accumulation; OFF keeps no buffer, FILL allocates with its next sparse frame
-      r->fb_reset = true;
-      shadow_change.reconstruction = true;
-      if (r->reconstruction.current != before) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (int e = free_reconstruction(r)) return e;
-      }
-    }
-  }
-  // light and material: a changed value resets the accumulation (and with it the convergence estimate, the retired blocks and the reconstruction's counts)
-  // and, below, voids what the layout / pipeline tuner measured - shadow rays change their length with the light; the beam grid of the shade order is
-  // rebuilt from RayMarchParams::light with every frame (shade_order_params)
-  {
-    const LightP lb = r->light.current;
-    const MaterialP mb = r->material.current;
-    const bool lu = r->light.update(), mu = r->material.update();
-    if (lu || mu) {
-      const float3_ dir = r->P.light;
-      apply_lighting(r);
-      shadow_change.light_direction = std::memcmp(&dir, &r->P.light, sizeof(dir)) != 0; // the unit vector the shadow march runs along
-      shadow_change.light_intensity = lb.intensity != r->light.current.intensity;
-      shadow_change.material = std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0;
-      if (std::memcmp(&lb, &r->light.current, sizeof(LightP)) != 0 || std::memcmp(&mb, &r->material.current, sizeof(MaterialP)) != 0) r->fb_reset = true;
-    }
-  }
-  // clip box: a changed value resets the accumulation like a changed light, re-sorts the schedule (its block test is the clipped one) and, below, voids
-  // the tuner's measurement - a cut volume is another workload; the same value again resets nothing
-  {
-    const ClipP cb = r->clip.current;
-    if (r->clip.update()) {
-      apply_clip_box(r);
-      if (std::memcmp(&cb, &r->clip.current, sizeof(ClipP)) != 0) { r->fb_reset = true; r->sched.dirty = true; shadow_change.clip_box = true; }
-    }
-  }
-  // shadow cache: a changed mode or cell resets the accumulation like a changed light - another shadow term - and, below, a changed mode voids the tuner's
-  // measurement (a cached frame is another workload); the same value again resets nothing.  MARCHED keeps no buffer; the caller's values are kept until the
-  // mode leaves SUPPLIED
-  bool shadow_mode_changed = false;
-  {
-    const ShadowP sb = r->shadow.current;
-    if (r->shadow.update()) {
-      shadow_change.mode = shadow_mode_changed = sb.mode != r->shadow.current.mode;
-      shadow_change.cell = sb.cell != r->shadow.current.cell;
-      if (shadow_change.mode || shadow_change.cell) r->fb_reset = true;
-      if (shadow_change.mode && (sb.mode == OVR_HIP_SHADOWS_SUPPLIED || r->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED)) {
-        HIP_TRY(hipDeviceSynchronize());
-        ShadowCacheState& c = r->shadow_cache;
-        if (sb.mode == OVR_HIP_SHADOWS_SUPPLIED && c.d_supplied) { HIP_TRY(hipFree(c.d_supplied)); c.d_supplied = nullptr; c.supplied_dims[0] = c.supplied_dims[1] = c.supplied_dims[2] = 0; }
-        if (r->shadow.current.mode == OVR_HIP_SHADOWS_MARCHED && c.d_built) { HIP_TRY(hipFree(c.d_built)); c.d_built = nullptr; c.built_cap = 0; c.built_dims[0] = c.built_dims[1] = c.built_dims[2] = 0; }
-      }
-    }
-  }
-  if (policy::shadow_cache_stale(shadow_change)) r->shadow_cache.built_valid = false;
-  (void)r->lds_staging.update(); // same frame either way
-  // every layout and both pipelines give the same frame: no accumulation reset - but what was measured under the old setting is void
-  // (a probe must not override a layout forced meanwhile; forced -> automatic has to measure again)
-  bool tune_void = false;
-  { const int before = r->layout_choice.current; if (r->layout_choice.update() && r->layout_choice.current != before) { tune_void = true; shadow_change.layout_choice = true; } }
-  { const int before = r->pipeline.current; if (r->pipeline.update() && r->pipeline.current != before) { tune_void = true; shadow_change.pipeline = true; } }
-  if (shadow_mode_changed) tune_void = true;
-  if (r->skipping.update()) r->skip.restart(); // skipping does not change the frame either
-  if (r->shard.update()) {
-    r->sched.list_dirty = true;
-    r->fb_reset = true;
-  }
-  const bool other_changed = r->fb_reset;
-  if (other_changed || only_camera_so_far) {
-    r->sched.clear_gen++;        // ... and so is what the pixels of the blocks that are not launched hold
-    r->pool_roomy = false; // something changed: the next frame's request count is unknown
-    r->tune.configuration_changed(!other_changed); // only the camera moved: the measured layout / pipeline stay (policy::Tuner::recheck)
-  }
-  if (tune_void) r->tune.restart();
-  r->fb_reset = other_changed || only_camera_so_far || reset_pending;
-  if (r->fb_reset) { r->conv.valid = false; r->conv.retired = 0; r->conv.active = r->sched.n_work; }
-  return 0;
+  // what is consumed, in the reference's order (device_impl.cpp:113-197), is recorded; what follows from it is commit_plan.hpp's table.  A failed step
+  // ends the consumption there: what was consumed so far takes effect, and the accumulation starts over - the state is partly applied
+  commit::Changes ch;
+  const int e = consume_queued(r, ch);
+  commit::CommitFacts facts;
+  facts.reset_pending = r->fb_reset || e != 0; // (without accumulation the flag is never consumed)
+  facts.camera_dirty = r->camera_dirty;
+  facts.framebuffer = r->fbsize.current.w > 0 && r->fbsize.current.h > 0;
+  facts.volume = r->have_volume;
+  apply_effects(r, commit::plan_commit(ch, facts));
+  return e;
 }
 } // namespace
 extern "C" {

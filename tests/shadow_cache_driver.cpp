@@ -1,5 +1,5 @@
 // Driver of tests/test_shadow_cache_model.py: runs the shadow cache's host rules - csrc/host/launch_plan.hpp (which kernels a cached frame takes) and
-// csrc/host/policy.hpp (when a built lattice is stale) - on the CPU.  `driver <scenario>` exits 0 when every row of the scenario gave what it expects.
+// csrc/host/policy.hpp (the lattice's dimensions) - on the CPU.  `driver <scenario>` exits 0 when every row of the scenario gave what it expects.
 // The expectations are literals worked out from DESIGN.md section 14; none is computed by calling the headers.
 #include "launch_plan.hpp"
 #include "policy.hpp"
@@ -158,38 +158,10 @@ static void sweep()
   CHECK(!shade_variant_exists(1, 0, false, true, true, true), "a cached clipped shade kernel exists");
 }
 
-// the staleness table of DESIGN.md section 14: each change alone, and together with every change that does not count
+// the lattice's dimensions.  (When a built lattice is stale is a column of csrc/host/commit_plan.hpp's table: the staleness table that stood here - each
+// change alone, and together with every change that does not count - is tests/commit_plan_driver.cpp's scenario shadow_staleness, expectations intact.)
 static void staleness()
 {
-  using policy::ShadowCacheChange;
-  typedef bool ShadowCacheChange::*Flag;
-  struct Row { const char* what; Flag flag; bool stale; };
-  const Row rows[] = {
-    { "volume", &ShadowCacheChange::volume, true }, { "update_volume", &ShadowCacheChange::volume_update, true }, { "transfer function", &ShadowCacheChange::transfer_function, true },
-    { "sampling rate", &ShadowCacheChange::sampling_rate, true }, { "light direction", &ShadowCacheChange::light_direction, true }, { "clip box", &ShadowCacheChange::clip_box, true },
-    { "grid convention", &ShadowCacheChange::grid_convention, true }, { "cell", &ShadowCacheChange::cell, true }, { "mode", &ShadowCacheChange::mode, true },
-    { "camera", &ShadowCacheChange::camera, false }, { "framebuffer", &ShadowCacheChange::framebuffer, false }, { "spp", &ShadowCacheChange::spp, false },
-    { "jitter", &ShadowCacheChange::jitter, false }, { "material", &ShadowCacheChange::material, false }, { "light intensity", &ShadowCacheChange::light_intensity, false },
-    { "accumulation", &ShadowCacheChange::accumulation, false }, { "sparse sampling", &ShadowCacheChange::sparse, false }, { "convergence", &ShadowCacheChange::convergence, false },
-    { "reconstruction", &ShadowCacheChange::reconstruction, false }, { "layout choice", &ShadowCacheChange::layout_choice, false }, { "pipeline", &ShadowCacheChange::pipeline, false },
-    { "skipping", &ShadowCacheChange::skipping, false },
-  };
-  CHECK(!policy::shadow_cache_stale(ShadowCacheChange()), "nothing changed: stale");
-  ShadowCacheChange neutral;
-  for (const Row& r : rows)
-    if (!r.stale) neutral.*(r.flag) = true;
-  CHECK(!policy::shadow_cache_stale(neutral), "every change that does not count, together: stale");
-  int n_stale = 0;
-  for (const Row& r : rows) {
-    ShadowCacheChange c;
-    c.*(r.flag) = true;
-    CHECK(policy::shadow_cache_stale(c) == r.stale, "%s alone: stale %d, expected %d", r.what, (int)policy::shadow_cache_stale(c), (int)r.stale);
-    ShadowCacheChange d = neutral;
-    d.*(r.flag) = true;
-    CHECK(policy::shadow_cache_stale(d) == r.stale, "%s with the neutral changes: stale %d, expected %d", r.what, (int)policy::shadow_cache_stale(d), (int)r.stale);
-    n_stale += r.stale;
-  }
-  CHECK(n_stale == 9 && sizeof(rows) / sizeof(rows[0]) == 22 && sizeof(ShadowCacheChange) == 22, "the table lists every flag (%zu flags)", sizeof(ShadowCacheChange));
   // lattice dimensions: ceil(dim / cell) + 1
   CHECK(policy::shadow_cache_nodes(32, 2) == 17 && policy::shadow_cache_nodes(32, 4) == 9 && policy::shadow_cache_nodes(40, 3) == 15 && policy::shadow_cache_nodes(20, 3) == 8
           && policy::shadow_cache_nodes(1, 4) == 2 && policy::shadow_cache_nodes(1024, 1) == 1025 && policy::shadow_cache_nodes(33, 32) == 3,

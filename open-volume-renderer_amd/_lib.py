@@ -22,6 +22,7 @@ JITTER_TEA, JITTER_BLUE_NOISE = 0, 1
 CONVERGENCE_OFF, CONVERGENCE_ESTIMATE, CONVERGENCE_ADAPTIVE = 0, 1, 2
 RECONSTRUCT_OFF, RECONSTRUCT_FILL = 0, 1
 SHADOWS_MARCHED, SHADOWS_CACHED, SHADOWS_SUPPLIED = 0, 1, 2
+PROJECT_OFF, PROJECT_MAXIMUM, PROJECT_MINIMUM, PROJECT_MEAN = 0, 1, 2, 3
 LAYOUT_AUTO, LAYOUT_GENERAL, LAYOUT_THIN, LAYOUT_THIN_T, LAYOUT_QUAD = -1, 0, 1, 2, 3
 # the ABI these ctypes structures describe: load() refuses a library of another version (ovr_hip_get_stats would write past them)
 EXPECTED_ABI = 11
@@ -126,6 +127,13 @@ class ShadowCache(C.Structure):
     ]
 
 
+class Projection(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("range_skipping", C.c_int32),
+    ]
+
+
 # every symbol include/ovr_hip.h declares: name -> (restype, argtypes)
 _F3 = C.POINTER(C.c_float)
 _H = C.c_void_p
@@ -202,6 +210,9 @@ SYMBOLS = {
     "ovr_hip_get_shadow_cache": (C.c_int, [_H, C.POINTER(ShadowCache)]),
     "ovr_hip_get_shadow_cache_values": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), _F3, _F3, C.c_size_t]),
     "ovr_hip_shadow_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_projection": (C.c_int, [_H, C.c_int32]),
+    "ovr_hip_get_projection": (C.c_int, [_H, C.POINTER(Projection)]),
+    "ovr_hip_project_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "ovr_hip_update_volume": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ovr_hip_get_update_times": (C.c_int, [_H, C.POINTER(C.c_double)]),

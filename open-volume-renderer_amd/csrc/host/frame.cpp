@@ -275,6 +275,20 @@ static void choose_layout(ovr_hip_renderer* r, hipStream_t st)
   r->stats.layout = choice;
 }
 
+// step 3 of a projection frame (ovr_hip_set_projection): the general layout, whatever the layout choice - the tuner is not consulted
+static void bind_general_layout(ovr_hip_renderer* r)
+{
+  RayMarchParams& P = r->P;
+  const float vs = P.vol.value_scale, vm = P.vol.value_min_clamp;
+  P.vol = r->vd_replica[LAYOUT_GENERAL];
+  P.vol.value_scale = vs;
+  P.vol.value_min_clamp = vm;
+  r->stats.layout = LAYOUT_GENERAL;
+  r->tune.frame = -1; // nothing the layout / pipeline tuner could time
+}
+
+const float* projection_ranges(const ovr_hip_renderer* r) { return r->have_volume && r->mc_ranges_valid ? r->d_mc_minmax : nullptr; }
+
 // step 2, continued: tables, shard, jitter, counters
 static int fill_table_params(ovr_hip_renderer* r)
 {
@@ -298,6 +312,8 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.majorant = nullptr;
   P.occupancy = nullptr;
   P.occupancy_fine = nullptr;
+  P.projection = r->projection.current;
+  P.mc_ranges = nullptr;
   return 0;
 }
 
@@ -306,7 +322,12 @@ static int fill_table_params(ovr_hip_renderer* r)
 static int choose_skipping(ovr_hip_renderer* r, FrameSetup& f)
 {
   RayMarchParams& P = r->P;
-  f.use_skip = r->skip.before_frame(r->skipping.current != 0, r->mc_majorant_valid);
+  // a projection frame skips by the macrocells' value ranges, which need no majorants: the adaptive-skipping probe is not consulted
+  if (P.projection != OVR_HIP_PROJECT_OFF) {
+    f.use_skip = false;
+    if (r->skipping.current != 0) P.mc_ranges = projection_ranges(r);
+  }
+  else f.use_skip = r->skip.before_frame(r->skipping.current != 0, r->mc_majorant_valid);
   if (f.use_skip) {
     if (int e = update_macrocells(r, f.st)) return e;
     P.majorant = r->d_mc_majorant;
@@ -429,7 +450,7 @@ static int prepare_pool(ovr_hip_renderer* r, const FrameSetup& f)
 {
   RayMarchParams& P = r->P;
   const size_t n = f.n;
-  const bool want_pool = r->auto_pipe.want_pool(P.shading, r->pipeline.current, r->tune.measured_pipeline());
+  const bool want_pool = P.projection == OVR_HIP_PROJECT_OFF && r->auto_pipe.want_pool(P.shading, r->pipeline.current, r->tune.measured_pipeline()); // (a projection: in place)
   P.pool = PoolDesc{};
   if (want_pool) {
     size_t guess = policy::pool_first_guess(n, r->pool_tiles); // grown after an overflow (resolve_pool)
@@ -600,12 +621,13 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  choose_layout(r, st);
+  if (r->projection.current != OVR_HIP_PROJECT_OFF) bind_general_layout(r);
+  else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
   // the shadow cache: a frame with full shading reads the lattice of a mode other than MARCHED (built here, in front of the frame, when it is stale)
   r->P.shadow_lattice = nullptr;
-  if (r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
+  if (r->P.projection == OVR_HIP_PROJECT_OFF && r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
     if (int e = ensure_shadow_cache(r, r->P, st)) return e;
   f.conv_on = r->convergence.current.mode != OVR_HIP_CONVERGENCE_OFF && f.accumulate && !f.sparse;
   r->P.accum_half = nullptr; // (before launch_clear_blocks: H is cleared with A)
@@ -770,6 +792,10 @@ static int read_frame_stats(ovr_hip_renderer* r)
   r->stats.frame_index = r->frame_index;
   r->sparse_prev_pixels = r->P.sparse_xy ? r->stats.active_pixels : 0;
   r->stats.skipping_kernels = r->skip.frame_used ? 1 : 0;
+  if (r->plan.project.mode != 0) { // a projection frame: which kernel ran; the adaptive-skipping probe had no say
+    r->projection_skipped = r->plan.project.skip;
+    r->stats.skipping_kernels = r->plan.project.skip ? 1 : 0;
+  }
   r->stats.replicas_building = poll_replica_builds(r);
   (void)hipGetLastError(); // hipErrorNotReady of the query is not an error
   return 0;
@@ -858,10 +884,13 @@ int finish_frame_one(ovr_hip_renderer* r)
   r->stats.stale_tiles = 0;
   if (int e = resolve_pool(r)) return e;
   if (int e = read_frame_stats(r)) return e;
-  const policy::FrameWork w = frame_work(r);
-  tune_after_frame(r, w);
-  r->auto_pipe.after_frame(w); // automatic shading pipeline of the next frame
-  r->skip.after_frame(w);      // did skipping pay?
+  if (r->plan.project.mode != 0) r->stats.tuning = 0; // a projection frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
+  else {
+    const policy::FrameWork w = frame_work(r);
+    tune_after_frame(r, w);
+    r->auto_pipe.after_frame(w); // automatic shading pipeline of the next frame
+    r->skip.after_frame(w);      // did skipping pay?
+  }
   if (r->conv.frame)
     if (int e = read_convergence(r)) return e;
   if (int e = read_reconstruction(r)) return e;

@@ -57,6 +57,18 @@ constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material,
   return !clipped || (shade == 2 && material); // clipped where the shade kernel marches shadow rays, on the material variant
 }
 
+// project_kernel<VT, am, mode, skip, clipped> (open-volume-renderer_amd/projection.py is the arithmetic): the projections of the general
+// layouts - mode 1 maximum, 2 minimum, 3 mean (include/ovr_hip.h OVR_HIP_PROJECT_*).  skip: the range-skipping twin, which only an extremum has (a mean needs
+// every sample); am == 4 only for the layouts row_load_layout names, like the march
+constexpr int kProjectMaximum = 1, kProjectMinimum = 2, kProjectMean = 3;
+constexpr int kProjectK = 4; // instructions (x 4 steps) per round, the unshaded march's
+constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped)
+{
+  (void)clipped; // both box tests exist for every variant
+  if (mode < kProjectMaximum || mode > kProjectMean || am < 0 || am > 4) return false;
+  return !skip || mode != kProjectMean;
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -103,6 +115,8 @@ struct LaunchFacts {
   int shade_blocks = 0;               // 0 = the default
   bool reference_material = true, shade_order = false; // the material is the reference's; the pool has an order buffer
   bool shadow_cache = false;          // a valid shadow lattice is bound (RayMarchParams::shadow_lattice): a frame with full shading reads it
+  int projection = 0;                 // 0: the march; 1 ... 3: a projection frame (kProjectMaximum ...) - shading, pool, majorants and LDS staging are not read
+  bool ranges = false;                // the macrocells' value ranges are bound (RayMarchParams::mc_ranges): an extremum may skip by them
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -115,6 +129,8 @@ struct LaunchPlan {
   struct Shade { bool material = false, clipped = false; } shade;
   bool shade_order = false;           // the shade kernel meets the runs sorted by light beam (PoolDesc::order)
   bool cached = false;                // the kernels that shade take the shadow term from the lattice: SHADE 1, material, no box test while shading
+  // a projection frame (LaunchFacts::projection != 0): project_kernel in the march's place, nothing else of the plan but `am` is read
+  struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
   size_t march_lds_bytes = 0, shade_lds_bytes = 0;
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
@@ -132,8 +148,30 @@ inline bool deep_rounds_pay(const LaunchFacts& f, const LaunchOverrides& o)
   return f.world > 1 && f.n_blocks_owned <= kDeepMaxBlocks;
 }
 
+// a projection frame: the general layout's addressing (the same rule, override and row loads as the march), one kernel, in place.  The transfer function is
+// read from global memory, once per ray: LDS holds the axis tables alone (and the counter reduction's words)
+inline LaunchPlan plan_projection(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
+  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
+  if (f.projection < kProjectMaximum || f.projection > kProjectMean || f.quad || (am < 3 && !f.tables) || (!f.sparse && f.n_schedule > 0 && !f.schedule)) {
+    pl.error = true;
+    return pl;
+  }
+  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
+  pl.am = am;
+  pl.project.mode = f.projection;
+  pl.project.skip = f.ranges && f.projection != kProjectMean;
+  pl.project.clipped = f.clip_on;
+  pl.project.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
+  pl.march_lds_bytes = pl.project.lds_bytes; // project_kernel takes the in-place march's place in the launch sequence
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
+  if (f.projection != 0) return plan_projection(f, o);
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   // the shadow cache: full shading without the shadow march is the gradient-shaded kernel plus one tap - everything below follows from SHADE 1 (no clipped

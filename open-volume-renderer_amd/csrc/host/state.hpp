@@ -203,6 +203,8 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::TfnP> tfn;
   Queued<ovrhip::host::FocusP> focus;
   Queued<int> spp, sparse, accumulate, shading, grid_convention, pipeline, skipping, jitter, lds_staging;
+  Queued<int> projection;   // ovr_hip_set_projection: OVR_HIP_PROJECT_*; recorded under the commit plan's source kShading
+  bool projection_skipped = false; // the last projection frame ran the range-skipping kernel (ovr_hip_get_projection)
   Queued<float> rate;
   Queued<ovrhip::host::ShardP> shard;
   Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (unit_light)
@@ -387,6 +389,8 @@ int finish_frame_one(ovr_hip_renderer* r);
 // the shadow cache: the parameters the shadow march reads as the next frame would set them (general layout, sampling rate, transfer function) into q; the lattice
 // the next cached frame reads bound into q - mode CACHED builds it first if it is stale, on st, and waits for it
 void fill_shadow_params(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
+// the macrocells' value ranges for a range-skipping projection: valid whenever a volume is resident (the upload and ovr_hip_update_volume keep them current)
+const float* projection_ranges(const ovr_hip_renderer* r);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -235,12 +235,21 @@ OVR_SIMPLE_SETTER(ovr_hip_set_volume_sampling_rate, rate, float, v > 0.f, "[hip]
 OVR_SIMPLE_SETTER(ovr_hip_set_frame_accumulation, accumulate, int32_t, true, "")
 OVR_SIMPLE_SETTER(ovr_hip_set_sparse_sampling, sparse, int32_t, true, "")
 OVR_SIMPLE_SETTER(ovr_hip_set_shading, shading, int32_t, v >= 0 && v <= 2, "[hip] unknown shading mode")
+OVR_SIMPLE_SETTER(ovr_hip_set_projection, projection, int32_t, v >= OVR_HIP_PROJECT_OFF && v <= OVR_HIP_PROJECT_MEAN, "[hip] ovr_hip_set_projection: unknown mode")
 OVR_SIMPLE_SETTER(ovr_hip_set_shading_pipeline, pipeline, int32_t, v >= 0 && v <= 2, "[hip] unknown shading pipeline")
 OVR_SIMPLE_SETTER(ovr_hip_set_empty_space_skipping, skipping, int32_t, true, "")
 OVR_SIMPLE_SETTER(ovr_hip_set_volume_layouts, layouts, int32_t, v >= 0 && v <= 2, "[hip] unknown volume-layout mode")
 OVR_SIMPLE_SETTER(ovr_hip_set_layout_choice, layout_choice, int32_t, v >= -1 && v < kLayouts, "[hip] unknown layout choice")
 OVR_SIMPLE_SETTER(ovr_hip_set_lds_staging, lds_staging, int32_t, v == 0 || v == 1, "[hip] unknown LDS-staging mode")
 OVR_SIMPLE_SETTER(ovr_hip_set_pixel_jitter, jitter, int32_t, v == 0 || v == 1, "[hip] unknown pixel-jitter mode")
+
+int ovr_hip_get_projection(const ovr_hip_renderer* r, ovr_hip_projection* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_projection: null argument");
+  out->mode = r->projection.current;
+  out->range_skipping = r->projection_skipped ? 1 : 0;
+  return 0;
+}
 
 int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold)
 {
@@ -554,7 +563,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (a->sparse.current != b->sparse.current) return false;
   if (a->accumulate.current != b->accumulate.current) return false;
   if (!(a->rate.current == b->rate.current)) return false;
-  if (a->shading.current != b->shading.current) return false;
+  if (a->shading.current != b->shading.current || a->projection.current != b->projection.current) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -632,7 +641,11 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
   consume(ch, kSparse, r->sparse);         // :180-183
   consume(ch, kAccumulation, r->accumulate); // :185-188
   consume(ch, kSamplingRate, r->rate);     // :190-196
-  consume(ch, kShading, r->shading);
+  { // the projection mode is recorded with the shading mode: set if either setter was called, differs if either value differs
+    const int shading = r->shading.current, projection = r->projection.current;
+    const bool set_s = r->shading.update(), set_p = r->projection.update();
+    ch.note(kShading, set_s || set_p, shading != r->shading.current || projection != r->projection.current);
+  }
   consume(ch, kJitter, r->jitter);
   {
     const int before = r->convergence.current.mode;
@@ -1177,6 +1190,21 @@ int ovr_hip_shadow_floats(ovr_hip_renderer* r, const float* pos, float* out, int
     HIP_TRY(launch_shadow_lookup(q, pos, out, n, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t mode, int32_t range_skipping)
+{
+  if (!r || !org || !dir || !out || n < 0 || mode < OVR_HIP_PROJECT_MAXIMUM || mode > OVR_HIP_PROJECT_MEAN) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_project_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: no volume was set");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
+  q.mc_ranges = projection_ranges(r);
+  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: the resident volume has no macrocell ranges");
+  HIP_TRY(launch_project_floats(q, org, dir, out, n, mode, range_skipping != 0 && mode != OVR_HIP_PROJECT_MEAN, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }
 

@@ -2047,6 +2047,302 @@ ShadowCacheKernel shadow_cache_kernel_of(int am)
   return nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// projections (include/ovr_hip.h ovr_hip_set_projection; open-volume-renderer_amd/projection.py is the normative arithmetic): per ray the
+// maximum, the minimum or the mean of the samples the unshaded march would classify - the march without its sequential part: no opacity recurrence, no early
+// termination, no pow, no transfer-function lookup per sample, ONE classification per ray (read from global memory: 64 rays x 6 loads per workgroup against
+// 20 KB of staged tables; LDS holds the axis tables alone).  The work decomposition is the march's: four lanes per ray = four consecutive steps (the quad
+// coalescing of the texture addresser, raymarch_kernel's header), every lane runs the (tx, ty) recurrence, a round = kProjectK instructions x 4 steps with all
+// its voxel loads in flight before the first is consumed.  Lane `sub` owns the steps i with i & 3 == sub: its running extremum (first of equal samples: the
+// strict comparison) or its sum IS the definition's accumulator A[i & 3]; the quad is combined once, behind the loop.
+// SKIP (maximum / minimum): a step's fetch is dropped when the value range of its tap's macrocell (RayMarchParams::mc_ranges, tap_cell) proves that the sample
+// cannot replace the extremum.  Two things make the test exact rather than approximate:
+//  * the filter rounds: a sample can leave the range of the voxels it reads.  range_slack bounds by how much (derivation: DESIGN.md section 16) - three levels of
+//    fmaf(f, b - a, a), each off by at most u (width + magnitude) with u = 2^-24, the 8-bit types' normalisation behind the filter and the rounding of the bound
+//    itself: below 7 u (W + M), taken as 2^-21 (W + M) so that the product is exact, plus FLT_MIN for gradual underflow;
+//  * ties decide tm*: the bound is the quad's extremum over the rounds BEFORE this one (shared with DPP quad broadcasts between rounds, as the march shares
+//    opacities) - every step it comes from is earlier than every step of this round, so an equal sample never replaces it and `<=` is exact.  What another lane
+//    finds in the SAME round is not used as a bound (it is not earlier; it would need the strict comparison and a second exchange per round).
+// The frame, the layer and samples + skipped_samples are bit for bit the non-skipping kernel's.  Measured: profiles/r14_projection.md.
+// ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float range_slack(float lo, float hi) { return fmaf(0x1p-21f, (hi - lo) + fmaxf(fabsf(lo), fabsf(hi)), FLT_MIN); }
+
+struct ProjectResult {
+  float v, tm;                          // the projected value and the distance of the sample that set it (0 for the mean); quad-uniform
+  unsigned int steps;                   // n, quad-uniform
+  unsigned int fetched, skipped;        // THIS LANE's steps whose voxels were fetched / whose fetch was skipped
+};
+
+// the ray org + t dir (world space, as the march forms it) over [t0, t1]; live: the ray is marched (quad-uniform)
+template <int VT, int AM, int MODE, bool SKIP>
+__device__ __forceinline__ ProjectResult project_ray(const RayMarchParams& P, const VolConsts& vc, const MarchConsts& mc, f3 org, f3 dir, float t0, float t1, bool live,
+                                                     const SubMask& subm)
+{
+  static_assert(project_variant_exists(MODE, AM, SKIP, false), "no such variant of the projection (host/launch_plan.hpp)");
+  constexpr int K = kProjectK;
+  constexpr bool MAXI = MODE == kProjectMaximum, MEAN = MODE == kProjectMean;
+  const int sub = subm.sub;
+  float m = MAXI ? -__builtin_inff() : __builtin_inff(), tmb = 0.f; // this lane's extremum over its own steps
+  float bound = m;                                                   // SKIP: the quad's extremum over the earlier rounds
+  float acc = 0.f;                                                   // mean: A[sub]
+  unsigned int own = 0, fetched = 0, skipped = 0;
+  float tx = t0, ty = fminf(t1, t0 + mc.step);
+  while (__ballot(live) != 0ull) {
+    unsigned int vmask = 0;
+    float tms[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float txq[4], tyq[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        txq[b] = tx; tyq[b] = ty;
+        vmask |= (ty > tx) ? (1u << (4 * k + b)) : 0u;
+        tx = ty;
+        ty = fminf(tx + mc.step, t1);
+      }
+      tms[k] = 0.5f * (sel4(txq[0], txq[1], txq[2], txq[3], subm) + sel4(tyq[0], tyq[1], tyq[2], tyq[3], subm));
+    }
+    Tap taps[K];
+    bool fetch[K];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const f3 pos = mk3(fmaf(tms[k], dir.x, org.x), fmaf(tms[k], dir.y, org.y), fmaf(tms[k], dir.z, org.z));
+      if (SKIP) taps[k] = Tap{}; // (a tap that is not fetched is finished all the same, and dropped)
+      tap_coords(vc, to_object(mc, pos), taps[k]);
+      const bool mine = live && ((vmask >> (4 * k + sub)) & 1u) != 0u;
+      fetch[k] = mine;
+      if (SKIP) {
+        const float2 r = reinterpret_cast<const float2*>(P.mc_ranges)[tap_cell(vc, taps[k])];
+        const float sl = range_slack(r.x, r.y);
+        const bool cannot = MAXI ? (r.y + sl <= bound) : (r.x - sl >= bound); // (a NaN range proves nothing)
+        fetch[k] = mine && !cannot;
+        skipped += (mine && cannot) ? 1u : 0u;
+      }
+      own += mine ? 1u : 0u;
+      fetched += fetch[k] ? 1u : 0u;
+      any = any || fetch[k];
+    }
+    live = live && ((vmask >> (4 * K - 1)) & 1u) != 0u; // validity is monotone: the round's last step decides whether another round exists
+    if (SKIP) {
+      if (__ballot(any) == 0ull) continue; // nothing to fetch for any lane of the wave: the extrema stand
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        if (fetch[k]) tap_loads<VT, AM>(vc, taps[k]);
+    }
+    else {
+      // branch-free, like the march: dead lanes load (their coordinates are clamped, the loads are in bounds) and drop the value
+#pragma unroll
+      for (int k = 0; k < K; ++k) tap_loads<VT, AM>(vc, taps[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float s = tap_finish<VT>(vc, taps[k]);
+      if (MEAN) acc = fetch[k] ? acc + s : acc;
+      else {
+        const bool take = fetch[k] && (MAXI ? s > m : s < m); // strict: of equal samples the first stays; a NaN is never selected
+        m = take ? s : m;
+        tmb = take ? tms[k] : tmb;
+      }
+    }
+    if (SKIP) {
+      const float b0 = quad_bcast<0>(m), b1 = quad_bcast<1>(m), b2 = quad_bcast<2>(m), b3 = quad_bcast<3>(m);
+      bound = MAXI ? fmaxf(fmaxf(b0, b1), fmaxf(b2, b3)) : fminf(fminf(b0, b1), fminf(b2, b3));
+    }
+  }
+  ProjectResult res;
+  {
+    const float o = __uint_as_float(own);
+    res.steps = __float_as_uint(quad_bcast<0>(o)) + __float_as_uint(quad_bcast<1>(o)) + __float_as_uint(quad_bcast<2>(o)) + __float_as_uint(quad_bcast<3>(o));
+  }
+  res.fetched = fetched;
+  res.skipped = skipped;
+  if (MEAN) {
+    const float a0 = quad_bcast<0>(acc), a1 = quad_bcast<1>(acc), a2 = quad_bcast<2>(acc), a3 = quad_bcast<3>(acc);
+    res.v = ((a0 + a1) + (a2 + a3)) / (float)res.steps;
+    res.tm = 0.f;
+  }
+  else {
+    // the larger (smaller) value; of equal values the smaller tm - the earlier step
+    float bv = quad_bcast<0>(m), bt = quad_bcast<0>(tmb);
+#define OVR_COMBINE(B)                                                                                                 \
+    {                                                                                                                  \
+      const float cv = quad_bcast<B>(m), ct = quad_bcast<B>(tmb);                                                      \
+      const bool take = (MAXI ? cv > bv : cv < bv) || (cv == bv && ct < bt);                                           \
+      bv = take ? cv : bv;                                                                                             \
+      bt = take ? ct : bt;                                                                                             \
+    }
+    OVR_COMBINE(1) OVR_COMBINE(2) OVR_COMBINE(3)
+#undef OVR_COMBINE
+    res.v = bv;
+    res.tm = bt;
+  }
+  return res;
+}
+
+// the classification of a projected value, once per ray, from the tables in global memory: the march's tf_coord and nodal lerps (the pair (i0, min(i0 + 1,
+// n - 1)) is the padded tables' (i0, i0 + 1): i0 = n - 1 only for a fraction of 0)
+__device__ __forceinline__ float4 project_classify(const RayMarchParams& P, float v)
+{
+  const float c = clamp01((fminf(fmaxf(v, P.tf_lower), P.tf_upper) - P.tf_lower) * P.tf_scale);
+  const int nc1 = P.n_color - 1, na1 = P.n_alpha - 1;
+  const float xc = c * (float)nc1, xa = c * (float)na1;
+  const int ic = (int)xc, ia = (int)xa;
+  const float fc = __builtin_amdgcn_fractf(xc), fa = __builtin_amdgcn_fractf(xa);
+  const float4* col = reinterpret_cast<const float4*>(P.tf_color);
+  const float4 a = col[ic], b = col[min(ic + 1, nc1)];
+  return make_float4(clamp01(lerpf(a.x, b.x, fc)), clamp01(lerpf(a.y, b.y, fc)), clamp01(lerpf(a.z, b.z, fc)), lerpf(P.tf_alpha[ia], P.tf_alpha[min(ia + 1, na1)], fa));
+}
+
+// a projection frame: the march's pixels, block schedule, sparse list, samples per pixel, jitter and write_pixel around project_ray; the buffer mapframe hands
+// out as `grad` carries the projection layer (v, tm*, 1).  No request queue, no alpha, no occupancy attribute (none is measured to pay)
+template <int VT, int AM, int MODE, bool SKIP, bool CLIP>
+__global__ __launch_bounds__(kBlock) void project_kernel(const RayMarchParams P)
+{
+  static_assert(project_variant_exists(MODE, AM, SKIP, CLIP) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the projection (host/launch_plan.hpp)");
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & 3;
+  const bool owner = sub == 0;
+  const SubMask subm = make_submask(sub);
+  int ix, iy;
+  const bool active = assign_pixel_quad(P, lane, wave, ix, iy);
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  if (__syncthreads_or(active ? 1 : 0) != 0) {
+    stage_tables<VT, AM>(P, lds_raw, vc);
+    __syncthreads();
+  }
+  else {
+    vc.tab_x = vc.tab_y = vc.tab_z = nullptr;
+    vc.tab_z64 = nullptr;
+  }
+  unsigned int n_rays = 0, n_samples = 0, n_skipped = 0, n_outside_hits = 0;
+  const float rsx = 1.f / (float)P.width, rsy = 1.f / (float)P.height;
+  const float scx = ((float)ix + .5f) * rsx, scy = ((float)iy + .5f) * rsy;
+  const unsigned int pixel_index = (unsigned int)ix + (unsigned int)iy * (unsigned int)P.width;
+  unsigned int v0 = (unsigned int)P.frame_index, v1 = pixel_index; // RandomTEA(frame_index, pixel_index)
+  const f3 org = ld3(P.cam_pos), cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
+  const f3 oo = to_object(mc, org);
+  float o_a = 0.f;
+  f3 o_c = mk3(0, 0, 0), o_g = mk3(0, 0, 0);
+  for (int k_spp = 0; k_spp < P.spp; ++k_spp) { // uniform trip count
+    float sx = scx, sy = scy;
+    if (P.jitter_mode == 1) {
+      float j0, j1;
+      jitter_global(P, ix, iy, k_spp, j0, j1);
+      sx += (j0 - 0.5f) * rsx;
+      sy += (j1 - 0.5f) * rsy;
+    }
+    else if (P.spp > 1) {
+      tea16(v0, v1);
+      sx += ((float)v0 * OVR_TEA_TOFLOAT - 0.5f) * rsx;
+      sy += ((float)v1 * OVR_TEA_TOFLOAT - 0.5f) * rsy;
+    }
+    const float ux = sx - 0.5f, uy = sy - 0.5f;
+    const f3 dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y, cdir.z + ux * chor.z + uy * cver.z));
+    const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
+    float t0 = 0.f, t1 = FLT_MAX;
+    const bool live = active && box_test<CLIP>(P, t0, t1, oo, od);
+    if (active && owner) ++n_rays;
+    if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
+    const ProjectResult pr = project_ray<VT, AM, MODE, SKIP>(P, vc, mc, org, dir, t0, t1, live, subm);
+    n_samples += pr.fetched;
+    n_skipped += pr.skipped;
+    if (live && owner && pr.steps > 0u) {
+      const float4 c = project_classify(P, pr.v);
+      o_c.x += c.x; o_c.y += c.y; o_c.z += c.z;
+      o_a += c.w;
+      o_g.x += pr.v; o_g.y += pr.tm; o_g.z += 1.f;
+    }
+  }
+  if (active && owner) {
+    const float rspp = 1.f / (float)P.spp;
+    o_a *= rspp;
+    o_c.x *= rspp; o_c.y *= rspp; o_c.z *= rspp;
+    o_g.x *= rspp; o_g.y *= rspp; o_g.z *= rspp;
+    write_pixel(P, pixel_index, o_c, o_a, o_g);
+  }
+  store_block_counters(P, reinterpret_cast<unsigned int*>(lds_raw), lane, wave, n_rays, n_samples, 0u, 0u, (active && owner) ? 1u : 0u, n_skipped, 0u, n_outside_hits);
+}
+
+// the known-answer entry's kernel: ray i = the quad of lanes 4 i ... 4 i + 3, through project_ray as the frame's kernel calls it.  The clipped box test alone: the
+// bounds (0, 1) without a clip box give the unclipped test's bits
+template <int VT, int AM, int MODE, bool SKIP>
+__global__ __launch_bounds__(kBlock) void project_floats_kernel(const RayMarchParams P, const float* org, const float* dir, float* out, long long n)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int sub = threadIdx.x & 3;
+  const SubMask subm = make_submask(sub);
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  stage_tables<VT, AM>(P, lds_raw, vc);
+  __syncthreads();
+  const long long i = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 2;
+  const bool valid = i < n;
+  const long long j = valid ? i : 0;
+  const f3 o = mk3(org[3 * j], org[3 * j + 1], org[3 * j + 2]), d = mk3(dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
+  const f3 oo = to_object(mc, o), od = mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z);
+  float t0 = 0.f, t1 = FLT_MAX;
+  const bool live = valid && box_test<true>(P, t0, t1, oo, od);
+  const ProjectResult pr = project_ray<VT, AM, MODE, SKIP>(P, vc, mc, o, d, t0, t1, live, subm);
+  const float f = __uint_as_float(pr.fetched);
+  const unsigned int fetched = __float_as_uint(quad_bcast<0>(f)) + __float_as_uint(quad_bcast<1>(f)) + __float_as_uint(quad_bcast<2>(f)) + __float_as_uint(quad_bcast<3>(f));
+  if (valid && sub == 0) {
+    const bool hit = live && pr.steps > 0u;
+    out[4 * i] = hit ? pr.v : 0.f; out[4 * i + 1] = hit ? pr.tm : 0.f;
+    out[4 * i + 2] = hit ? (float)pr.steps : 0.f; out[4 * i + 3] = hit ? (float)fetched : 0.f;
+  }
+}
+
+typedef void (*ProjectFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
+struct ProjectKernels { FrameKernel frame = nullptr; ProjectFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
+template <int VT, int AM, int MODE>
+inline ProjectKernels project_kernels_of(bool skip, bool clipped)
+{
+  ProjectKernels k;
+  if constexpr (MODE != kProjectMean) {
+    if (skip) {
+      k.frame = clipped ? project_kernel<VT, AM, MODE, true, true> : project_kernel<VT, AM, MODE, true, false>;
+      k.floats = project_floats_kernel<VT, AM, MODE, true>;
+      return k;
+    }
+  }
+  if (skip) return k;
+  k.frame = clipped ? project_kernel<VT, AM, MODE, false, true> : project_kernel<VT, AM, MODE, false, false>;
+  k.floats = project_floats_kernel<VT, AM, MODE, false>;
+  return k;
+}
+template <int VT, int AM>
+inline ProjectKernels project_kernels_of(int mode, bool skip, bool clipped)
+{
+  switch (mode) {
+  case kProjectMaximum: return project_kernels_of<VT, AM, kProjectMaximum>(skip, clipped);
+  case kProjectMinimum: return project_kernels_of<VT, AM, kProjectMinimum>(skip, clipped);
+  case kProjectMean: return project_kernels_of<VT, AM, kProjectMean>(skip, clipped);
+  default: return ProjectKernels();
+  }
+}
+// the projection kernels of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads), like shadow_cache_kernel_of
+template <int VT>
+ProjectKernels project_kernels_of(int am, int mode, bool skip, bool clipped)
+{
+  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
+    switch (am) {
+    case 0: return project_kernels_of<VT, 0>(mode, skip, clipped);
+    case 1: return project_kernels_of<VT, 1>(mode, skip, clipped);
+    case 2: return project_kernels_of<VT, 2>(mode, skip, clipped);
+    case 3: return project_kernels_of<VT, 3>(mode, skip, clipped);
+    case 4:
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return project_kernels_of<VT, 4>(mode, skip, clipped);
+      else return ProjectKernels();
+    }
+  }
+  return ProjectKernels();
+}
+
 // one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~160 kernel
 // variants of a type compile in parallel with the other types
 template <int VT>

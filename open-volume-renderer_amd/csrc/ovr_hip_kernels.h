@@ -256,6 +256,11 @@ struct RayMarchParams {
   // read them, and the host launches those only with a valid lattice bound (null = none; the kernels do not test the pointer)
   const float* shadow_lattice;
   int shadow_n1[3];
+  // projection (ovr_hip_set_projection; open-volume-renderer_amd/projection.py is the arithmetic): 0 = the march, 1 ... 3 = the frame is project_kernel's (maximum,
+  // minimum, mean), and the macrocells' value ranges (min, max per 16^3 cell, x fastest) the range-skipping instantiations read (null = no skipping).  Behind
+  // everything else, like the material, the clip box and the lattice: no kernel that existed before reads them
+  int projection;
+  const float* mc_ranges;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -301,6 +306,11 @@ hipError_t launch_schedule(const RayMarchParams& p, const unsigned int* src, uns
                            hipStream_t stream);
 // zero the pixels (RGBA, gradient layer, optionally the accumulation buffer) of `n` blocks that are not launched: what their rays' miss would write
 hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* blocks, unsigned int n, int clear_accum, hipStream_t stream);
+
+// known-answer entry of the projections (project_ray in ovr_hip_device.h, the function project_kernel calls): n world-space rays (origin, direction - used as given) ->
+// 4 floats each: v, tm*, steps, fetched steps (four zeros for a ray that is not marched), four lanes per ray.  p.vol: the general layout; p.mc_ranges: the ranges
+// if range_skipping (hipErrorInvalidValue without them, for a replica's type or a mode outside 1 ... 3)
+hipError_t launch_project_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int mode, int range_skipping, hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

@@ -989,6 +989,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.row_loads = p.row_loads; f.shade_blocks = p.shade_blocks;
   f.reference_material = reference_material(p); f.shade_order = p.pool.order != nullptr;
   f.shadow_cache = p.shadow_lattice != nullptr;
+  f.projection = p.projection; f.ranges = p.mc_ranges != nullptr;
   return plan_launch(f, o);
 }
 
@@ -1047,12 +1048,25 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   return hipGetLastError();
 }
 
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template ProjectKernels project_kernels_of<E>(int, int, bool, bool);
+OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+static ProjectKernels project_kernels(const RayMarchParams& p, const LaunchPlan& plan)
+{
+  ProjectKernels k;
+  if (!plan.error) dispatch_voxel_type(p.vol.type, [&](auto vt) { k = project_kernels_of<decltype(vt)::value>(plan.am, plan.project.mode, plan.project.skip, plan.project.clipped); });
+  return k;
+}
+
 hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipStream_t stream, const hipEvent_t* ev)
 {
   // ev (optional): ev[0] before the first kernel, ev[1] after the march, ev[2] after the shade kernel (both may be null: no per-phase times), ev[3] at the end
   if (ev) (void)hipEventRecord(ev[0], stream);
   FrameKernels k;
-  dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
+  // a projection frame: project_kernel in the in-place march's place (its plan is neither pooled nor LDS-staged, march_lds_bytes is the projection's), then
+  // the same reduction and publish steps
+  if (plan.project.mode != 0) k.march = project_kernels(p, plan).frame;
+  else dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
   const hipError_t e = k.march && (k.shade || !plan.pooled) ? launch_sequence(p, plan, k, stream, ev) : hipErrorInvalidValue;
   if (ev) (void)hipEventRecord(ev[3], stream);
   return e;
@@ -2039,6 +2053,25 @@ hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float
   if (n <= 0) return hipSuccess;
   if (!p.shadow_lattice) return hipErrorInvalidValue;
   hipLaunchKernelGGL(shadow_lookup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, pos, out, (long long)n);
+  return hipGetLastError();
+}
+
+// known-answer entry of the projections: the kernel of the general layout's type at the addressing mode a projection frame takes for it
+hipError_t launch_project_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int mode, int range_skipping, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if (range_skipping && !p.mc_ranges) return hipErrorInvalidValue;
+  RayMarchParams q = p;
+  q.projection = mode; q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  if (!range_skipping) q.mc_ranges = nullptr;
+  const LaunchPlan pl = plan_raymarch(q);
+  const ProjectFloatsKernel kern = project_kernels(q, pl).floats;
+  if (!kern) return hipErrorInvalidValue;
+  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  if (pl.project.lds_bytes > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.project.lds_bytes)) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.project.lds_bytes, stream, q, org, dir, out, (long long)n);
   return hipGetLastError();
 }
 

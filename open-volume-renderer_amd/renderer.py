@@ -327,6 +327,33 @@ class DeviceHIP:
         L.check(self._lib.ovr_hip_shadow_floats(self._h, t.data_ptr(), out.data_ptr(), n, int(which)))
         return out.cpu().numpy()
 
+    # projections (include/ovr_hip.h ovr_hip_set_projection; projection.py is the arithmetic): the maximum, minimum or mean of the samples along each ray in the
+    # march's place; the buffer mapframe hands out as `grad` carries the projection layer (v, tm*, 1).  Queued, applied at commit; every call resets the accumulation.
+    def set_projection(self, mode):
+        """0 off - the march, the default -, 1 maximum, 2 minimum, 3 mean intensity projection (PROJECT_*)"""
+        L.check(self._lib.ovr_hip_set_projection(self._h, int(mode)))
+
+    def get_projection(self):
+        """ovr_hip_projection, the COMMITTED state: mode, range_skipping (1: the last projection frame ran the range-skipping kernel)"""
+        c = L.Projection()
+        L.check(self._lib.ovr_hip_get_projection(self._h, C.byref(c)))
+        return c
+
+    def project_rays(self, org, direction, mode, range_skipping=False):
+        """a projection as the kernels evaluate it (ovr_hip_project_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
+        v (n,), tm* (n,) float32, steps (n,), fetched steps (n,) int64, with the committed volume, sampling rate and clip box; zeros for a ray that is not marched"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("project_rays: org and direction hold three floats per ray")
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_project_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(mode), int(bool(range_skipping))))
+        o = out.cpu().numpy()
+        return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].astype(np.int64), o[:, 3].astype(np.int64)
+
     # ---- extensions of this backend ----------------------------------------------------------------------------
     def set_shading(self, mode):
         L.check(self._lib.ovr_hip_set_shading(self._h, int(mode)))

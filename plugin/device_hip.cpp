@@ -177,6 +177,15 @@ public:
         check(ovr_hip_set_shadow_cache(h, OVR_HIP_SHADOWS_CACHED, cell));
         if (!quiet) std::fprintf(stderr, "[hip] shadow cache: one node per %d voxels%s\n", cell > 0 ? cell : 4, cell > 0 ? "" : " (the default)");
       }
+      // Projections (ovr_hip_set_projection): OVR_HIP_PROJECTION=max|min|mean renders the maximum, minimum or mean intensity projection in the march's
+      // place, classified by the scene's transfer function.  Unset: nothing is called, the frames are the march's
+      if (const char* pv = std::getenv("OVR_HIP_PROJECTION")) {
+        const std::string p(pv);
+        const int mode = p == "max" ? OVR_HIP_PROJECT_MAXIMUM : p == "min" ? OVR_HIP_PROJECT_MINIMUM : p == "mean" ? OVR_HIP_PROJECT_MEAN : -1;
+        if (mode < 0) throw std::runtime_error("[hip] OVR_HIP_PROJECTION expects max, min or mean");
+        check(ovr_hip_set_projection(h, mode));
+        if (!quiet) std::fprintf(stderr, "[hip] projection: %s intensity\n", p == "max" ? "maximum" : p == "min" ? "minimum" : "mean");
+      }
     }
     commit();
   }

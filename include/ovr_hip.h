@@ -408,6 +408,39 @@ typedef struct ovr_hip_projection {
 /* the COMMITTED state, not the queued one */
 int ovr_hip_get_projection(const ovr_hip_renderer* r, ovr_hip_projection* out);
 
+/* Isosurfaces (added within ABI v11 like the projections: new entry points and one new struct only).  Opaque, shaded, hard-shadowed level
+ * sets of the resident volume for up to OVR_HIP_MAX_ISOVALUES isovalues, drawn in the march's place; open-volume-renderer_amd/isosurface.py is the arithmetic in
+ * numpy, the normative text.  Isovalues are in the units of the projection layer's v and of ovr_hip_get_macrocells: 16-bit and float types raw, 8-bit types
+ * normalised.  The setter stores them sorted ascending.
+ *   ray, steps, samples   exactly the projection's (tm_i, s_i; the clipped box test while a clip box is committed).
+ *   hit      side(s) = #{k : iso_k <= s} (a NaN: 0); the hit is the first step i >= 1 with side(s_{i-1}) != side(s_i).  No caps: a box face or a clip face is no
+ *            surface, a ray that starts inside a solid hits where it leaves it.  Rising: the lowest isovalue crossed, falling: the highest.  The walk ends there.
+ *   t*       two rounds of four points (0.2, 0.4, 0.6, 0.8 of the interval, the first sub-interval whose ends lie on different sides), then the secant, clamped to it.
+ *   normal   the march's forward difference at pos* = fmaf(t*, dir, org), normalised, negated, to world space.
+ *   shadow   under OVR_HIP_SHADE_FULL: 1 iff two consecutive samples of the ray pos* + t light, stepped from 1.5 steps on, differ in side - a hard shadow cast by the
+ *            level sets themselves, not by the transfer function's opacity; else 0.
+ *   pixel    a miss: zeros.  A hit: rgb = the colour table at the isovalue (the alpha table is not read) - as it is under OVR_HIP_SHADE_NONE, times the shade factor
+ *            of the committed light and material (clamped) under GRADIENT / FULL -, a = 1; the layer (`grad`) is (isovalue, t*, 1).  Samples per pixel and accumulated
+ *            frames combine as the march's do; everything behind the pixel works unchanged.
+ * While n > 0 is committed frames are isosurface frames: a committed projection mode is kept but not drawn and resumes at n = 0.  Like a projection frame an
+ * isosurface frame reads the general layout (stats.layout = 0, pipeline = 1, tuning = 0; tuner and adaptive-skipping probe neither asked nor fed) and ignores shadow
+ * cache, pipeline, LDS staging and layout choice; it honours shading mode, light, material, clip box and ovr_hip_set_empty_space_skipping: while that is committed
+ * a step's fetch is dropped when no isovalue lies in its macrocell's value range (widened by the projections' rounding slack) - on volumes of finite voxels the frame,
+ * the layer, shaded_samples and samples + skipped_samples are bit for bit the non-skipping kernel's.  Counters: samples / skipped_samples = the steps walked, fetched /
+ * not fetched; shaded_samples = hits; shadow_samples / skipped_shadow_samples = the shadow walks' steps; refinement and gradient taps are not counted.
+ * Queued, applied at commit; EVERY call resets the accumulation, like ovr_hip_set_shading.  n = 0 (the default) is off: until the setter is called with n > 0 every
+ * frame, counter and kernel is what it was without it.  EINVAL (the state stays): n < 0 or n > OVR_HIP_MAX_ISOVALUES, a null pointer with n > 0, a non-finite
+ * value, two equal values.  A device group forwards the call. */
+#define OVR_HIP_MAX_ISOVALUES 4
+int ovr_hip_set_isosurfaces(ovr_hip_renderer* r, const float* isovalues, int32_t n);
+typedef struct ovr_hip_isosurfaces {
+  int32_t n;                                   /* the COMMITTED isovalues, ascending; the entries behind n are 0 */
+  float isovalues[OVR_HIP_MAX_ISOVALUES];
+  int32_t range_skipping;                      /* 1: the last isosurface frame ran the range-skipping kernel */
+} ovr_hip_isosurfaces;
+/* the COMMITTED state, not the queued one */
+int ovr_hip_get_isosurfaces(const ovr_hip_renderer* r, ovr_hip_isosurfaces* out);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -557,6 +590,11 @@ int ovr_hip_shadow_floats(ovr_hip_renderer* r, const float* pos_device, float* o
  * tables as empty, which can pick another addressing mode than a frame's - every mode gives the same values).  ESTATE without a volume; EINVAL: a null
  * pointer, n < 0, mode not in 1 ... 3. */
 int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t mode, int32_t range_skipping);
+/* an isosurface ray as the kernels evaluate it (added with the isosurfaces): n world-space rays as for ovr_hip_project_floats -> 8 floats each (device buffers):
+ * hit (0 / 1), isovalue, t*, steps walked, the world normal (x, y, z), the shadow term - through the device function the isosurface frame's kernel calls under full
+ * shading (normal and shadow are always computed), with the COMMITTED isovalues, volume transform, sampling rate, light and clip box; a ray without a hit gives zeros
+ * but for the steps walked.  range_skipping comes from the argument.  ESTATE without a volume or while no isovalue is committed; EINVAL: a null pointer, n < 0. */
+int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t range_skipping);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,17 @@ class Projection(C.Structure):
     ]
 
 
+MAX_ISOVALUES = 4
+
+
+class Isosurfaces(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("isovalues", C.c_float * MAX_ISOVALUES),
+        ("range_skipping", C.c_int32),
+    ]
+
+
 # every symbol include/ovr_hip.h declares: name -> (restype, argtypes)
 _F3 = C.POINTER(C.c_float)
 _H = C.c_void_p
@@ -213,6 +224,9 @@ SYMBOLS = {
     "ovr_hip_set_projection": (C.c_int, [_H, C.c_int32]),
     "ovr_hip_get_projection": (C.c_int, [_H, C.POINTER(Projection)]),
     "ovr_hip_project_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
+    "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
+    "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "ovr_hip_update_volume": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ovr_hip_get_update_times": (C.c_int, [_H, C.POINTER(C.c_double)]),

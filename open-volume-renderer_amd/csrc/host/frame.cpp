@@ -289,6 +289,15 @@ static void bind_general_layout(ovr_hip_renderer* r)
 
 const float* projection_ranges(const ovr_hip_renderer* r) { return r->have_volume && r->mc_ranges_valid ? r->d_mc_minmax : nullptr; }
 
+void fill_isosurface_params(const ovr_hip_renderer* r, RayMarchParams& q)
+{
+  const IsoP& p = r->isosurfaces.current;
+  q.iso_n = p.n;
+  for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) q.iso_values[k] = k < p.n ? p.v[k] : 0.f;
+}
+// a frame drawn by one kernel in the march's place, from the general layout: a projection or the isosurfaces
+static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0; }
+
 // step 2, continued: tables, shard, jitter, counters
 static int fill_table_params(ovr_hip_renderer* r)
 {
@@ -314,6 +323,7 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.occupancy_fine = nullptr;
   P.projection = r->projection.current;
   P.mc_ranges = nullptr;
+  fill_isosurface_params(r, P);
   return 0;
 }
 
@@ -322,8 +332,8 @@ static int fill_table_params(ovr_hip_renderer* r)
 static int choose_skipping(ovr_hip_renderer* r, FrameSetup& f)
 {
   RayMarchParams& P = r->P;
-  // a projection frame skips by the macrocells' value ranges, which need no majorants: the adaptive-skipping probe is not consulted
-  if (P.projection != OVR_HIP_PROJECT_OFF) {
+  // a projection or isosurface frame skips by the macrocells' value ranges, which need no majorants: the adaptive-skipping probe is not consulted
+  if (in_place_frame(P)) {
     f.use_skip = false;
     if (r->skipping.current != 0) P.mc_ranges = projection_ranges(r);
   }
@@ -450,7 +460,7 @@ static int prepare_pool(ovr_hip_renderer* r, const FrameSetup& f)
 {
   RayMarchParams& P = r->P;
   const size_t n = f.n;
-  const bool want_pool = P.projection == OVR_HIP_PROJECT_OFF && r->auto_pipe.want_pool(P.shading, r->pipeline.current, r->tune.measured_pipeline()); // (a projection: in place)
+  const bool want_pool = !in_place_frame(P) && r->auto_pipe.want_pool(P.shading, r->pipeline.current, r->tune.measured_pipeline()); // (a projection: in place)
   P.pool = PoolDesc{};
   if (want_pool) {
     size_t guess = policy::pool_first_guess(n, r->pool_tiles); // grown after an overflow (resolve_pool)
@@ -621,13 +631,13 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  if (r->projection.current != OVR_HIP_PROJECT_OFF) bind_general_layout(r);
+  if (r->projection.current != OVR_HIP_PROJECT_OFF || r->isosurfaces.current.n > 0) bind_general_layout(r);
   else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
   // the shadow cache: a frame with full shading reads the lattice of a mode other than MARCHED (built here, in front of the frame, when it is stale)
   r->P.shadow_lattice = nullptr;
-  if (r->P.projection == OVR_HIP_PROJECT_OFF && r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
+  if (!in_place_frame(r->P) && r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
     if (int e = ensure_shadow_cache(r, r->P, st)) return e;
   f.conv_on = r->convergence.current.mode != OVR_HIP_CONVERGENCE_OFF && f.accumulate && !f.sparse;
   r->P.accum_half = nullptr; // (before launch_clear_blocks: H is cleared with A)
@@ -796,6 +806,10 @@ static int read_frame_stats(ovr_hip_renderer* r)
     r->projection_skipped = r->plan.project.skip;
     r->stats.skipping_kernels = r->plan.project.skip ? 1 : 0;
   }
+  if (r->plan.isosurface.on) { // an isosurface frame, likewise
+    r->isosurface_skipped = r->plan.isosurface.skip;
+    r->stats.skipping_kernels = r->plan.isosurface.skip ? 1 : 0;
+  }
   r->stats.replicas_building = poll_replica_builds(r);
   (void)hipGetLastError(); // hipErrorNotReady of the query is not an error
   return 0;
@@ -884,7 +898,7 @@ int finish_frame_one(ovr_hip_renderer* r)
   r->stats.stale_tiles = 0;
   if (int e = resolve_pool(r)) return e;
   if (int e = read_frame_stats(r)) return e;
-  if (r->plan.project.mode != 0) r->stats.tuning = 0; // a projection frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
+  if (r->plan.project.mode != 0 || r->plan.isosurface.on) r->stats.tuning = 0; // a projection or isosurface frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
   else {
     const policy::FrameWork w = frame_work(r);
     tune_after_frame(r, w);

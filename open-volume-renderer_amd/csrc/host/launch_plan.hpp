@@ -69,6 +69,16 @@ constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped)
   return !skip || mode != kProjectMean;
 }
 
+// isosurface_kernel<VT, am, shade, skip, clipped> (open-volume-renderer_amd/isosurface.py is the arithmetic): opaque level sets of the general
+// layouts for up to kMaxIsovalues isovalues.  shade: the committed shading mode (0 colour alone, 1 gradient-shaded, 2 with the hard shadow walk); skip: the
+// range-skipping twin, which every shading mode has (primary and shadow walk skip alike); the material is a run-time argument, not a variant
+constexpr int kMaxIsovalues = 4; // include/ovr_hip.h OVR_HIP_MAX_ISOVALUES
+constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped)
+{
+  (void)skip; (void)clipped; // both walks and both box tests exist for every variant
+  return shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -117,6 +127,7 @@ struct LaunchFacts {
   bool shadow_cache = false;          // a valid shadow lattice is bound (RayMarchParams::shadow_lattice): a frame with full shading reads it
   int projection = 0;                 // 0: the march; 1 ... 3: a projection frame (kProjectMaximum ...) - shading, pool, majorants and LDS staging are not read
   bool ranges = false;                // the macrocells' value ranges are bound (RayMarchParams::mc_ranges): an extremum may skip by them
+  int isosurfaces = 0;                // the number of committed isovalues; > 0: an isosurface frame - `projection` is kept but not drawn, pool, majorants and LDS staging are not read
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -131,6 +142,8 @@ struct LaunchPlan {
   bool cached = false;                // the kernels that shade take the shadow term from the lattice: SHADE 1, material, no box test while shading
   // a projection frame (LaunchFacts::projection != 0): project_kernel in the march's place, nothing else of the plan but `am` is read
   struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
+  // an isosurface frame (LaunchFacts::isosurfaces > 0): isosurface_kernel in the march's place, nothing else of the plan but `am` and `shading` is read
+  struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; } isosurface;
   size_t march_lds_bytes = 0, shade_lds_bytes = 0;
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
@@ -169,8 +182,31 @@ inline LaunchPlan plan_projection(const LaunchFacts& f, const LaunchOverrides& o
   return pl;
 }
 
+// an isosurface frame: plan_projection's addressing and LDS (the axis tables alone; the colour of a hit is read from global memory), the committed shading
+// mode as the kernel's, the skipping twin whenever the ranges are bound
+inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
+  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
+  if (f.isosurfaces < 1 || f.isosurfaces > kMaxIsovalues || f.quad || (am < 3 && !f.tables) || (!f.sparse && f.n_schedule > 0 && !f.schedule)) {
+    pl.error = true;
+    return pl;
+  }
+  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
+  pl.am = am;
+  pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  pl.isosurface.on = true;
+  pl.isosurface.skip = f.ranges;
+  pl.isosurface.clipped = f.clip_on;
+  pl.isosurface.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
+  pl.march_lds_bytes = pl.isosurface.lds_bytes; // isosurface_kernel takes the in-place march's place in the launch sequence
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
+  if (f.isosurfaces != 0) return plan_isosurface(f, o); // a committed projection mode is kept but not drawn
   if (f.projection != 0) return plan_projection(f, o);
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;

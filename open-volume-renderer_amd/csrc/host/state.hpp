@@ -67,6 +67,7 @@ struct TfnP { std::vector<float> colors, alphas; float lo = 1, hi = -1; };
 struct ShardP { int rank = 0, world = 1, tw = 64, th = 64; };
 struct Size2 { int w = 0, h = 0; };
 struct ConvP { int mode = OVR_HIP_CONVERGENCE_OFF; float threshold = 0.f; };
+struct IsoP { int n = 0; float v[OVR_HIP_MAX_ISOVALUES] = { 0.f, 0.f, 0.f, 0.f }; };
 // ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
 // and the 0.5 / 0.5 of its shade expression (shaders_raymarching.cu:138,156-157)
 struct LightP { float dir[3] = { -907.108f, 2205.875f, -400.0267f }; float intensity = 1.f; };
@@ -205,6 +206,8 @@ struct ovr_hip_renderer {
   Queued<int> spp, sparse, accumulate, shading, grid_convention, pipeline, skipping, jitter, lds_staging;
   Queued<int> projection;   // ovr_hip_set_projection: OVR_HIP_PROJECT_*; recorded under the commit plan's source kShading
   bool projection_skipped = false; // the last projection frame ran the range-skipping kernel (ovr_hip_get_projection)
+  Queued<ovrhip::host::IsoP> isosurfaces; // ovr_hip_set_isosurfaces: sorted ascending; recorded under kShading like the projection mode.  n > 0: isosurface frames
+  bool isosurface_skipped = false; // the last isosurface frame ran the range-skipping kernel (ovr_hip_get_isosurfaces)
   Queued<float> rate;
   Queued<ovrhip::host::ShardP> shard;
   Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (unit_light)
@@ -391,6 +394,8 @@ int finish_frame_one(ovr_hip_renderer* r);
 void fill_shadow_params(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 // the macrocells' value ranges for a range-skipping projection: valid whenever a volume is resident (the upload and ovr_hip_update_volume keep them current)
 const float* projection_ranges(const ovr_hip_renderer* r);
+// the committed isovalues into a frame's parameters (iso_n = 0: no isosurface frame)
+void fill_isosurface_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -251,6 +251,35 @@ int ovr_hip_get_projection(const ovr_hip_renderer* r, ovr_hip_projection* out)
   return 0;
 }
 
+int ovr_hip_set_isosurfaces(ovr_hip_renderer* r, const float* isovalues, int32_t n)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (n < 0 || n > OVR_HIP_MAX_ISOVALUES || (n > 0 && !isovalues)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: between 0 and 4 isovalues");
+  IsoP p;
+  p.n = n;
+  for (int k = 0; k < n; ++k) {
+    if (!std::isfinite(isovalues[k])) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: the isovalues must be finite");
+    p.v[k] = isovalues[k];
+  }
+  std::sort(p.v, p.v + n);
+  for (int k = 1; k < n; ++k)
+    if (p.v[k] == p.v[k - 1]) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: two isovalues are equal");
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->isosurfaces.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_isosurfaces(m, isovalues, n));
+  return 0;
+}
+
+int ovr_hip_get_isosurfaces(const ovr_hip_renderer* r, ovr_hip_isosurfaces* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_isosurfaces: null argument");
+  const IsoP& p = r->isosurfaces.current;
+  out->n = p.n;
+  for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) out->isovalues[k] = k < p.n ? p.v[k] : 0.f;
+  out->range_skipping = r->isosurface_skipped ? 1 : 0;
+  return 0;
+}
+
 int ovr_hip_set_convergence(ovr_hip_renderer* r, int32_t mode, float threshold)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -564,6 +593,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (a->accumulate.current != b->accumulate.current) return false;
   if (!(a->rate.current == b->rate.current)) return false;
   if (a->shading.current != b->shading.current || a->projection.current != b->projection.current) return false;
+  if (!same_bytes(a->isosurfaces.current, b->isosurfaces.current)) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -641,10 +671,12 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
   consume(ch, kSparse, r->sparse);         // :180-183
   consume(ch, kAccumulation, r->accumulate); // :185-188
   consume(ch, kSamplingRate, r->rate);     // :190-196
-  { // the projection mode is recorded with the shading mode: set if either setter was called, differs if either value differs
+  { // the projection mode and the isovalues are recorded with the shading mode: set if any of the setters was called, differs if any value differs
     const int shading = r->shading.current, projection = r->projection.current;
-    const bool set_s = r->shading.update(), set_p = r->projection.update();
-    ch.note(kShading, set_s || set_p, shading != r->shading.current || projection != r->projection.current);
+    const IsoP iso = r->isosurfaces.current;
+    const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update();
+    ch.note(kShading, set_s || set_p || set_i,
+            shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0);
   }
   consume(ch, kJitter, r->jitter);
   {
@@ -1204,6 +1236,23 @@ int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org, const float* d
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_project_floats(q, org, dir, out, n, mode, range_skipping != 0 && mode != OVR_HIP_PROJECT_MEAN, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)
+{
+  if (!r || !org || !dir || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: no volume was set");
+  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: no isovalue is committed (ovr_hip_set_isosurfaces)");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
+  fill_isosurface_params(r, q);
+  q.mc_ranges = projection_ranges(r);
+  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: the resident volume has no macrocell ranges");
+  HIP_TRY(launch_isosurface_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

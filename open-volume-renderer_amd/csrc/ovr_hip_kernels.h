@@ -261,6 +261,10 @@ struct RayMarchParams {
   // everything else, like the material, the clip box and the lattice: no kernel that existed before reads them
   int projection;
   const float* mc_ranges;
+  // isosurfaces (ovr_hip_set_isosurfaces; open-volume-renderer_amd/isosurface.py is the arithmetic): iso_n > 0 = the frame is isosurface_kernel's; the isovalues
+  // ascending, the entries behind iso_n unread.  Behind everything else, like the projection: no kernel that existed before reads them
+  int iso_n;
+  float iso_values[4];
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -311,6 +315,11 @@ hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* bloc
 // 4 floats each: v, tm*, steps, fetched steps (four zeros for a ray that is not marched), four lanes per ray.  p.vol: the general layout; p.mc_ranges: the ranges
 // if range_skipping (hipErrorInvalidValue without them, for a replica's type or a mode outside 1 ... 3)
 hipError_t launch_project_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int mode, int range_skipping, hipStream_t stream);
+
+// known-answer entry of the isosurfaces (isosurface_ray in ovr_hip_device.h, the function isosurface_kernel calls, with full shading): n world-space rays -> 8 floats
+// each: hit, isovalue, t*, steps walked, the world normal, the shadow term (zeros for a ray without a hit, but the steps walked), four lanes per ray.  p.iso_n /
+// p.iso_values: the isovalues; p.mc_ranges: the ranges if range_skipping (hipErrorInvalidValue without them, without isovalues or for a replica's type)
+hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

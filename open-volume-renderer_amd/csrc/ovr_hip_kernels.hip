@@ -990,6 +990,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.reference_material = reference_material(p); f.shade_order = p.pool.order != nullptr;
   f.shadow_cache = p.shadow_lattice != nullptr;
   f.projection = p.projection; f.ranges = p.mc_ranges != nullptr;
+  f.isosurfaces = p.iso_n;
   return plan_launch(f, o);
 }
 
@@ -1058,6 +1059,18 @@ static ProjectKernels project_kernels(const RayMarchParams& p, const LaunchPlan&
   return k;
 }
 
+// (the isosurface kernels exist for the general layout's types alone: ovr_hip_isosurface.hip, one object per such type)
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceKernels isosurface_kernels_of<E>(int, int, bool, bool);
+OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+static IsosurfaceKernels isosurface_kernels(const RayMarchParams& p, const LaunchPlan& plan)
+{
+  IsosurfaceKernels k;
+  if (!plan.error && plan.isosurface.on)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.isosurface.clipped); });
+  return k;
+}
+
 hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipStream_t stream, const hipEvent_t* ev)
 {
   // ev (optional): ev[0] before the first kernel, ev[1] after the march, ev[2] after the shade kernel (both may be null: no per-phase times), ev[3] at the end
@@ -1065,7 +1078,8 @@ hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipS
   FrameKernels k;
   // a projection frame: project_kernel in the in-place march's place (its plan is neither pooled nor LDS-staged, march_lds_bytes is the projection's), then
   // the same reduction and publish steps
-  if (plan.project.mode != 0) k.march = project_kernels(p, plan).frame;
+  if (plan.isosurface.on) k.march = isosurface_kernels(p, plan).frame; // an isosurface frame: the same place, the same steps behind it
+  else if (plan.project.mode != 0) k.march = project_kernels(p, plan).frame;
   else dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
   const hipError_t e = k.march && (k.shade || !plan.pooled) ? launch_sequence(p, plan, k, stream, ev) : hipErrorInvalidValue;
   if (ev) (void)hipEventRecord(ev[3], stream);
@@ -2018,6 +2032,7 @@ hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a
   RayMarchParams q = p;
   q.shading = 0; q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
   q.shadow_lattice = nullptr;
+  q.iso_n = 0; // (p may be a frame's parameters: the plan asked here is the march's, whatever the last frame drew)
   const LaunchPlan pl = plan_raymarch(q);
   if (pl.error) return hipErrorInvalidValue;
   ShadowCacheKernel kern = nullptr;
@@ -2062,7 +2077,8 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
   if (n <= 0) return hipSuccess;
   if (range_skipping && !p.mc_ranges) return hipErrorInvalidValue;
   RayMarchParams q = p;
-  q.projection = mode; q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  q.projection = mode; q.iso_n = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
+  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
   if (!range_skipping) q.mc_ranges = nullptr;
   const LaunchPlan pl = plan_raymarch(q);
   const ProjectFloatsKernel kern = project_kernels(q, pl).floats;
@@ -2072,6 +2088,25 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
   if (pl.project.lds_bytes > 64 * 1024)
     if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.project.lds_bytes)) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.project.lds_bytes, stream, q, org, dir, out, (long long)n);
+  return hipGetLastError();
+}
+
+// known-answer entry of the isosurfaces: the kernel of the general layout's type at the addressing mode an isosurface frame takes for it
+hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues) return hipErrorInvalidValue;
+  RayMarchParams q = p;
+  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  if (!range_skipping) q.mc_ranges = nullptr;
+  const LaunchPlan pl = plan_raymarch(q);
+  const IsosurfaceFloatsKernel kern = isosurface_kernels(q, pl).floats;
+  if (!kern) return hipErrorInvalidValue;
+  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  if (pl.isosurface.lds_bytes > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.isosurface.lds_bytes)) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.isosurface.lds_bytes, stream, q, org, dir, out, (long long)n);
   return hipGetLastError();
 }
 

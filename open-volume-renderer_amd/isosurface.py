@@ -1,0 +1,248 @@
+"""The isosurfaces of the HIP backend (include/ovr_hip.h, ovr_hip_set_isosurfaces) as a numpy model: the normative text.
+
+Opaque, shaded, hard-shadowed level sets of the resident volume for up to four isovalues iso_0 < iso_1 < ..., drawn in the march's place.  Everything is
+float32; fma is lighting.fma, every other operation rounds on its own.  The ray, the steps tm_i and the samples s_i are the projection's (projection.py:
+`pixel_rays`, `steps`, `sample`), with the clipped box test while a clip box is committed.
+
+Side       side(s) = #{k : iso_k <= s}; a NaN compares false, its side is 0.
+Hit        the first step i >= 1 with side(s_{i-1}) != side(s_i).  No caps: a box face or a clip face is no surface.  Rising (the side grows): k* = side(s_{i-1}),
+           the lowest isovalue crossed; falling: k* = side(s_{i-1}) - 1, the highest.  iso = iso_{k*}.  The walk ends at step i: steps walked = i + 1 on a hit, n
+           on a miss.
+Refinement two rounds of four points - what four lanes per ray evaluate at once.  From (ta, sa) = (tm_{i-1}, s_{i-1}), (tb, sb) = (tm_i, s_i), in(x) = (iso <= x):
+           a round taps q_j at p_j = fma(c_j, tb - ta, ta), c = (0.2f, 0.4f, 0.6f, 0.8f); of the sequence sa, q_1 .. q_4, sb the first consecutive pair whose `in`
+           differs becomes the new (ta, sa), (tb, sb) (in(sa) != in(sb) holds for the hit's pair and is kept by every round).  Then
+           t* = fmin(fmax(fma((iso - sa) / (sb - sa), tb - ta, ta), ta), tb), pos* = fma(t*, dir, org), s* = the tap at pos*.
+Normal     shade_request's forward difference at po* = to_object(pos*): per axis d = -g if po* + g > 1 else g (g = one voxel in object space), (tap(po* + d e) - s*) / d;
+           then normalize, negate, times otw_it (= inv_scale), normalize.  normalize = lighting.normalize.  (The product multiplies with 1 / g and normalises with
+           v_rsq_f32, as in the march; the exact-parity build is this text.)
+Shadow     under OVR_HIP_SHADE_FULL only: the ray pos* + t * light through the (clipped) box, (t0, t1, hit) from (0, FLT_MAX); its steps are the projection's
+           recurrence from tx_0 = t0 + step (t0 = 0 for a point inside the box: the first two samples sit at 1.5 and 2.5 step); shadow = 1 iff two consecutive
+           shadow samples differ in side, else 0; the walk ends at the first such pair, nothing is refined.
+Pixel      a miss: zeros.  A hit: rgb = the colour table at iso (projection.classify; the alpha table is not read); under NONE as it is, under GRADIENT / FULL
+           clamp01(rgb * lighting.shade(n_w, pos*, shadow, ...)) with the committed light and material; a = 1; the layer is (iso, t*, 1).  The samples of a
+           pixel are summed in order and multiplied by 1 / spp.
+Skipping   (primary and shadow walks, while range skipping is on) with [lo, hi] the value range of the step's tap_cell, S = projection.slack(lo, hi), a = lo - S,
+           b = hi + S: the step's fetch is dropped iff every k has iso_k < a or iso_k > b (a NaN bound proves nothing); its side is then #{k : iso_k < a} - the
+           side of every sample the cell can produce, by the bound of DESIGN.md section 16.  The two samples of the hit's pair are always taken (for the
+           refinement: a tap of its own at tm_{i-1} and tm_i, the walk's bits), whether the walk fetched them or not.
+Counters   samples / skipped_samples = the walked steps whose fetch the WALK made / dropped (their sum: the steps walked); shaded_samples = hits; shadow_samples /
+           skipped_shadow_samples = the same of the shadow walks.  Refinement, end-point and gradient taps are not counted.
+
+The 8-bit voxel types: the product filters the stored integers and normalises once behind the filter (s = filter(raw) * (1 / 255)), the exact-parity build and
+projection.sample normalise voxel by voxel.  `product_sampler` restates the former, so that hit, isovalue, t* and the steps walked of the product are this model's
+bits too."""
+import numpy as np
+
+from . import clipping, lighting
+from .clipping import clamp01, fmax, fmin
+from .lighting import fma
+from .projection import blue_noise_variates, classify, macrocell_ranges, pixel_rays, sample, slack, steps, tap_cell, tap_coordinates
+
+F = np.float32
+MAX_ISOVALUES = 4
+NONE, GRADIENT, FULL = 0, 1, 2
+C = (F(0.2), F(0.4), F(0.6), F(0.8))
+
+
+def isovalues(values):
+    """the values as the setter stores them: float32, sorted ascending; ValueError for what it refuses"""
+    v = np.sort(np.asarray(values, F).ravel())
+    if v.size > MAX_ISOVALUES or not np.isfinite(v).all() or (np.diff(v) == 0).any():
+        raise ValueError("at most four finite, distinct isovalues")
+    return v
+
+
+def side(s, iso):
+    s = np.asarray(s, F)
+    with np.errstate(invalid="ignore"):
+        return (np.asarray(iso, F).reshape((1,) * s.ndim + (-1,)) <= s[..., None]).sum(-1)
+
+
+def product_sampler(volume, vertex_centred=False):
+    """the product build's tap of an 8-bit volume: the filter over the stored integers, normalised once behind it; None for the other types (projection.sample)"""
+    v = np.asarray(volume)
+    if v.dtype == np.uint8:
+        raw, scale = v.astype(F), F(1) / F(255)
+    elif v.dtype == np.int8:
+        raw, scale = np.maximum(v.astype(F), F(-127)), F(1) / F(127)
+    else:
+        return None
+    return lambda po: (sample(raw, po, vertex_centred) * scale).astype(F)
+
+
+def skipped_side(lo, hi, iso):
+    """(fetch, side of a dropped step) from the value ranges of the steps' cells"""
+    lo, hi, iso = np.asarray(lo, F), np.asarray(hi, F), np.asarray(iso, F)
+    sl = slack(lo, hi)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a, b = (lo - sl).astype(F)[..., None], (hi + sl).astype(F)[..., None]
+        below, above = iso < a, iso > b
+    return ~(below | above).all(-1), below.sum(-1)
+
+
+def walk(s, count, iso, ranges=None):
+    """s (n, width) samples, count (n,) -> dict(hit, i - the hit's step -, k - k* -, walked, fetched): the first crossing.  ranges = (lo, hi), each (n, width): the
+    skipping walk, which never looks at a dropped step's sample"""
+    s = np.asarray(s, F)
+    n, width = s.shape
+    count = np.asarray(count, np.int64)
+    sd = side(s, iso)
+    fetch = np.ones((n, width), bool)
+    if ranges is not None:
+        fetch, below = skipped_side(ranges[0], ranges[1], iso)
+        sd = np.where(fetch, sd, below)
+    idx = np.arange(width)[None, :]
+    cross = np.zeros((n, width), bool)
+    if width > 1:
+        cross[:, 1:] = (sd[:, 1:] != sd[:, :-1]) & (idx[:, 1:] < count[:, None])
+    hit = cross.any(1)
+    i = np.where(hit, cross.argmax(1), 0)
+    r = np.arange(n)
+    before, at = sd[r, np.maximum(i - 1, 0)], sd[r, i]
+    k = np.where(at > before, before, before - 1)
+    walked = np.where(hit, i + 1, count)
+    fetched = (fetch & (idx < walked[:, None])).sum(1)
+    return dict(hit=hit, i=i, k=np.where(hit, k, 0), walked=walked, fetched=fetched)
+
+
+def refine(tap, iso, ta, sa, tb, sb):
+    """two rounds of four points, then the secant: tap(t) -> samples at the rays' distances t.  Returns (t*, ta, tb) - the last interval with it"""
+    ta, sa, tb, sb, iso = (np.asarray(x, F).copy() for x in (ta, sa, tb, sb, iso))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for _ in range(2):
+            w = (tb - ta).astype(F)
+            p = [ta] + [fma(c, w, ta) for c in C] + [tb]
+            q = [sa] + [tap(pj) for pj in p[1:5]] + [sb]
+            inside = [iso <= x for x in q]
+            done = np.zeros(ta.shape, bool)
+            nta, nsa, ntb, nsb = ta.copy(), sa.copy(), tb.copy(), sb.copy()
+            for j in range(5):
+                take = ~done & (inside[j] != inside[j + 1])
+                nta, nsa = np.where(take, p[j], nta), np.where(take, q[j], nsa)
+                ntb, nsb = np.where(take, p[j + 1], ntb), np.where(take, q[j + 1], nsb)
+                done |= take
+            ta, sa, tb, sb = nta.astype(F), nsa.astype(F), ntb.astype(F), nsb.astype(F)
+        f = ((iso - sa).astype(F) / (sb - sa).astype(F)).astype(F)
+        t = fmin(fmax(fma(f, (tb - ta).astype(F), ta), ta), tb)
+    return t, ta, tb
+
+
+def normals(tap_object, po, s, dims, inv_scale, vertex_centred=False):
+    """shade_request's forward difference at the object positions po (n, 3) with the samples s there -> n_w (n, 3)"""
+    n = np.asarray(dims, np.int64)
+    g = (F(1) / (n - 1 if vertex_centred else n).astype(F)).astype(F)
+    grad = np.empty(po.shape, F)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for k in range(3):
+            d = np.where((po[:, k] + g[k]).astype(F) > F(1), -g[k], g[k]).astype(F)
+            pk = po.copy()
+            pk[:, k] = (po[:, k] + d).astype(F)
+            grad[:, k] = ((tap_object(pk) - s).astype(F) / d).astype(F)
+        n_o = (-lighting.normalize(grad)).astype(F)
+        return lighting.normalize((n_o * np.asarray(inv_scale, F)[None, :]).astype(F))
+
+
+def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, shadows=True, light=None,
+               sampler=None):
+    """world rays org, direction (n, 3) - the direction used as given - -> what ovr_hip_isosurface_floats returns per ray, and the counters' parts:
+    dict(hit, iso, t, steps, normal (n, 3), shadow, fetched, pos (n, 3), shadow_steps, shadow_fetched, tm_before, tm_at, k); zeros for a ray without a hit.
+    light: the raw vector towards the light (normalised here as the host does); sampler(po) replaces projection.sample (product_sampler)"""
+    vol = np.asarray(volume)
+    nz, ny, nx = vol.shape
+    dims = (nx, ny, nz)
+    iso = isovalues(iso)
+    org, direction = np.asarray(org, F).reshape(-1, 3), np.asarray(direction, F).reshape(-1, 3)
+    inv, wp = clipping.volume_constants(dims, spacing, origin, vertex_centred)
+    lo, hi = ((0, 0, 0), (1, 1, 1)) if clip is None else clip
+    step = F(1) / F(rate)
+    tap_object = (lambda po: sample(vol, po, vertex_centred)) if sampler is None else (lambda po: np.asarray(sampler(po), F))
+    rng = macrocell_ranges(vol) if skipping else None
+
+    def first_crossing(o, d, tm, count):
+        n, width = tm.shape
+        with np.errstate(invalid="ignore", over="ignore"):
+            po = clipping.to_object(fma(np.nan_to_num(tm)[:, :, None], d[:, None, :], o[:, None, :]).reshape(-1, 3), inv, wp)
+        s = tap_object(po).reshape(n, width)
+        ranges = None
+        if skipping:
+            c = tap_cell(tap_coordinates(po, dims, vertex_centred)[0], dims)
+            r = rng[c[:, 2], c[:, 1], c[:, 0]].reshape(n, width, 2)
+            ranges = (r[..., 0], r[..., 1])
+        return s, walk(s, count, iso, ranges)
+
+    t0, t1, box = clipping.world_intervals(org, direction, inv, wp, lo, hi)
+    tm, count = steps(t0, t1, step, box)
+    n = len(org)
+    if tm.shape[1] == 0:
+        tm = np.zeros((n, 1), F)
+    s, w = first_crossing(org, direction, tm, count)
+    hit, r = w["hit"], np.arange(n)
+    i = w["i"]
+    ta, tb, sa, sb = tm[r, np.maximum(i - 1, 0)], tm[r, i], s[r, np.maximum(i - 1, 0)], s[r, i]
+    isov = iso[np.clip(w["k"], 0, len(iso) - 1)] if len(iso) else np.zeros(n, F)
+    out = dict(hit=hit, k=w["k"], iso=np.where(hit, isov, F(0)).astype(F), steps=np.where(box, w["walked"], 0), fetched=np.where(box, w["fetched"], 0),
+               t=np.zeros(n, F), normal=np.zeros((n, 3), F), shadow=np.zeros(n, F), pos=np.zeros((n, 3), F), shadow_steps=np.zeros(n, np.int64),
+               shadow_fetched=np.zeros(n, np.int64), tm_before=np.where(hit, ta, F(0)).astype(F), tm_at=np.where(hit, tb, F(0)).astype(F))
+    h = np.flatnonzero(hit)
+    if h.size == 0:
+        return out
+    oh, dh = org[h], direction[h]
+
+    def tap_ray(t):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return tap_object(clipping.to_object(fma(t[:, None], dh, oh), inv, wp))
+
+    t, _, _ = refine(tap_ray, isov[h], ta[h], sa[h], tb[h], sb[h])
+    with np.errstate(invalid="ignore", over="ignore"):
+        pos = fma(t[:, None], dh, oh)
+    po = clipping.to_object(pos, inv, wp)
+    out["t"][h], out["pos"][h] = t, pos
+    out["normal"][h] = normals(tap_object, po, tap_object(po), dims, inv, vertex_centred)
+    if shadows:
+        L = lighting.normalize(np.asarray(lighting.LITERAL_LIGHT if light is None else light, F))
+        Ld = np.broadcast_to(L, pos.shape)
+        s0, s1, sbox = clipping.world_intervals(pos, Ld, inv, wp, lo, hi)
+        stm, scount = steps((s0 + step).astype(F), s1, step, sbox)
+        if stm.shape[1] == 0:
+            stm = np.zeros((h.size, 1), F)
+        _, sw = first_crossing(pos, Ld, stm, scount)
+        out["shadow"][h] = sw["hit"].astype(F)
+        out["shadow_steps"][h] = np.where(sbox, sw["walked"], 0)
+        out["shadow_fetched"][h] = np.where(sbox, sw["fetched"], 0)
+    return out
+
+
+def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=None, intensity=1.0, material=lighting.REFERENCE_MATERIAL, spacing=(1, 1, 1),
+          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None):
+    """one isosurface frame: rgba (H, W, 4), layer (H, W, 3) and counters.  basis = (pos, dir, hor, ver); tf_range in the samples' units
+    (projection.normalized_range); noise = the blue-noise tile switches that jitter on - without it spp must be 1, as in projection.frame"""
+    w, h = size
+    if noise is None and spp != 1:
+        raise ValueError("without the blue-noise jitter the model forms the rays of one sample per pixel")
+    rgba, layer = np.zeros((h * w, 4), F), np.zeros((h * w, 3), F)
+    counters = dict(rays=0, active_pixels=h * w, steps=0, fetched=0, hits=0, shadow_steps=0, shadow_fetched=0)
+    org = np.broadcast_to(np.asarray(basis[0], F), (h * w, 3))
+    raw_light = lighting.LITERAL_LIGHT if light is None else light
+    L = lighting.normalize(np.asarray(raw_light, F))
+    ka, kd, ks, shin = material
+    for k in range(spp):
+        xi = None if noise is None else blue_noise_variates(noise, w, h, frame_index, spp, k)
+        d = pixel_rays(basis, w, h, xi).reshape(-1, 3)
+        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler)
+        m = r["hit"]
+        rgb = classify(r["iso"], colors, np.zeros(2, F), *tf_range)[:, :3]
+        if shading != NONE:
+            f = lighting.shade(r["normal"], r["pos"], r["shadow"], L, basis[0], ka, kd, ks, shin, intensity)
+            with np.errstate(invalid="ignore", over="ignore"):
+                rgb = clamp01((rgb * f[:, None]).astype(F))
+        c = np.concatenate([rgb, np.ones((h * w, 1), F)], 1)
+        rgba = (rgba + np.where(m[:, None], c, F(0))).astype(F)
+        layer = (layer + np.where(m[:, None], np.stack([r["iso"], r["t"], np.ones(h * w, F)], 1), F(0))).astype(F)
+        counters["rays"] += h * w
+        counters["steps"] += int(r["steps"].sum())
+        counters["fetched"] += int(r["fetched"].sum())
+        counters["hits"] += int(m.sum())
+        counters["shadow_steps"] += int(r["shadow_steps"].sum())
+        counters["shadow_fetched"] += int(r["shadow_fetched"].sum())
+    rspp = F(1) / F(spp)
+    return (rgba * rspp).astype(F).reshape(h, w, 4), (layer * rspp).astype(F).reshape(h, w, 3), counters

@@ -354,6 +354,34 @@ class DeviceHIP:
         o = out.cpu().numpy()
         return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].astype(np.int64), o[:, 3].astype(np.int64)
 
+    # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
+    # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
+    def set_isosurfaces(self, values=()):
+        """up to four finite, distinct isovalues in the samples' units (8-bit types normalised); none: off, the default"""
+        v = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        L.check(self._lib.ovr_hip_set_isosurfaces(self._h, v.ctypes.data_as(C.POINTER(C.c_float)) if v.size else None, int(v.size)))
+
+    def get_isosurfaces(self):
+        """ovr_hip_isosurfaces, the COMMITTED state: n, isovalues (ascending), range_skipping (1: the last isosurface frame ran the range-skipping kernel)"""
+        c = L.Isosurfaces()
+        L.check(self._lib.ovr_hip_get_isosurfaces(self._h, C.byref(c)))
+        return c
+
+    def isosurface_rays(self, org, direction, range_skipping=False):
+        """isosurface rays as the kernels evaluate them (ovr_hip_isosurface_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
+        dict(hit (n,) bool, iso, t (n,) float32, steps (n,) int64, normal (n, 3), shadow (n,)) with the committed isovalues, volume, sampling rate, light and clip box"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("isosurface_rays: org and direction hold three floats per ray")
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_isosurface_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(bool(range_skipping))))
+        o = out.cpu().numpy()
+        return dict(hit=o[:, 0] != 0, iso=o[:, 1].copy(), t=o[:, 2].copy(), steps=o[:, 3].astype(np.int64), normal=o[:, 4:7].copy(), shadow=o[:, 7].copy())
+
     # ---- extensions of this backend ----------------------------------------------------------------------------
     def set_shading(self, mode):
         L.check(self._lib.ovr_hip_set_shading(self._h, int(mode)))

@@ -10,6 +10,7 @@
 #include <ovr/renderer.h>
 
 #include "../include/ovr_hip.h"
+#include "isovalues_env.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -185,6 +186,19 @@ public:
         if (mode < 0) throw std::runtime_error("[hip] OVR_HIP_PROJECTION expects max, min or mean");
         check(ovr_hip_set_projection(h, mode));
         if (!quiet) std::fprintf(stderr, "[hip] projection: %s intensity\n", p == "max" ? "maximum" : p == "min" ? "minimum" : "mean");
+      }
+      // Isosurfaces (ovr_hip_set_isosurfaces): OVR_HIP_ISOVALUES=0.4,0.7 draws the level sets of up to four isovalues (the samples' units: 8-bit volumes
+      // normalised) in the march's place, coloured by the scene's transfer function, shaded by the scene's shading mode.  Unset: nothing is called
+      if (const char* iv = std::getenv("OVR_HIP_ISOVALUES")) {
+        float v[OVR_HIP_MAX_ISOVALUES + 1];
+        const int n = ovrhip_plugin::parse_isovalues(iv, v, OVR_HIP_MAX_ISOVALUES); // (the whole string: trailing text is an error, not a shorter list)
+        if (n < 1) throw std::runtime_error("[hip] OVR_HIP_ISOVALUES expects one to four isovalues separated by commas");
+        check(ovr_hip_set_isosurfaces(h, v, n));
+        if (!quiet) {
+          std::fprintf(stderr, "[hip] isosurfaces at");
+          for (int k = 0; k < n; ++k) std::fprintf(stderr, "%s %g", k ? "," : "", (double)v[k]);
+          std::fprintf(stderr, "\n");
+        }
       }
     }
     commit();

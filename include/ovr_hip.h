@@ -188,6 +188,23 @@ int ovr_hip_set_transfer_function(ovr_hip_renderer* r, const float* colors_rgb, 
 
 /* replaces MainRenderer::set_camera (ovr/renderer.h:140-152); fovy in degrees (scene.h:219 default 60) */
 int ovr_hip_set_camera(ovr_hip_renderer* r, const float from[3], const float at[3], const float up[3], float fovy);
+/* The orthographic camera (ovr::scene::Camera::type == ORTHOGRAPHIC, ovr/scene.h:207-230; open-volume-renderer_amd/camera.py is the normative arithmetic,
+ * DESIGN.md section 18): parallel rays along normalize(at - from), one per pixel sample, starting on the image plane through `from`; `height` is the world
+ * height of the image, height * width / height its width.  A queued value like the perspective camera's, in the same slot: ovr_hip_set_camera stays the
+ * perspective setter and switches back.  Every kind of frame honours it (the march, the projections, the isosurfaces); a ray that the reference's box test
+ * would let through an ignored slab from outside it (a direction component below FLT_MIN: EVERY ray of an axis view has two) is a miss under this camera.
+ * The distances of the projection and isosurface layers are then planar depth.  EINVAL, the state kept: a null pointer, a height that is not finite or not > 0. */
+#define OVR_HIP_CAMERA_PERSPECTIVE 0
+#define OVR_HIP_CAMERA_ORTHOGRAPHIC 1
+int ovr_hip_set_camera_orthographic(ovr_hip_renderer* r, const float from[3], const float at[3], const float up[3], float height);
+/* the COMMITTED camera: what the setter was given (fovy of a perspective, height of an orthographic camera; the other is 0) and pos ... ver, the basis the
+ * kernels read (zeros until a framebuffer size is committed) */
+typedef struct ovr_hip_camera {
+  int32_t kind;
+  float from[3], at[3], up[3], fovy, height;
+  float pos[3], dir[3], hor[3], ver[3];
+} ovr_hip_camera;
+int ovr_hip_get_camera(const ovr_hip_renderer* r, ovr_hip_camera* out);
 /* ovr/renderer.h:135-138 */
 int ovr_hip_set_fbsize(ovr_hip_renderer* r, int32_t width, int32_t height);
 /* ovr/renderer.h:170-173 */
@@ -595,6 +612,11 @@ int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org_device, const f
  * shading (normal and shadow are always computed), with the COMMITTED isovalues, volume transform, sampling rate, light and clip box; a ray without a hit gives zeros
  * but for the steps walked.  range_skipping comes from the argument.  ESTATE without a volume or while no isovalue is committed; EINVAL: a null pointer, n < 0. */
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t range_skipping);
+/* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
+ * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
+ * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no
+ * volume.  EINVAL: a null pointer, frame_index < 1, a sample outside 0 ... spp - 1, a capacity below width x height x 6; ESTATE: no framebuffer size. */
+int ovr_hip_camera_rays(ovr_hip_renderer* r, int32_t frame_index, int32_t sample, float* org_dir_device, size_t capacity_floats);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,24 @@ class Isosurfaces(C.Structure):
     ]
 
 
+CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC = 0, 1
+
+
+class CameraState(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("eye", C.c_float * 3),   # `from` in the header (a Python keyword)
+        ("at", C.c_float * 3),
+        ("up", C.c_float * 3),
+        ("fovy", C.c_float),
+        ("height", C.c_float),
+        ("pos", C.c_float * 3),
+        ("dir", C.c_float * 3),
+        ("hor", C.c_float * 3),
+        ("ver", C.c_float * 3),
+    ]
+
+
 # every symbol include/ovr_hip.h declares: name -> (restype, argtypes)
 _F3 = C.POINTER(C.c_float)
 _H = C.c_void_p
@@ -166,6 +184,9 @@ SYMBOLS = {
     "ovr_hip_set_grid_convention": (C.c_int, [_H, C.c_int]),
     "ovr_hip_set_transfer_function": (C.c_int, [_H, _F3, C.c_int32, _F3, C.c_int32, C.c_float, C.c_float]),
     "ovr_hip_set_camera": (C.c_int, [_H, _F3, _F3, _F3, C.c_float]),
+    "ovr_hip_set_camera_orthographic": (C.c_int, [_H, _F3, _F3, _F3, C.c_float]),
+    "ovr_hip_get_camera": (C.c_int, [_H, C.POINTER(CameraState)]),
+    "ovr_hip_camera_rays": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t]),
     "ovr_hip_set_fbsize": (C.c_int, [_H, C.c_int32, C.c_int32]),
     "ovr_hip_set_sample_per_pixel": (C.c_int, [_H, C.c_int32]),
     "ovr_hip_set_volume_sampling_rate": (C.c_int, [_H, C.c_float]),

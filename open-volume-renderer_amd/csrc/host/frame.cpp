@@ -65,7 +65,8 @@ SparseMaskParams make_mask_params(ovr_hip_renderer* r, int frame_index, int32_t*
 // Screen-space bounding rectangle (pixels, aligned outwards to 8, two pixels of margin for the sub-pixel jitter) of the volume's box
 // under the committed camera: a ray outside it misses the box and its pixel is exactly 0 in every layer (background 0, alpha 0,
 // shaders_raymarching.cu:260-321) - in any mode: accumulation adds 0, sparse sampling and image shards leave it cleared.  The whole
-// frame when a corner of the box lies at or behind the camera plane.
+// frame when a corner of the box lies at or behind the camera plane.  Under the orthographic camera a corner projects without the division by its
+// distance - 0.5 + (p . h) / hh - and the rectangle is always valid: what lies outside the silhouette misses (primary_box_test), also on an axis view.
 static void nonzero_rect(const ovr_hip_renderer* r, int rect[4])
 {
   const int W = r->fbsize.current.w, H = r->fbsize.current.h;
@@ -80,7 +81,7 @@ static void nonzero_rect(const ovr_hip_renderer* r, int rect[4])
   for (int c = 0; c < 8; ++c) {
     double p[3];
     for (int k = 0; k < 3; ++k) p[k] = (((c >> k) & 1 ? 1.0 : 0.0) - wp[k]) / inv[k] - from[k]; // object corner -> world, relative to the eye
-    const double a = p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
+    const double a = P.cam_orthographic ? 1.0 : p[0] * d[0] + p[1] * d[1] + p[2] * d[2];
     if (!(a > 1e-6 * (std::fabs(p[0]) + std::fabs(p[1]) + std::fabs(p[2]) + 1e-30))) return; // at or behind the camera plane: whole frame
     const double sx = 0.5 + (p[0] * h[0] + p[1] * h[1] + p[2] * h[2]) / (hh * a), sy = 0.5 + (p[0] * v[0] + p[1] * v[1] + p[2] * v[2]) / (vv * a);
     sx0 = std::min(sx0, sx); sx1 = std::max(sx1, sx); sy0 = std::min(sy0, sy); sy1 = std::max(sy1, sy);

@@ -36,10 +36,14 @@ constexpr int kAxisAbExtra = 3, kAxisZExtra = 2; // table entries beyond nx + ny
 // layout) and shade_pool_kernel<VT, shade, am, skip, material, clipped, cached>; am == 4 only for the layouts row_load_layout names.
 // cached (the shadow cache): the shadow term is one tap into a lattice instead of a march - on the kernels that shade without a
 // shadow march (shade 1), riding on the material variant like the clipped ones; the pooled march does not shade and has no cached twin
+// orthographic (the orthographic camera): a per-lane ray origin and the miss rule of primary_box_test.  THE ORTHOGRAPHIC VARIANTS EXIST
+// EXACTLY WHERE THE CLIPPED ONES EXIST, as the clipped ones ride on the material variants: an orthographic frame without a clip box runs them with the unit
+// box (whose bounds give the unclipped test's bits), and it never takes the LDS-staged or the deep march - a clipped frame takes neither
 constexpr bool row_load_layout(int elem_bytes, bool quad) { return elem_bytes <= 2 && !quad; } // the 16-bit pairs (and 8-bit ones) as aligned 8-byte rows
 constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, bool lds_staged, bool deep, bool material, bool clipped, bool f32_general,
-                                    bool cached = false)
+                                    bool cached = false, bool orthographic = false)
 {
+  if (orthographic && (!clipped || lds_staged || deep)) return false;          // on the clipped variants alone
   if (cached && !(shade == 1 && material && !pooled)) return false;           // where the march shades, without a shadow march, on the material variant
   if (shade < 0 || shade > 2 || am < 0 || am > 4 || (f32_general && am == 4)) return false;
   if (pooled && shade == 0) return false;                                      // nothing to shade: the in-place march is the only pipeline
@@ -49,9 +53,12 @@ constexpr bool march_variant_exists(int shade, int am, bool pooled, bool skip, b
   if (clipped && !pooled && material != (shade != 0)) return false;            // the clipped in-place march rides on the material variant where it shades
   return true;
 }
-constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material, bool clipped, bool cached = false)
+constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material, bool clipped, bool cached = false, bool orthographic = false)
 {
   if (shade < 1 || shade > 2 || am < 0 || am > 4) return false;
+  // the shade kernel forms no primary ray: its orthographic twin differs by the view vector alone, so it rides on the material variant - the clipped one where
+  // the kernel marches shadow rays (an orthographic frame is a clipped frame), the plain one where it does not
+  if (orthographic && !(material && clipped == (shade == 2))) return false;
   if (cached && !(shade == 1 && material)) return false;
   (void)skip;
   return !clipped || (shade == 2 && material); // clipped where the shade kernel marches shadow rays, on the material variant
@@ -62,9 +69,9 @@ constexpr bool shade_variant_exists(int shade, int am, bool skip, bool material,
 // every sample); am == 4 only for the layouts row_load_layout names, like the march
 constexpr int kProjectMaximum = 1, kProjectMinimum = 2, kProjectMean = 3;
 constexpr int kProjectK = 4; // instructions (x 4 steps) per round, the unshaded march's
-constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped)
+constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped, bool orthographic = false)
 {
-  (void)clipped; // both box tests exist for every variant
+  if (orthographic && !clipped) return false; // both box tests exist for every variant, the orthographic camera on the clipped one
   if (mode < kProjectMaximum || mode > kProjectMean || am < 0 || am > 4) return false;
   return !skip || mode != kProjectMean;
 }
@@ -73,9 +80,10 @@ constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped)
 // layouts for up to kMaxIsovalues isovalues.  shade: the committed shading mode (0 colour alone, 1 gradient-shaded, 2 with the hard shadow walk); skip: the
 // range-skipping twin, which every shading mode has (primary and shadow walk skip alike); the material is a run-time argument, not a variant
 constexpr int kMaxIsovalues = 4; // include/ovr_hip.h OVR_HIP_MAX_ISOVALUES
-constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped)
+constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false)
 {
-  (void)skip; (void)clipped; // both walks and both box tests exist for every variant
+  (void)skip; // both walks and both box tests exist for every variant, the orthographic camera on the clipped test
+  if (orthographic && !clipped) return false;
   return shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
 }
 
@@ -127,6 +135,7 @@ struct LaunchFacts {
   bool shadow_cache = false;          // a valid shadow lattice is bound (RayMarchParams::shadow_lattice): a frame with full shading reads it
   int projection = 0;                 // 0: the march; 1 ... 3: a projection frame (kProjectMaximum ...) - shading, pool, majorants and LDS staging are not read
   bool ranges = false;                // the macrocells' value ranges are bound (RayMarchParams::mc_ranges): an extremum may skip by them
+  bool orthographic = false;          // the committed camera is orthographic (ovr_hip_set_camera_orthographic): the frame takes the orthographic twins of the clipped variants
   int isosurfaces = 0;                // the number of committed isovalues; > 0: an isosurface frame - `projection` is kept but not drawn, pool, majorants and LDS staging are not read
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
@@ -139,6 +148,7 @@ struct LaunchPlan {
   struct March { bool lds_staged = false, deep = false, material = false, clipped = false; } march;
   struct Shade { bool material = false, clipped = false; } shade;
   bool shade_order = false;           // the shade kernel meets the runs sorted by light beam (PoolDesc::order)
+  bool orthographic = false;          // every kernel of the frame that forms a primary ray or a view vector is the orthographic twin (of the clipped variant)
   bool cached = false;                // the kernels that shade take the shadow term from the lattice: SHADE 1, material, no box test while shading
   // a projection frame (LaunchFacts::projection != 0): project_kernel in the march's place, nothing else of the plan but `am` is read
   struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
@@ -176,7 +186,8 @@ inline LaunchPlan plan_projection(const LaunchFacts& f, const LaunchOverrides& o
   pl.am = am;
   pl.project.mode = f.projection;
   pl.project.skip = f.ranges && f.projection != kProjectMean;
-  pl.project.clipped = f.clip_on;
+  pl.project.clipped = f.clip_on || f.orthographic; // (an orthographic frame without a clip box: the clipped variant with the unit box)
+  pl.orthographic = f.orthographic;
   pl.project.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
   pl.march_lds_bytes = pl.project.lds_bytes; // project_kernel takes the in-place march's place in the launch sequence
   return pl;
@@ -198,7 +209,8 @@ inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.isosurface.on = true;
   pl.isosurface.skip = f.ranges;
-  pl.isosurface.clipped = f.clip_on;
+  pl.isosurface.clipped = f.clip_on || f.orthographic;
+  pl.orthographic = f.orthographic;
   pl.isosurface.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
   pl.march_lds_bytes = pl.isosurface.lds_bytes; // isosurface_kernel takes the in-place march's place in the launch sequence
   return pl;
@@ -210,6 +222,8 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   if (f.projection != 0) return plan_projection(f, o);
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  pl.orthographic = f.orthographic;
+  const bool clip = f.clip_on || f.orthographic; // an orthographic frame is a clipped frame: with the unit box where no clip box is committed
   // the shadow cache: full shading without the shadow march is the gradient-shaded kernel plus one tap - everything below follows from SHADE 1 (no clipped
   // shade kernel: the clip is baked into the lattice; no shade order: there are no light beams to sort by) but the material flag, which the cached variants ride on
   pl.cached = pl.shading == 2 && f.shadow_cache;
@@ -230,27 +244,47 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   if (!pl.pooled) {
     pl.march_lds_bytes = std::max<size_t>(tf + tables + queues, (size_t)kWaves * kCounterWords * 4); // the counter reduction reuses it
     // a clipped frame takes the ordinary march (the same frame, and no further set of kernels), and where that shades, its material variant
-    if (f.f32_general && sh == 0 && !f.skipping && am <= 1 && f.lds_staging && !f.sparse && !f.clip_on) {
+    if (f.f32_general && sh == 0 && !f.skipping && am <= 1 && f.lds_staging && !f.sparse && !clip) {
       pl.march.lds_staged = true; // [.. tables, TF ..][bricks][region descriptor][corner rays 4 x float3][t range]
       pl.lds_brick_offset = (unsigned int)align16(pl.march_lds_bytes);
       pl.march_lds_bytes = pl.lds_brick_offset + (size_t)kLdsBrickCap * 128 + kLdsRegionBytes + 12 * 4 + 2 * 4 + 16;
     }
     else {
-      pl.march.clipped = f.clip_on;
-      pl.march.material = sh != 0 && (f.clip_on || !f.reference_material || pl.cached);
+      pl.march.clipped = clip;
+      pl.march.material = sh != 0 && (clip || !f.reference_material || pl.cached);
     }
     return pl;
   }
   pl.march_lds_bytes = queues + tables + (size_t)f.n_alpha * 4 + 64;
-  pl.march.clipped = f.clip_on;
-  pl.march.deep = !f.skipping && (am <= 1 || am == 4) && !f.clip_on && deep_rounds_pay(f, o); // a small image shard: the longest ray's chain of rounds is the floor
-  pl.shade.clipped = sh == 2 && f.clip_on; // shadow rays are clipped too; without them the shade kernel never tests the box
-  pl.shade.material = pl.shade.clipped || !f.reference_material || pl.cached;
+  pl.march.clipped = clip;
+  pl.march.deep = !f.skipping && (am <= 1 || am == 4) && !clip && deep_rounds_pay(f, o); // a small image shard: the longest ray's chain of rounds is the floor
+  pl.shade.clipped = sh == 2 && clip; // shadow rays are clipped too; without them the shade kernel never tests the box
+  pl.shade.material = pl.shade.clipped || !f.reference_material || pl.cached || f.orthographic; // (orthographic: the view vector's twin rides on it)
   pl.shade_order = sh == 2 && f.shade_order; // no shadow rays: creation order (its tickets' batches, profiles/r02_notes.md section 11)
   pl.shade_lds_bytes = std::max<size_t>(tf + tables, 64);
   const int blocks = o.shade_blocks > 0 ? o.shade_blocks : f.shade_blocks;
   pl.shade_grid_blocks = blocks > 0 ? std::min(blocks, kShadeBlocks) : kShadeBlocks;
   return pl;
 }
+
+// the plan's variants exist - what frame_kernels / project_kernels_of / isosurface_kernels_of then look up (f32_general decides the LDS-staged march alone)
+inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
+{
+  if (pl.error) return false;
+  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic);
+  if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
+  return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
+                              pl.cached && !pl.pooled, pl.orthographic) &&
+         (!pl.pooled || shade_variant_exists(pl.shading, pl.am, pl.skip, pl.shade.material, pl.shade.clipped, pl.cached, pl.orthographic));
+}
+static_assert(!march_variant_exists(0, 0, false, false, false, false, false, false, true, false, true) && march_variant_exists(0, 0, false, false, false, false, false, true, true, false, true)
+                && !march_variant_exists(0, 0, false, false, true, false, false, true, true, false, true) && !march_variant_exists(1, 0, true, false, false, true, false, true, false, false, true),
+              "the orthographic march: on the clipped variants alone, never LDS-staged, never deep");
+static_assert(shade_variant_exists(1, 0, false, true, false, false, true) && shade_variant_exists(2, 0, false, true, true, false, true) && !shade_variant_exists(2, 0, false, true, false, false, true)
+                && !shade_variant_exists(1, 0, false, false, false, false, true) && shade_variant_exists(1, 0, false, true, false, true, true),
+              "the orthographic shade kernel: the material variant - clipped where it marches shadow rays");
+static_assert(project_variant_exists(kProjectMaximum, 0, true, true, true) && !project_variant_exists(kProjectMaximum, 0, true, false, true)
+                && isosurface_variant_exists(2, 0, true, true, true) && !isosurface_variant_exists(2, 0, true, false, true),
+              "the orthographic projection and isosurface kernels: on the clipped variants alone");
 
 } // namespace ovrhip

@@ -61,7 +61,8 @@ template <typename T> struct Queued { // vidi::TransactionalValue (ovr/common/vi
   bool update() { if (!dirty) return false; current = queued; dirty = false; return true; }
 };
 
-struct CameraP { float from[3] = { 0, 0, 0 }, at[3] = { 0, 0, -1 }, up[3] = { 0, 1, 0 }; float fovy = 60.f; };
+// kind: OVR_HIP_CAMERA_*; fovy belongs to the perspective, height (the image's world height) to the orthographic camera
+struct CameraP { float from[3] = { 0, 0, 0 }, at[3] = { 0, 0, -1 }, up[3] = { 0, 1, 0 }; float fovy = 60.f; int kind = OVR_HIP_CAMERA_PERSPECTIVE; float height = 0.f; };
 struct FocusP { float cx = 0.5f, cy = 0.5f, scale = 0.2f, base_noise = 0.1f; }; // params.h:82-84
 struct TfnP { std::vector<float> colors, alphas; float lo = 1, hi = -1; };
 struct ShardP { int rank = 0, world = 1, tw = 64, th = 64; };

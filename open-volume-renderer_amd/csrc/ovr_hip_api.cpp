@@ -210,6 +210,48 @@ int ovr_hip_set_camera(ovr_hip_renderer* r, const float from[3], const float at[
   return 0;
 }
 
+int ovr_hip_set_camera_orthographic(ovr_hip_renderer* r, const float from[3], const float at[3], const float up[3], float height)
+{
+  if (!r || !from || !at || !up) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_camera_orthographic: null argument");
+  if (!std::isfinite(height) || !(height > 0.f)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_camera_orthographic: the height must be finite and > 0");
+  GroupLock gl(r);
+  {
+    std::lock_guard<std::mutex> lk(r->mtx);
+    CameraP c;
+    std::memcpy(c.from, from, sizeof(c.from));
+    std::memcpy(c.at, at, sizeof(c.at));
+    std::memcpy(c.up, up, sizeof(c.up));
+    c.fovy = 0.f;
+    c.kind = OVR_HIP_CAMERA_ORTHOGRAPHIC;
+    c.height = height;
+    r->camera.set(c); // the perspective camera's slot: recorded under the commit plan's kCamera
+  }
+  GROUP_FORWARD(r, ovr_hip_set_camera_orthographic(m, from, at, up, height));
+  return 0;
+}
+
+int ovr_hip_get_camera(const ovr_hip_renderer* r, ovr_hip_camera* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_camera: null argument");
+  std::lock_guard<std::mutex> lk(const_cast<ovr_hip_renderer*>(r)->mtx);
+  const CameraP& c = r->camera.current;
+  const RayMarchParams& P = r->P;
+  std::memset(out, 0, sizeof(*out));
+  out->kind = c.kind;
+  std::memcpy(out->from, c.from, sizeof(c.from));
+  std::memcpy(out->at, c.at, sizeof(c.at));
+  std::memcpy(out->up, c.up, sizeof(c.up));
+  out->fovy = c.kind == OVR_HIP_CAMERA_ORTHOGRAPHIC ? 0.f : c.fovy;
+  out->height = c.kind == OVR_HIP_CAMERA_ORTHOGRAPHIC ? c.height : 0.f;
+  if (!r->camera_dirty) { // (dirty: no framebuffer size was committed yet, update_camera has not run for this camera)
+    out->pos[0] = P.cam_pos.x; out->pos[1] = P.cam_pos.y; out->pos[2] = P.cam_pos.z;
+    out->dir[0] = P.cam_dir.x; out->dir[1] = P.cam_dir.y; out->dir[2] = P.cam_dir.z;
+    out->hor[0] = P.cam_hor.x; out->hor[1] = P.cam_hor.y; out->hor[2] = P.cam_hor.z;
+    out->ver[0] = P.cam_ver.x; out->ver[1] = P.cam_ver.y; out->ver[2] = P.cam_ver.z;
+  }
+  return 0;
+}
+
 int ovr_hip_set_fbsize(ovr_hip_renderer* r, int32_t w, int32_t h)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -1253,6 +1295,28 @@ int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_isosurface_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_camera_rays(ovr_hip_renderer* r, int32_t frame_index, int32_t sample, float* org_dir, size_t capacity_floats)
+{
+  if (!r || !org_dir || frame_index < 1) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_camera_rays: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  const int W = r->fbsize.current.w, H = r->fbsize.current.h;
+  if (W <= 0 || H <= 0 || r->camera_dirty) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_camera_rays: no framebuffer size is committed");
+  if (sample < 0 || sample >= r->spp.current) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_camera_rays: the sample lies outside 0 ... spp - 1");
+  if (capacity_floats < (size_t)W * (size_t)H * 6) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_camera_rays: the buffer holds fewer than width x height x 6 floats");
+  if (r->jitter.current == 1 && !r->d_noise) return fail(OVR_HIP_ESTATE, "[hip] blue-noise pixel jitter enabled but no noise tile was set (ovr_hip_set_noise_tile)");
+  RayMarchParams q = r->P; // the committed camera; the frame's size, sampling and jitter as fill_target_params / fill_table_params set them
+  q.width = W; q.height = H;
+  q.frame_index = frame_index;
+  q.spp = r->spp.current;
+  q.jitter_mode = r->jitter.current;
+  q.jitter_noise = r->d_noise;
+  q.jitter_xy = r->noise_xy;
+  HIP_TRY(launch_camera_rays(q, sample, org_dir, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

@@ -636,21 +636,51 @@ __device__ __forceinline__ f3 to_object(const MarchConsts& mc, f3 p)
   return mk3(fmaf(p.x, mc.inv_scale.x, mc.wto_p.x), fmaf(p.y, mc.inv_scale.y, mc.wto_p.y), fmaf(p.z, mc.inv_scale.z, mc.wto_p.z));
 }
 
+// The ray of a pixel sample at the screen offsets (ux, uy) = (sx - 0.5, sy - 0.5), in world space (open-volume-renderer_amd/camera.py is the normative
+// arithmetic): the ONE statement of it - the frame kernels, the schedule's kernels and ovr_hip_camera_rays call this.
+// Perspective: every ray starts at cam_pos - wave-uniform, scalar registers - and the direction is normalised per sample.  ORTHO (the orthographic camera,
+// ovr_hip_set_camera_orthographic): every ray has cam_dir's bits as stored, and the origin is the direction expression with the roles of position and
+// direction swapped - per lane, which is why it is a compile-time variant: the kernels of a perspective frame never hold it.
+template <bool ORTHO>
+__device__ __forceinline__ void pixel_ray(const RayMarchParams& P, float ux, float uy, f3& org, f3& dir)
+{
+  const f3 cpos = ld3(P.cam_pos), cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
+  if (ORTHO) {
+    org = mk3(cpos.x + ux * chor.x + uy * cver.x, cpos.y + ux * chor.y + uy * cver.y, cpos.z + ux * chor.z + uy * cver.z);
+    dir = cdir;
+  }
+  else {
+    org = cpos;
+    dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y, cdir.z + ux * chor.z + uy * cver.z));
+  }
+}
+// Does a primary ray meet the box?  Perspective: the reference's test, its quirk included.  ORTHO: a ray through an ignored slab with its origin outside that
+// slab is a MISS - under a camera along a volume axis EVERY ray has two such components, and the reference's rule would smear the edge voxels over the
+// whole image.  The orthographic kernels exist on the clipped test alone (CLIP = true; the unit box without a clip box)
+template <bool CLIP, bool ORTHO>
+__device__ __forceinline__ bool primary_box_test(const RayMarchParams& P, float& t0, float& t1, f3 oo, f3 od)
+{
+  static_assert(!ORTHO || CLIP, "the orthographic variants exist exactly where the clipped ones exist (host/launch_plan.hpp)");
+  const bool hit = box_test<CLIP>(P, t0, t1, oo, od);
+  if (ORTHO) return hit && !box_ignored_slab_outside<CLIP>(P, oo, od);
+  return hit;
+}
+
 // Does the ray of pixel (ix, iy) - one sample per pixel, no jitter - meet the volume's box?  The expressions are the march's own
-// (raymarch_kernel: screen position, ray direction, object-space ray, box test), so the answer is the march's answer bit for bit, the
+// (raymarch_kernel: screen position, pixel_ray, object-space ray, box test), so the answer is the march's answer bit for bit, the
 // ignored-slab quirk of the reference's box test included.  launch_schedule uses it to find the 8x8 blocks NONE of whose rays hits.
-template <bool CLIP = false>
+template <bool CLIP = false, bool ORTHO = false>
 __device__ __forceinline__ bool pixel_ray_hits_box(const RayMarchParams& P, const MarchConsts& mc, int ix, int iy)
 {
   const float rsx = 1.f / (float)P.width, rsy = 1.f / (float)P.height;
   const float sx = ((float)ix + .5f) * rsx, sy = ((float)iy + .5f) * rsy;
   const float ux = sx - 0.5f, uy = sy - 0.5f;
-  const f3 cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
-  const f3 dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y, cdir.z + ux * chor.z + uy * cver.z));
+  f3 org, dir;
+  pixel_ray<ORTHO>(P, ux, uy, org, dir);
   const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
-  const f3 oo = to_object(mc, ld3(P.cam_pos));
+  const f3 oo = to_object(mc, org);
   float t0 = 0.f, t1 = FLT_MAX;
-  return box_test<CLIP>(P, t0, t1, oo, od);
+  return primary_box_test<CLIP, ORTHO>(P, t0, t1, oo, od);
 }
 
 // Empty-space skipping, per ray: the t interval outside of which every sample lies in a macrocell with majorant 0.
@@ -965,13 +995,15 @@ __device__ __forceinline__ void write_pixel(const RayMarchParams& P, unsigned in
 // shading instantiation, +3 ... +6 VGPRs and an occupancy step for the gradient-shaded quad layouts, +11 ... +18 spilled scalars with shadows;
 // profiles/r08_lighting.md.)  The host picks MAT = true when the committed material or intensity is not the reference's (reference_material).
 __host__ __device__ inline bool reference_material(const RayMarchParams& P) { return P.mat_ka == 0.5f && P.mat_kd == 0.5f && P.mat_ks == 0.f && P.light_i2 == 2.f; }
-template <bool MAT>
+// ORTHO: the view vector of the orthographic camera, -cam_dir for every sample (no position enters)
+template <bool MAT, bool ORTHO = false>
 __device__ __forceinline__ float shade_light(const RayMarchParams& P, f3 light, f3 n_w, f3 pos)
 {
   const float cosNL = fabsf(dot3(light, n_w));
   float d = ((MAT ? P.mat_kd : 0.5f) * cosNL) * (MAT ? P.light_i2 : 2.f);
   if (MAT && P.mat_ks > 0.f) {
-    const f3 v = normalize3(mk3(P.cam_pos.x - pos.x, P.cam_pos.y - pos.y, P.cam_pos.z - pos.z)); // from the sample's position, not from its ray: a pooled request holds no direction
+    const f3 v = ORTHO ? mk3(-P.cam_dir.x, -P.cam_dir.y, -P.cam_dir.z)
+                       : normalize3(mk3(P.cam_pos.x - pos.x, P.cam_pos.y - pos.y, P.cam_pos.z - pos.z)); // from the sample's position, not from its ray: a pooled request holds no direction
     const f3 h = normalize3(mk3(light.x + v.x, light.y + v.y, light.z + v.z));
     const float cosNH = fabsf(dot3(h, n_w)); // two-sided, like the diffuse term
     // NaN (a sample at the camera, h of length 0) and denormals (v_log_f32 takes them for 0: -inf, times shininess 0 = NaN) select 0
@@ -1008,7 +1040,8 @@ __device__ __forceinline__ float shadow_lookup(const RayMarchParams& P, f3 po)
 // shade one request: gradient (shaders_common.h:195-215), normals, shadow march, shade factor
 // (shaders_raymarching.cu:124-158).  Writes the result over the request.
 // CACHED: the shadow term is shadow_lookup's tap instead of a march (SHADE == 1: the kernel has no shadow march)
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false>
+// ORTHO: the orthographic camera's view vector (shade_light)
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false, bool ORTHO = false>
 __device__ __forceinline__ void shade_request(const RayMarchParams& P, const VolConsts& vc, const TfConsts& tf, const MarchConsts& mc, ShadeReq& r,
                                               unsigned int& n_shadow, unsigned int& n_shadow_skipped)
 {
@@ -1043,7 +1076,7 @@ __device__ __forceinline__ void shade_request(const RayMarchParams& P, const Vol
     n_c = normalize3(mk3(fmaf(n_w.x, m[0], fmaf(n_w.y, m[3], n_w.z * m[6])), fmaf(n_w.x, m[1], fmaf(n_w.y, m[4], n_w.z * m[7])),
                          fmaf(n_w.x, m[2], fmaf(n_w.y, m[5], n_w.z * m[8]))));
   }
-  const float lit = shade_light<MAT>(P, mc.light, n_w, pos);
+  const float lit = shade_light<MAT, ORTHO>(P, mc.light, n_w, pos);
   float shadow = 0.f;
   if (SHADE == 2) shadow = march_shadow<VT, AM, kShadowTaps, SKIP, CLIP>(P, vc, tf, mc, pos, n_shadow, n_shadow_skipped);
   if (CACHED) shadow = shadow_lookup(P, po);
@@ -1233,10 +1266,13 @@ constexpr int kPinMaxAM = 1; // the 64-bit addressing modes would spill to scrat
 // CLIP = true: the clipped march (box_test).  Where the march shades in place it rides on MAT = true - the material's values as arguments give the
 // reference state's bits when they are the reference's - so a clipped state adds one instantiation per kernel, not two
 // CACHED = true: the shadow cache's frame (shade_request) - SHADE == 1 and MAT = true, in place only
-template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false, bool CACHED = false>
+// ORTHO = true: the orthographic camera (pixel_ray: a per-lane origin; primary_box_test; shade_light's view vector) - on the clipped variants alone, never
+// LDS-staged or deep
+template <int VT, int SHADE, int AM, bool POOLED, bool SKIP, bool LDSB = false, bool DEEP = false, bool MAT = false, bool CLIP = false, bool CACHED = false,
+          bool ORTHO = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP && POOLED && (AM == 4 ? 0 : AM) <= kPinMaxAM) ? kMarchWavesPerEu : 1, kMarchWavesPerEu))) void raymarch_kernel(const RayMarchParams P)
 {
-  static_assert(march_variant_exists(SHADE, AM, POOLED, SKIP, LDSB, DEEP, MAT, CLIP, VT == VOX_F32, CACHED), "no such variant of the march (host/launch_plan.hpp)");
+  static_assert(march_variant_exists(SHADE, AM, POOLED, SKIP, LDSB, DEEP, MAT, CLIP, VT == VOX_F32, CACHED, ORTHO), "no such variant of the march (host/launch_plan.hpp)");
   using Cfg = QCfg<SHADE, POOLED>;
   constexpr int K = DEEP ? kDeepK : Cfg::K;
   constexpr int QCAP = Cfg::QCAP;
@@ -1303,11 +1339,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
         sy0 += (j1 - 0.5f) * rsy;
       }
       const float ux0 = sx0 - 0.5f, uy0 = sy0 - 0.5f;
-      const f3 c0 = ld3(P.cam_dir), h0 = ld3(P.cam_hor), v0 = ld3(P.cam_ver);
-      const f3 d0 = normalize3_exact(mk3(c0.x + ux0 * h0.x + uy0 * v0.x, c0.y + ux0 * h0.y + uy0 * v0.y, c0.z + ux0 * h0.z + uy0 * v0.z));
+      f3 o0, d0;
+      pixel_ray<ORTHO>(P, ux0, uy0, o0, d0);
       float a0 = 0.f, b0 = FLT_MAX;
-      const f3 oo0 = to_object(mc, ld3(P.cam_pos)), od0 = mk3(d0.x * mc.inv_scale.x, d0.y * mc.inv_scale.y, d0.z * mc.inv_scale.z);
-      need = box_test<CLIP>(P, a0, b0, oo0, od0);
+      const f3 oo0 = to_object(mc, o0), od0 = mk3(d0.x * mc.inv_scale.x, d0.y * mc.inv_scale.y, d0.z * mc.inv_scale.z);
+      need = primary_box_test<CLIP, ORTHO>(P, a0, b0, oo0, od0);
       if (SKIP && need) { // skipping: a ray that meets no occupied macrocell never fetches a voxel or a TF entry either
         pro_span = skip_interval(vc, oo0, od0, a0, b0, sub, true);
         need = pro_span.first <= pro_span.last;
@@ -1337,15 +1373,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
     const unsigned int e = P.schedule[blockIdx.x];
     const float cx_ = ((float)((int)(e & 0xffffu) * 8 + ((threadIdx.x & 1) ? 8 : 0))) / (float)P.width - 0.5f;
     const float cy_ = ((float)((int)(e >> 16) * 8 + ((threadIdx.x & 2) ? 8 : 0))) / (float)P.height - 0.5f;
-    const f3 c0 = ld3(P.cam_dir), h0 = ld3(P.cam_hor), v0 = ld3(P.cam_ver);
-    const f3 d = normalize3_exact(mk3(c0.x + cx_ * h0.x + cy_ * v0.x, c0.y + cx_ * h0.y + cy_ * v0.y, c0.z + cx_ * h0.z + cy_ * v0.z));
+    f3 o_, d; // (LDS staging is the perspective camera's alone: one origin, P.cam_pos, for the whole block)
+    pixel_ray<false>(P, cx_, cy_, o_, d);
     lds_corner[3 * threadIdx.x] = d.x; lds_corner[3 * threadIdx.x + 1] = d.y; lds_corner[3 * threadIdx.x + 2] = d.z;
   }
 
   const unsigned int pixel_index = (unsigned int)ix + (unsigned int)iy * (unsigned int)P.width;
   unsigned int v0 = (unsigned int)P.frame_index, v1 = pixel_index; // RandomTEA(frame_index, pixel_index)
-  const f3 org = ld3(P.cam_pos), cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
-  const f3 oo = to_object(mc, org);
+  // the perspective camera's origin is the frame's: wave-uniform, formed once; the orthographic camera's is the sample's (pixel_ray, below)
+  f3 org = ld3(P.cam_pos);
+  f3 oo = to_object(mc, org);
 
   float o_a = 0.f;
   f3 o_c = mk3(0, 0, 0), o_g = mk3(0, 0, 0);
@@ -1416,15 +1453,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
       sy += ((float)v1 * OVR_TEA_TOFLOAT - 0.5f) * rsy;
     }
     const float ux = sx - 0.5f, uy = sy - 0.5f;
-    const f3 dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y,
-                                        cdir.z + ux * chor.z + uy * cver.z));
+    f3 dir;
+    if (ORTHO) { pixel_ray<true>(P, ux, uy, org, dir); oo = to_object(mc, org); }
+    else { f3 o_; pixel_ray<false>(P, ux, uy, o_, dir); }
     // ---- __intersection__volume: object-space ray, direction not renormalised so t is shared
     const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
     float t0 = 0.f, t1 = FLT_MAX;
     alpha = 0.f;
     color = mk3(0, 0, 0);
     gradient = mk3(0, 0, 0);
-    bool live = active && box_test<CLIP>(P, t0, t1, oo, od);
+    bool live = active && primary_box_test<CLIP, ORTHO>(P, t0, t1, oo, od);
     if (active && owner) ++n_rays;
     if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
     SkipSpan span = skipspan_all(); // samples outside the hull, or in an unmarked segment of it, are in empty macrocells
@@ -1459,7 +1497,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
           r.px = r.py = r.pz = r.s = r.v = r.tr = r.a = 0.f; r.next = 0;
           if ((unsigned int)lane < n) {
             r = queue[(q_head + lane) & (QCAP - 1)];
-            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
+            if (r.a > 0.f) shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED, ORTHO>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped); // a == 0: null request
           }
           int opend = owner ? pend : 0;
           apply_batch(r, q_head, n, lane, opend, first, color, gradient);
@@ -1803,10 +1841,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((SKIP &&
 // ------------------------------------------------------------------------------------------------------------------
 // pooled pipeline, kernel B: persistent waves shade chunks from all tiles; one returning atomic per chunk
 // ------------------------------------------------------------------------------------------------------------------
-template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false>
+template <int VT, int SHADE, int AM, bool SKIP, bool MAT, bool CLIP = false, bool CACHED = false, bool ORTHO = false>
 __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams P)
 {
-  static_assert(shade_variant_exists(SHADE, AM, SKIP, MAT, CLIP, CACHED), "no such variant of the shade kernel (host/launch_plan.hpp)");
+  static_assert(shade_variant_exists(SHADE, AM, SKIP, MAT, CLIP, CACHED, ORTHO), "no such variant of the shade kernel (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   TfConsts tf;
@@ -1850,7 +1888,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
     if ((unsigned int)lane < n) {
       ShadeReq r = Q.reqs[(size_t)c * 64 + lane];
       if (r.a > 0.f) { // a == 0: null request (a step of the quad that needs no shading)
-        shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
+        shade_request<VT, SHADE, AM, SKIP, MAT, CLIP, CACHED, ORTHO>(P, vc, tf, mc, r, n_shadow, n_shadow_skipped);
         Q.reqs[(size_t)c * 64 + lane] = r;
       }
     }
@@ -1937,24 +1975,24 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
 typedef void (*FrameKernel)(const RayMarchParams);
 struct FrameKernels { FrameKernel march = nullptr, shade = nullptr; }; // shade: pooled plans only; march == nullptr: no such variant of this type
 enum VariantBits : unsigned { kBitPooled = 1, kBitSkip = 2, kBitLdsStaged = 4, kBitDeep = 8, kBitMaterial = 16, kBitClipped = 32, kBitCached = 64,
-                     kVariantBitsEnd = 128 };
-constexpr unsigned kShadeBits = kBitSkip | kBitMaterial | kBitClipped | kBitCached; // the flags shade_pool_kernel has
+                     kBitOrtho = 128, kVariantBitsEnd = 256 };
+constexpr unsigned kShadeBits = kBitSkip | kBitMaterial | kBitClipped | kBitCached | kBitOrtho; // the flags shade_pool_kernel has
 
 template <int VT, int SHADE, int AM, unsigned BITS>
 constexpr FrameKernel march_variant()
 {
   constexpr bool pooled = BITS & kBitPooled, skip = BITS & kBitSkip, lds_staged = BITS & kBitLdsStaged, deep = BITS & kBitDeep, material = BITS & kBitMaterial,
-                 clipped = BITS & kBitClipped, cached = BITS & kBitCached;
-  if constexpr (march_variant_exists(SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, VT == VOX_F32, cached))
-    return raymarch_kernel<VT, SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, cached>;
+                 clipped = BITS & kBitClipped, cached = BITS & kBitCached, ortho = BITS & kBitOrtho;
+  if constexpr (march_variant_exists(SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, VT == VOX_F32, cached, ortho))
+    return raymarch_kernel<VT, SHADE, AM, pooled, skip, lds_staged, deep, material, clipped, cached, ortho>;
   else return nullptr;
 }
 template <int VT, int SHADE, int AM, unsigned BITS>
 constexpr FrameKernel shade_variant()
 {
-  constexpr bool skip = BITS & kBitSkip, material = BITS & kBitMaterial, clipped = BITS & kBitClipped, cached = BITS & kBitCached;
-  if constexpr ((BITS & ~kShadeBits) == 0 && shade_variant_exists(SHADE, AM, skip, material, clipped, cached))
-    return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped, cached>;
+  constexpr bool skip = BITS & kBitSkip, material = BITS & kBitMaterial, clipped = BITS & kBitClipped, cached = BITS & kBitCached, ortho = BITS & kBitOrtho;
+  if constexpr ((BITS & ~kShadeBits) == 0 && shade_variant_exists(SHADE, AM, skip, material, clipped, cached, ortho))
+    return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped, cached, ortho>;
   else return nullptr;
 }
 template <int VT, int SHADE, int AM, unsigned... BITS>
@@ -2196,10 +2234,11 @@ __device__ __forceinline__ float4 project_classify(const RayMarchParams& P, floa
 
 // a projection frame: the march's pixels, block schedule, sparse list, samples per pixel, jitter and write_pixel around project_ray; the buffer mapframe hands
 // out as `grad` carries the projection layer (v, tm*, 1).  No request queue, no alpha, no occupancy attribute (none is measured to pay)
-template <int VT, int AM, int MODE, bool SKIP, bool CLIP>
+// ORTHO: the orthographic camera's rays (pixel_ray) - on the clipped variants alone
+template <int VT, int AM, int MODE, bool SKIP, bool CLIP, bool ORTHO = false>
 __global__ __launch_bounds__(kBlock) void project_kernel(const RayMarchParams P)
 {
-  static_assert(project_variant_exists(MODE, AM, SKIP, CLIP) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the projection (host/launch_plan.hpp)");
+  static_assert(project_variant_exists(MODE, AM, SKIP, CLIP, ORTHO) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the projection (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane & 3;
@@ -2223,8 +2262,6 @@ __global__ __launch_bounds__(kBlock) void project_kernel(const RayMarchParams P)
   const float scx = ((float)ix + .5f) * rsx, scy = ((float)iy + .5f) * rsy;
   const unsigned int pixel_index = (unsigned int)ix + (unsigned int)iy * (unsigned int)P.width;
   unsigned int v0 = (unsigned int)P.frame_index, v1 = pixel_index; // RandomTEA(frame_index, pixel_index)
-  const f3 org = ld3(P.cam_pos), cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
-  const f3 oo = to_object(mc, org);
   float o_a = 0.f;
   f3 o_c = mk3(0, 0, 0), o_g = mk3(0, 0, 0);
   for (int k_spp = 0; k_spp < P.spp; ++k_spp) { // uniform trip count
@@ -2241,10 +2278,12 @@ __global__ __launch_bounds__(kBlock) void project_kernel(const RayMarchParams P)
       sy += ((float)v1 * OVR_TEA_TOFLOAT - 0.5f) * rsy;
     }
     const float ux = sx - 0.5f, uy = sy - 0.5f;
-    const f3 dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y, cdir.z + ux * chor.z + uy * cver.z));
+    f3 org, dir;
+    pixel_ray<ORTHO>(P, ux, uy, org, dir);
+    const f3 oo = to_object(mc, org);
     const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
     float t0 = 0.f, t1 = FLT_MAX;
-    const bool live = active && box_test<CLIP>(P, t0, t1, oo, od);
+    const bool live = active && primary_box_test<CLIP, ORTHO>(P, t0, t1, oo, od);
     if (active && owner) ++n_rays;
     if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
     const ProjectResult pr = project_ray<VT, AM, MODE, SKIP>(P, vc, mc, org, dir, t0, t1, live, subm);
@@ -2300,43 +2339,44 @@ __global__ __launch_bounds__(kBlock) void project_floats_kernel(const RayMarchPa
 typedef void (*ProjectFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
 struct ProjectKernels { FrameKernel frame = nullptr; ProjectFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
 template <int VT, int AM, int MODE>
-inline ProjectKernels project_kernels_of(bool skip, bool clipped)
+inline ProjectKernels project_kernels_of(bool skip, bool clipped, bool ortho)
 {
   ProjectKernels k;
+  if (ortho && !clipped) return k; // (project_variant_exists)
   if constexpr (MODE != kProjectMean) {
     if (skip) {
-      k.frame = clipped ? project_kernel<VT, AM, MODE, true, true> : project_kernel<VT, AM, MODE, true, false>;
+      k.frame = ortho ? project_kernel<VT, AM, MODE, true, true, true> : clipped ? project_kernel<VT, AM, MODE, true, true> : project_kernel<VT, AM, MODE, true, false>;
       k.floats = project_floats_kernel<VT, AM, MODE, true>;
       return k;
     }
   }
   if (skip) return k;
-  k.frame = clipped ? project_kernel<VT, AM, MODE, false, true> : project_kernel<VT, AM, MODE, false, false>;
+  k.frame = ortho ? project_kernel<VT, AM, MODE, false, true, true> : clipped ? project_kernel<VT, AM, MODE, false, true> : project_kernel<VT, AM, MODE, false, false>;
   k.floats = project_floats_kernel<VT, AM, MODE, false>;
   return k;
 }
 template <int VT, int AM>
-inline ProjectKernels project_kernels_of(int mode, bool skip, bool clipped)
+inline ProjectKernels project_kernels_of(int mode, bool skip, bool clipped, bool ortho)
 {
   switch (mode) {
-  case kProjectMaximum: return project_kernels_of<VT, AM, kProjectMaximum>(skip, clipped);
-  case kProjectMinimum: return project_kernels_of<VT, AM, kProjectMinimum>(skip, clipped);
-  case kProjectMean: return project_kernels_of<VT, AM, kProjectMean>(skip, clipped);
+  case kProjectMaximum: return project_kernels_of<VT, AM, kProjectMaximum>(skip, clipped, ortho);
+  case kProjectMinimum: return project_kernels_of<VT, AM, kProjectMinimum>(skip, clipped, ortho);
+  case kProjectMean: return project_kernels_of<VT, AM, kProjectMean>(skip, clipped, ortho);
   default: return ProjectKernels();
   }
 }
 // the projection kernels of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads), like shadow_cache_kernel_of
 template <int VT>
-ProjectKernels project_kernels_of(int am, int mode, bool skip, bool clipped)
+ProjectKernels project_kernels_of(int am, int mode, bool skip, bool clipped, bool ortho)
 {
   if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
     switch (am) {
-    case 0: return project_kernels_of<VT, 0>(mode, skip, clipped);
-    case 1: return project_kernels_of<VT, 1>(mode, skip, clipped);
-    case 2: return project_kernels_of<VT, 2>(mode, skip, clipped);
-    case 3: return project_kernels_of<VT, 3>(mode, skip, clipped);
+    case 0: return project_kernels_of<VT, 0>(mode, skip, clipped, ortho);
+    case 1: return project_kernels_of<VT, 1>(mode, skip, clipped, ortho);
+    case 2: return project_kernels_of<VT, 2>(mode, skip, clipped, ortho);
+    case 3: return project_kernels_of<VT, 3>(mode, skip, clipped, ortho);
     case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return project_kernels_of<VT, 4>(mode, skip, clipped);
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return project_kernels_of<VT, 4>(mode, skip, clipped, ortho);
       else return ProjectKernels();
     }
   }
@@ -2608,10 +2648,11 @@ __device__ __forceinline__ f3 isosurface_colour(const RayMarchParams& P, float v
 
 // an isosurface frame: project_kernel's frame around isosurface_ray; the layer is (iso, t*, 1).  The material is a run-time argument (shade_light<true> with
 // the reference's values IS the reference's expression, operation for operation): one instantiation per shading mode, none per material
-template <int VT, int AM, int SHADE, bool SKIP, bool CLIP>
+// ORTHO: the orthographic camera's rays (pixel_ray) and view vector (shade_light) - on the clipped variants alone
+template <int VT, int AM, int SHADE, bool SKIP, bool CLIP, bool ORTHO = false>
 __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams P)
 {
-  static_assert(isosurface_variant_exists(SHADE, AM, SKIP, CLIP) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the isosurface kernel (host/launch_plan.hpp)");
+  static_assert(isosurface_variant_exists(SHADE, AM, SKIP, CLIP, ORTHO) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the isosurface kernel (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane & 3;
@@ -2636,8 +2677,6 @@ __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams
   const float scx = ((float)ix + .5f) * rsx, scy = ((float)iy + .5f) * rsy;
   const unsigned int pixel_index = (unsigned int)ix + (unsigned int)iy * (unsigned int)P.width;
   unsigned int v0 = (unsigned int)P.frame_index, v1 = pixel_index; // RandomTEA(frame_index, pixel_index)
-  const f3 org = ld3(P.cam_pos), cdir = ld3(P.cam_dir), chor = ld3(P.cam_hor), cver = ld3(P.cam_ver);
-  const f3 oo = to_object(mc, org);
   float o_a = 0.f;
   f3 o_c = mk3(0, 0, 0), o_g = mk3(0, 0, 0);
   for (int k_spp = 0; any_active && k_spp < P.spp; ++k_spp) { // uniform trip count (a workgroup without a pixel has no tables: it taps nothing)
@@ -2654,10 +2693,12 @@ __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams
       sy += ((float)v1 * OVR_TEA_TOFLOAT - 0.5f) * rsy;
     }
     const float ux = sx - 0.5f, uy = sy - 0.5f;
-    const f3 dir = normalize3_exact(mk3(cdir.x + ux * chor.x + uy * cver.x, cdir.y + ux * chor.y + uy * cver.y, cdir.z + ux * chor.z + uy * cver.z));
+    f3 org, dir;
+    pixel_ray<ORTHO>(P, ux, uy, org, dir);
+    const f3 oo = to_object(mc, org);
     const f3 od = mk3(dir.x * mc.inv_scale.x, dir.y * mc.inv_scale.y, dir.z * mc.inv_scale.z);
     float t0 = 0.f, t1 = FLT_MAX;
-    const bool live = active && box_test<CLIP>(P, t0, t1, oo, od);
+    const bool live = active && primary_box_test<CLIP, ORTHO>(P, t0, t1, oo, od);
     if (active && owner) ++n_rays;
     if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
     const IsoResult ir = isosurface_ray<VT, AM, SHADE, SKIP, CLIP>(P, vc, mc, org, dir, t0, t1, live, subm);
@@ -2668,7 +2709,7 @@ __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams
     if (ir.hit && owner) {
       f3 c = isosurface_colour(P, ir.iso);
       if (SHADE != 0) {
-        const float shade = shade_factor<true>(P, shade_light<true>(P, mc.light, ir.n_w, ir.pos), ir.shadow);
+        const float shade = shade_factor<true>(P, shade_light<true, ORTHO>(P, mc.light, ir.n_w, ir.pos), ir.shadow);
         c = mk3(clamp01(c.x * shade), clamp01(c.y * shade), clamp01(c.z * shade));
       }
       ++n_hits;
@@ -2719,19 +2760,20 @@ __global__ __launch_bounds__(kBlock) void isosurface_floats_kernel(const RayMarc
 typedef void (*IsosurfaceFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
 struct IsosurfaceKernels { FrameKernel frame = nullptr; IsosurfaceFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
 template <int VT, int AM, int SHADE>
-inline FrameKernel isosurface_frame_kernel(bool skip, bool clipped)
+inline FrameKernel isosurface_frame_kernel(bool skip, bool clipped, bool ortho)
 {
+  if (ortho) return !clipped ? nullptr : skip ? isosurface_kernel<VT, AM, SHADE, true, true, true> : isosurface_kernel<VT, AM, SHADE, false, true, true>; // (isosurface_variant_exists)
   if (skip) return clipped ? isosurface_kernel<VT, AM, SHADE, true, true> : isosurface_kernel<VT, AM, SHADE, true, false>;
   return clipped ? isosurface_kernel<VT, AM, SHADE, false, true> : isosurface_kernel<VT, AM, SHADE, false, false>;
 }
 template <int VT, int AM>
-inline IsosurfaceKernels isosurface_kernels_of(int shade, bool skip, bool clipped)
+inline IsosurfaceKernels isosurface_kernels_of(int shade, bool skip, bool clipped, bool ortho)
 {
   IsosurfaceKernels k;
   switch (shade) {
-  case 0: k.frame = isosurface_frame_kernel<VT, AM, 0>(skip, clipped); break;
-  case 1: k.frame = isosurface_frame_kernel<VT, AM, 1>(skip, clipped); break;
-  case 2: k.frame = isosurface_frame_kernel<VT, AM, 2>(skip, clipped); break;
+  case 0: k.frame = isosurface_frame_kernel<VT, AM, 0>(skip, clipped, ortho); break;
+  case 1: k.frame = isosurface_frame_kernel<VT, AM, 1>(skip, clipped, ortho); break;
+  case 2: k.frame = isosurface_frame_kernel<VT, AM, 2>(skip, clipped, ortho); break;
   default: return k;
   }
   k.floats = skip ? isosurface_floats_kernel<VT, AM, true> : isosurface_floats_kernel<VT, AM, false>;
@@ -2739,16 +2781,16 @@ inline IsosurfaceKernels isosurface_kernels_of(int shade, bool skip, bool clippe
 }
 // the isosurface kernels of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads), like project_kernels_of
 template <int VT>
-IsosurfaceKernels isosurface_kernels_of(int am, int shade, bool skip, bool clipped)
+IsosurfaceKernels isosurface_kernels_of(int am, int shade, bool skip, bool clipped, bool ortho)
 {
   if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
     switch (am) {
-    case 0: return isosurface_kernels_of<VT, 0>(shade, skip, clipped);
-    case 1: return isosurface_kernels_of<VT, 1>(shade, skip, clipped);
-    case 2: return isosurface_kernels_of<VT, 2>(shade, skip, clipped);
-    case 3: return isosurface_kernels_of<VT, 3>(shade, skip, clipped);
+    case 0: return isosurface_kernels_of<VT, 0>(shade, skip, clipped, ortho);
+    case 1: return isosurface_kernels_of<VT, 1>(shade, skip, clipped, ortho);
+    case 2: return isosurface_kernels_of<VT, 2>(shade, skip, clipped, ortho);
+    case 3: return isosurface_kernels_of<VT, 3>(shade, skip, clipped, ortho);
     case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return isosurface_kernels_of<VT, 4>(shade, skip, clipped);
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return isosurface_kernels_of<VT, 4>(shade, skip, clipped, ortho);
       else return IsosurfaceKernels();
     }
   }
@@ -2761,8 +2803,9 @@ template <int VT>
 FrameKernels frame_kernels(const LaunchPlan& pl)
 {
   const unsigned flags = (pl.skip ? kBitSkip : 0u) | (pl.pooled ? kBitPooled : 0u) | (pl.march.lds_staged ? kBitLdsStaged : 0u) | (pl.march.deep ? kBitDeep : 0u);
-  const unsigned march_bits = flags | (pl.march.material ? kBitMaterial : 0u) | (pl.march.clipped ? kBitClipped : 0u) | (pl.cached && !pl.pooled ? kBitCached : 0u);
-  const unsigned shade_bits = (flags & kBitSkip) | (pl.shade.material ? kBitMaterial : 0u) | (pl.shade.clipped ? kBitClipped : 0u) | (pl.cached ? kBitCached : 0u);
+  const unsigned ortho = pl.orthographic ? kBitOrtho : 0u;
+  const unsigned march_bits = flags | (pl.march.material ? kBitMaterial : 0u) | (pl.march.clipped ? kBitClipped : 0u) | (pl.cached && !pl.pooled ? kBitCached : 0u) | ortho;
+  const unsigned shade_bits = (flags & kBitSkip) | (pl.shade.material ? kBitMaterial : 0u) | (pl.shade.clipped ? kBitClipped : 0u) | (pl.cached ? kBitCached : 0u) | ortho;
   FrameKernels k;
   if (pl.error) return k;
   switch (pl.shading) {

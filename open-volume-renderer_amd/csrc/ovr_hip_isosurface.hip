@@ -8,5 +8,5 @@
 
 namespace ovrhip {
 static_assert(kVoxelTypes[OVR_MARCH_VT].layout == LAYOUT_GENERAL, "the isosurface kernels read the general layout");
-template IsosurfaceKernels isosurface_kernels_of<OVR_MARCH_VT>(int, int, bool, bool);
+template IsosurfaceKernels isosurface_kernels_of<OVR_MARCH_VT>(int, int, bool, bool, bool);
 }

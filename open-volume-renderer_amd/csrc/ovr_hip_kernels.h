@@ -265,6 +265,9 @@ struct RayMarchParams {
   // ascending, the entries behind iso_n unread.  Behind everything else, like the projection: no kernel that existed before reads them
   int iso_n;
   float iso_values[4];
+  // the camera's kind (ovr_hip_set_camera_orthographic; open-volume-renderer_amd/camera.py is the arithmetic): 1 = cam_pos ... cam_ver are the orthographic
+  // camera's and the host launches the orthographic twins of the clipped kernels (the kernels do not read it).  Behind everything else, like the isovalues
+  int cam_orthographic;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -447,6 +450,9 @@ hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, c
 // known-answer entry of the box test (box_test in ovr_hip_device.h, the function the march, the shadow march and the schedule call): n world-space rays
 // (origin, direction - used as given, not normalised) -> n triples (t0, t1, hit ? 1 : 0) with p's volume transform and clip box (the unit cube without one)
 hipError_t launch_clip_intervals(const RayMarchParams& p, const float* org, const float* dir, float* t0t1hit, int64_t n, hipStream_t stream);
+// known-answer entry of the pixel ray (pixel_ray in ovr_hip_device.h, the function the frame kernels call): the world origin and direction of sample `sample` of
+// frame p.frame_index for every pixel of the p.width x p.height frame, 6 floats per pixel in image order, under p's camera, jitter mode and spp
+hipError_t launch_camera_rays(const RayMarchParams& p, int sample, float* org_dir, hipStream_t stream);
 
 // macrocells (reference accel/sp_singlemc.cu): (min,max) per 16^3 cell once per volume; majorant per cell on every TF change
 hipError_t launch_macrocell_ranges(const VolumeDesc& vd, float* out_minmax, hipStream_t stream);

@@ -169,17 +169,17 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(const unsigned int
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kSchedClasses = 64;
 // length of probe ray k of block e inside the box (k = 0: the block's centre, 1 ... 4: its corners), -1 = it misses
-template <bool CLIP>
+template <bool CLIP, bool ORTHO>
 __device__ __forceinline__ float schedule_probe(const RayMarchParams& P, const MarchConsts& mc, unsigned int e, int k)
 {
-  const f3 c0 = ld3(P.cam_dir), h0 = ld3(P.cam_hor), v0 = ld3(P.cam_ver);
-  const f3 oo = to_object(mc, ld3(P.cam_pos));
   const int bx = (int)(e & 0xffffu) * 8, by = (int)(e >> 16) * 8;
   const int ix = min(bx + (k == 0 ? 4 : (k & 1) ? 0 : 7), P.width - 1), iy = min(by + (k == 0 ? 4 : (k & 2) ? 0 : 7), P.height - 1);
   const float ux = ((float)ix + .5f) / (float)P.width - 0.5f, uy = ((float)iy + .5f) / (float)P.height - 0.5f;
-  const f3 d = normalize3_exact(mk3(c0.x + ux * h0.x + uy * v0.x, c0.y + ux * h0.y + uy * v0.y, c0.z + ux * h0.z + uy * v0.z));
+  f3 o, d;
+  pixel_ray<ORTHO>(P, ux, uy, o, d);
+  const f3 oo = to_object(mc, o);
   float a = 0.f, b = FLT_MAX;
-  if (box_test<CLIP>(P, a, b, oo, mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z))) return b - a;
+  if (primary_box_test<CLIP, ORTHO>(P, a, b, oo, mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z))) return b - a;
   return -1.f;
 }
 // the block's class from the longest of its five probe rays: 0 = none meets the volume (last), 1 ... kSchedClasses - 1 by length
@@ -205,7 +205,9 @@ __device__ __forceinline__ unsigned int schedule_class_of(const RayMarchParams& 
 //                            (pixel_ray_hits_box: the march's own test); cls[i] = class | active pixels << 8, class 0 <=> (exact) no ray hits
 //                            CLIP: both against the committed clip box, as the clipped march tests it (the frustum culling of exact == 2 keeps the
 //                            volume's own box: a superset)
-template <bool CLIP>
+//                            ORTHO: the orthographic camera's rays (pixel_ray, primary_box_test), on the clipped test; exact == 2 culls by rectangles - the
+//                            planes of the frustum cull meet in the eye, which parallel rays do not have: see below
+template <bool CLIP, bool ORTHO = false>
 __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchParams P, const unsigned int* __restrict__ src, unsigned int n, int exact,
                                                                unsigned int* __restrict__ cls)
 {
@@ -219,14 +221,35 @@ __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchPa
   const int ix = (int)(e & 0xffffu) * 8 + (lane & 7), iy = (int)(e >> 16) * 8 + (lane >> 3);
   bool active = ix < P.width && iy < P.height;
   if (P.world > 1 && active) active = ((ix / P.tile_w + iy / P.tile_h) % P.world) == P.rank; // assign_pixel_quad's ownership test
-  const bool hit = exact == 1 && active && pixel_ray_hits_box<CLIP>(P, mc, ix, iy);
+  const bool hit = exact == 1 && active && pixel_ray_hits_box<CLIP, ORTHO>(P, mc, ix, iy);
   const unsigned long long any = __ballot(hit), act = __ballot(active);
   // exact == 2 (several samples per pixel, or jittered ones: a pixel's rays are only known to lie within half a pixel of its centre): the block
   // is surely empty if the cone of ALL rays through the block widened by 1.5 pixels lies beyond one of its own four side planes from the whole
   // box (frustum culling: 4 planes x 8 box corners, one pair per lane, object space), and no ray in it can have a direction component near 0
   // (the reference's box test ignores the slab of such a component, shaders_common.h:162-172: a ray could then "hit" from outside the silhouette)
   bool culled = false;
-  if (exact == 2) {
+  if (exact == 2 && ORTHO) {
+    // parallel rays: a ray's origin is cam_pos + ux hor + uy ver, and it can only meet the box if (ux, uy) lies inside the rectangle that bounds the box's
+    // eight corners projected along cam_dir onto (hor, ver).  The block's rays have (ux, uy) inside its pixel rectangle widened by 1.5 pixels (any jitter);
+    // the block is surely empty if the two rectangles are apart by more than a margin far above the rounding of the projections.  The volume's own box, like
+    // the frustum cull: a superset of a clip box.  (Under this camera a ray outside an ignored slab misses, so no sign condition is needed.)
+    const float x0 = ((float)((int)(e & 0xffffu) * 8) - 1.5f) / (float)P.width - 0.5f, x1 = ((float)((int)(e & 0xffffu) * 8 + 8) + 1.5f) / (float)P.width - 0.5f;
+    const float y0 = ((float)((int)(e >> 16) * 8) - 1.5f) / (float)P.height - 0.5f, y1 = ((float)((int)(e >> 16) * 8 + 8) + 1.5f) / (float)P.height - 0.5f;
+    const f3 cp = ld3(P.cam_pos), ch = ld3(P.cam_hor), cv = ld3(P.cam_ver);
+    const int cn = lane & 7; // one corner per lane, eight lanes hold the box
+    const f3 w = mk3(((float)(cn & 1) - mc.wto_p.x) / mc.inv_scale.x - cp.x, ((float)((cn >> 1) & 1) - mc.wto_p.y) / mc.inv_scale.y - cp.y,
+                     ((float)(cn >> 2) - mc.wto_p.z) / mc.inv_scale.z - cp.z);
+    const float su = dot3(w, ch) / dot3(ch, ch), sv = dot3(w, cv) / dot3(cv, cv);
+    float ulo = su, uhi = su, vlo = sv, vhi = sv;
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+      ulo = fminf(ulo, __shfl_xor(ulo, off)); uhi = fmaxf(uhi, __shfl_xor(uhi, off));
+      vlo = fminf(vlo, __shfl_xor(vlo, off)); vhi = fmaxf(vhi, __shfl_xor(vhi, off));
+    }
+    const float margin = 1e-4f * (1.f + fmaxf(fmaxf(fabsf(ulo), fabsf(uhi)), fmaxf(fabsf(vlo), fabsf(vhi))));
+    culled = x1 < ulo - margin || x0 > uhi + margin || y1 < vlo - margin || y0 > vhi + margin; // (a NaN compares false: not culled)
+  }
+  if (exact == 2 && !ORTHO) {
     const float x0 = ((float)((int)(e & 0xffffu) * 8) - 1.5f) / (float)P.width - 0.5f, x1 = ((float)((int)(e & 0xffffu) * 8 + 8) + 1.5f) / (float)P.width - 0.5f;
     const float y0 = ((float)((int)(e >> 16) * 8) - 1.5f) / (float)P.height - 0.5f, y1 = ((float)((int)(e >> 16) * 8 + 8) + 1.5f) / (float)P.height - 0.5f;
     const f3 cd = ld3(P.cam_dir), ch = ld3(P.cam_hor), cv = ld3(P.cam_ver);
@@ -259,7 +282,7 @@ __global__ __launch_bounds__(256) void schedule_classify_kernel(const RayMarchPa
     }
     culled = beyond && sign_safe;
   }
-  float longest = lane < 5 ? schedule_probe<CLIP>(P, mc, e, lane) : -1.f; // (until round 4 lane 0 traced all five: 58 us per camera change at 1080p)
+  float longest = lane < 5 ? schedule_probe<CLIP, ORTHO>(P, mc, e, lane) : -1.f; // (until round 4 lane 0 traced all five: 58 us per camera change at 1080p)
 #pragma unroll
   for (int off = 1; off < 8; off <<= 1) longest = fmaxf(longest, __shfl_xor(longest, off));
   if (lane == 0) {
@@ -347,7 +370,7 @@ hipError_t launch_schedule(const RayMarchParams& p, const unsigned int* src, uns
   const dim3 grid((n + 1023u) / 1024u);
   unsigned int* hist = workspace;
   unsigned int* cls = workspace + (size_t)grid.x * kSchedRow;
-  auto classify = p.clip_on ? schedule_classify_kernel<true> : schedule_classify_kernel<false>;
+  auto classify = p.cam_orthographic ? schedule_classify_kernel<true, true> : p.clip_on ? schedule_classify_kernel<true> : schedule_classify_kernel<false>;
   hipLaunchKernelGGL(classify, dim3((n + 3u) / 4u), dim3(256), 0, stream, p, src, n, exact, cls);
   hipLaunchKernelGGL(schedule_hist_kernel, grid, dim3(1024), 0, stream, cls, n, hist);
   hipLaunchKernelGGL(schedule_scatter_kernel, grid, dim3(1024), 0, stream, src, cls, n, hist, dst, info);
@@ -991,6 +1014,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.shadow_cache = p.shadow_lattice != nullptr;
   f.projection = p.projection; f.ranges = p.mc_ranges != nullptr;
   f.isosurfaces = p.iso_n;
+  f.orthographic = p.cam_orthographic != 0;
   return plan_launch(f, o);
 }
 
@@ -1049,25 +1073,25 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   return hipGetLastError();
 }
 
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template ProjectKernels project_kernels_of<E>(int, int, bool, bool);
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template ProjectKernels project_kernels_of<E>(int, int, bool, bool, bool);
 OVR_VOXEL_TYPES(OVR_X)
 #undef OVR_X
 static ProjectKernels project_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   ProjectKernels k;
-  if (!plan.error) dispatch_voxel_type(p.vol.type, [&](auto vt) { k = project_kernels_of<decltype(vt)::value>(plan.am, plan.project.mode, plan.project.skip, plan.project.clipped); });
+  if (!plan.error) dispatch_voxel_type(p.vol.type, [&](auto vt) { k = project_kernels_of<decltype(vt)::value>(plan.am, plan.project.mode, plan.project.skip, plan.project.clipped, plan.orthographic); });
   return k;
 }
 
 // (the isosurface kernels exist for the general layout's types alone: ovr_hip_isosurface.hip, one object per such type)
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceKernels isosurface_kernels_of<E>(int, int, bool, bool);
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceKernels isosurface_kernels_of<E>(int, int, bool, bool, bool);
 OVR_VOXEL_TYPES(OVR_X)
 #undef OVR_X
 static IsosurfaceKernels isosurface_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   IsosurfaceKernels k;
   if (!plan.error && plan.isosurface.on)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.isosurface.clipped); });
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.isosurface.clipped, plan.orthographic); });
   return k;
 }
 
@@ -2004,18 +2028,19 @@ hipError_t launch_pow(const float* x, const float* y, float* out, int64_t n, int
 int built_for_exact_parity() { return OVR_PARITY_EXACT; }
 
 // known-answer entry of the shade factor: shade_light + shade_factor exactly as shade_request calls them, with the frame's parameter block
-template <bool MAT>
+template <bool MAT, bool ORTHO = false>
 __global__ void shade_floats_kernel(const RayMarchParams P, const float* normal_w, const float* pos, const float* shadow, float* out, long long n)
 {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const f3 n_w = mk3(normal_w[3 * i], normal_w[3 * i + 1], normal_w[3 * i + 2]), p = mk3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
-  out[i] = shade_factor<MAT>(P, shade_light<MAT>(P, ld3(P.light), n_w, p), shadow[i]);
+  out[i] = shade_factor<MAT>(P, shade_light<MAT, ORTHO>(P, ld3(P.light), n_w, p), shadow[i]);
 }
 hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, const float* pos, const float* shadow, float* out, int64_t n, hipStream_t stream)
 {
   if (n <= 0) return hipSuccess;
-  auto kern = reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>; // as plan_launch picks the frame's kernels
+  // as plan_launch picks the frame's kernels: an orthographic frame shades on the material variant (with the view vector -cam_dir)
+  auto kern = p.cam_orthographic ? shade_floats_kernel<true, true> : reference_material(p) ? shade_floats_kernel<false> : shade_floats_kernel<true>;
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, normal_w, pos, shadow, out, (long long)n);
   return hipGetLastError();
 }
@@ -2131,6 +2156,43 @@ hipError_t launch_clip_intervals(const RayMarchParams& p, const float* org, cons
   if (n <= 0) return hipSuccess;
   auto kern = p.clip_on ? clip_intervals_kernel<true> : clip_intervals_kernel<false>; // as plan_launch picks the frame's kernels
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, org, dir, t0t1hit, (long long)n);
+  return hipGetLastError();
+}
+
+// known-answer entry of the pixel ray: one lane per pixel; the screen position, the jitter of the sample and pixel_ray as the frame kernels form and call them
+// (raymarch_kernel's in-place form: RandomTEA(frame_index, pixel_index) advanced once per sample when spp > 1, the blue-noise variates of jitter_global)
+template <bool ORTHO>
+__global__ __launch_bounds__(256) void camera_rays_kernel(const RayMarchParams P, int sample, float* __restrict__ out)
+{
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)P.width * P.height) return;
+  const int ix = (int)(i % P.width), iy = (int)(i / P.width);
+  const float rsx = 1.f / (float)P.width, rsy = 1.f / (float)P.height;
+  float sx = ((float)ix + .5f) * rsx, sy = ((float)iy + .5f) * rsy;
+  if (P.jitter_mode == 1) {
+    float j0, j1;
+    jitter_global(P, ix, iy, sample, j0, j1);
+    sx += (j0 - 0.5f) * rsx;
+    sy += (j1 - 0.5f) * rsy;
+  }
+  else if (P.spp > 1) {
+    unsigned int v0 = (unsigned int)P.frame_index, v1 = (unsigned int)i;
+    for (int k = 0; k <= sample; ++k) tea16(v0, v1);
+    sx += ((float)v0 * OVR_TEA_TOFLOAT - 0.5f) * rsx;
+    sy += ((float)v1 * OVR_TEA_TOFLOAT - 0.5f) * rsy;
+  }
+  const float ux = sx - 0.5f, uy = sy - 0.5f;
+  f3 org, dir;
+  pixel_ray<ORTHO>(P, ux, uy, org, dir);
+  float* q = out + 6 * i;
+  q[0] = org.x; q[1] = org.y; q[2] = org.z; q[3] = dir.x; q[4] = dir.y; q[5] = dir.z;
+}
+hipError_t launch_camera_rays(const RayMarchParams& p, int sample, float* org_dir, hipStream_t stream)
+{
+  const long long n = (long long)p.width * p.height;
+  if (n <= 0) return hipSuccess;
+  auto kern = p.cam_orthographic ? camera_rays_kernel<true> : camera_rays_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, sample, org_dir);
   return hipGetLastError();
 }
 

@@ -143,10 +143,11 @@ def normals(tap_object, po, s, dims, inv_scale, vertex_centred=False):
 
 
 def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, shadows=True, light=None,
-               sampler=None):
+               sampler=None, camera_kind=0):
     """world rays org, direction (n, 3) - the direction used as given - -> what ovr_hip_isosurface_floats returns per ray, and the counters' parts:
     dict(hit, iso, t, steps, normal (n, 3), shadow, fetched, pos (n, 3), shadow_steps, shadow_fetched, tm_before, tm_at, k); zeros for a ray without a hit.
-    light: the raw vector towards the light (normalised here as the host does); sampler(po) replaces projection.sample (product_sampler)"""
+    light: the raw vector towards the light (normalised here as the host does); sampler(po) replaces projection.sample (product_sampler);
+    camera_kind = camera.ORTHOGRAPHIC: the rays are that camera's primary rays (camera.hits: a ray outside an ignored slab misses; shadow rays are untouched)"""
     vol = np.asarray(volume)
     nz, ny, nx = vol.shape
     dims = (nx, ny, nz)
@@ -170,7 +171,11 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
             ranges = (r[..., 0], r[..., 1])
         return s, walk(s, count, iso, ranges)
 
-    t0, t1, box = clipping.world_intervals(org, direction, inv, wp, lo, hi)
+    if camera_kind:
+        from . import camera
+        t0, t1, box = camera.hits(org, direction, inv, wp, lo, hi, camera_kind)
+    else:
+        t0, t1, box = clipping.world_intervals(org, direction, inv, wp, lo, hi)
     tm, count = steps(t0, t1, step, box)
     n = len(org)
     if tm.shape[1] == 0:
@@ -213,9 +218,10 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
 
 
 def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=None, intensity=1.0, material=lighting.REFERENCE_MATERIAL, spacing=(1, 1, 1),
-          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None):
+          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None, camera_kind=0):
     """one isosurface frame: rgba (H, W, 4), layer (H, W, 3) and counters.  basis = (pos, dir, hor, ver); tf_range in the samples' units
-    (projection.normalized_range); noise = the blue-noise tile switches that jitter on - without it spp must be 1, as in projection.frame"""
+    (projection.normalized_range); noise = the blue-noise tile switches that jitter on - without it spp must be 1, as in projection.frame;
+    camera_kind = camera.ORTHOGRAPHIC: the basis is an orthographic camera's - rays from camera.pixel_rays, the view vector -dir (the default: today's frame)"""
     w, h = size
     if noise is None and spp != 1:
         raise ValueError("without the blue-noise jitter the model forms the rays of one sample per pixel")
@@ -228,11 +234,16 @@ def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=
     for k in range(spp):
         xi = None if noise is None else blue_noise_variates(noise, w, h, frame_index, spp, k)
         d = pixel_rays(basis, w, h, xi).reshape(-1, 3)
-        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler)
+        view = None
+        if camera_kind:
+            from . import camera
+            org, d = (a.reshape(-1, 3) for a in camera.pixel_rays(basis, w, h, xi, camera_kind))
+            view = camera.view_vector(basis) if camera_kind == camera.ORTHOGRAPHIC else None
+        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler, camera_kind)
         m = r["hit"]
         rgb = classify(r["iso"], colors, np.zeros(2, F), *tf_range)[:, :3]
         if shading != NONE:
-            f = lighting.shade(r["normal"], r["pos"], r["shadow"], L, basis[0], ka, kd, ks, shin, intensity)
+            f = lighting.shade(r["normal"], r["pos"], r["shadow"], L, basis[0], ka, kd, ks, shin, intensity, view=view)
             with np.errstate(invalid="ignore", over="ignore"):
                 rgb = clamp01((rgb * f[:, None]).astype(F))
         c = np.concatenate([rgb, np.ones((h * w, 1), F)], 1)

@@ -127,8 +127,9 @@ def specular_power(cosNH, shininess):
     return np.where(ok, det_exp2((F(shininess) * det_log2(x)).astype(F)), F(0)).astype(F)
 
 
-def shade(normal_w, pos, shadow, light, cam_pos, ambient=0.5, diffuse=0.5, specular=0.0, shininess=0.0, intensity=1.0):
-    """the shade factor of n samples: normal_w (n, 3), pos (n, 3), shadow (n,); light = the UNIT direction (normalize(raw))"""
+def shade(normal_w, pos, shadow, light, cam_pos, ambient=0.5, diffuse=0.5, specular=0.0, shininess=0.0, intensity=1.0, view=None):
+    """the shade factor of n samples: normal_w (n, 3), pos (n, 3), shadow (n,); light = the UNIT direction (normalize(raw)).  view: the view vector of every
+    sample, used as given (the orthographic camera's -dir, camera.py); None = normalize(cam_pos - pos), the perspective camera's"""
     n_w, pos, shadow = np.asarray(normal_w, F), np.asarray(pos, F), np.asarray(shadow, F)
     L, cam = np.asarray(light, F), np.asarray(cam_pos, F)
     ka, kd, ks, i2 = F(ambient), F(diffuse), F(specular), F(2) * F(intensity)
@@ -136,7 +137,7 @@ def shade(normal_w, pos, shadow, light, cam_pos, ambient=0.5, diffuse=0.5, specu
         cosNL = np.abs(dot(np.broadcast_to(L, n_w.shape), n_w))
         d = ((kd * cosNL).astype(F) * i2).astype(F)
         if ks > 0:
-            V = normalize((cam - pos).astype(F))
+            V = normalize((cam - pos).astype(F)) if view is None else np.broadcast_to(np.asarray(view, F), n_w.shape)
             H = normalize((L + V).astype(F))
             cosNH = np.abs(dot(H, n_w))
             sp = specular_power(cosNH, shininess)

@@ -288,16 +288,22 @@ def normalized_range(value_range, dtype):
 
 
 # ---- rays and frames -------------------------------------------------------------------------------------------------------------------
-def project_rays(volume, org, direction, rate, mode, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, sampler=None, skipping=False):
+def project_rays(volume, org, direction, rate, mode, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, sampler=None, skipping=False,
+                 camera_kind=0):
     """world rays org, direction (n, 3) - the direction used as given - -> dict(v, tm, steps, fetched, marched): what ovr_hip_project_floats returns
-    (zeros for a ray that is not marched).  clip = (lo, hi): the OBJECT box; sampler(po) -> samples replaces the model's own tap (tests pass the oracle's)"""
+    (zeros for a ray that is not marched).  clip = (lo, hi): the OBJECT box; sampler(po) -> samples replaces the model's own tap (tests pass the oracle's);
+    camera_kind = camera.ORTHOGRAPHIC: the rays are that camera's primary rays (camera.hits: a ray outside an ignored slab misses)"""
     vol = np.asarray(volume)
     nz, ny, nx = vol.shape
     dims = (nx, ny, nz)
     org, direction = np.asarray(org, F).reshape(-1, 3), np.asarray(direction, F).reshape(-1, 3)
     inv, wp = clipping.volume_constants(dims, spacing, origin, vertex_centred)
     lo, hi = ((0, 0, 0), (1, 1, 1)) if clip is None else clip
-    t0, t1, hit = clipping.world_intervals(org, direction, inv, wp, lo, hi)
+    if camera_kind:
+        from . import camera
+        t0, t1, hit = camera.hits(org, direction, inv, wp, lo, hi, camera_kind)
+    else:
+        t0, t1, hit = clipping.world_intervals(org, direction, inv, wp, lo, hi)
     tm, count = steps(t0, t1, F(1) / F(rate), hit)
     n, width = tm.shape
     with np.errstate(invalid="ignore", over="ignore"):
@@ -319,9 +325,10 @@ def project_rays(volume, org, direction, rate, mode, spacing=(1, 1, 1), origin=(
 
 
 def frame(volume, basis, size, rate, mode, colors, alphas, tf_range, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, sampler=None,
-          skipping=False, spp=1, noise=None, frame_index=1):
+          skipping=False, spp=1, noise=None, frame_index=1, camera_kind=0):
     """one projection frame: rgba (H, W, 4), layer (H, W, 3) and counters.  basis = (pos, dir, hor, ver); tf_range in the samples' units (normalized_range);
-    noise = the blue-noise tile ([y][x][t]) switches that jitter on - without it spp must be 1 (the RandomTEA jitter is not restated here)"""
+    noise = the blue-noise tile ([y][x][t]) switches that jitter on - without it spp must be 1 (the RandomTEA jitter is not restated here);
+    camera_kind = camera.ORTHOGRAPHIC: the basis is an orthographic camera's and the rays come from camera.pixel_rays (the default: today's rays, bit for bit)"""
     w, h = size
     if noise is None and spp != 1:
         raise ValueError("without the blue-noise jitter the model forms the rays of one sample per pixel")
@@ -331,7 +338,10 @@ def frame(volume, basis, size, rate, mode, colors, alphas, tf_range, spacing=(1,
     for k in range(spp):
         xi = None if noise is None else blue_noise_variates(noise, w, h, frame_index, spp, k)
         d = pixel_rays(basis, w, h, xi).reshape(-1, 3)
-        r = project_rays(volume, org, d, rate, mode, spacing, origin, vertex_centred, clip, sampler, skipping)
+        if camera_kind:
+            from . import camera
+            org, d = (a.reshape(-1, 3) for a in camera.pixel_rays(basis, w, h, xi, camera_kind))
+        r = project_rays(volume, org, d, rate, mode, spacing, origin, vertex_centred, clip, sampler, skipping, camera_kind)
         m = r["marched"]
         c = classify(r["v"], colors, alphas, *tf_range)
         rgba = (rgba + np.where(m[:, None], c, F(0))).astype(F)

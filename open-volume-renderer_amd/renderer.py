@@ -24,11 +24,13 @@ _NP_TO_TYPE = {
 
 @dataclass
 class Camera:
-    """ovr::scene::Camera (reference ovr/scene.h:201-231); fovy defaults to 60 like PerspectiveCamera."""
+    """ovr::scene::Camera (reference ovr/scene.h:201-231); fovy defaults to 60 like PerspectiveCamera.  orthographic_height: None = the perspective
+    camera; a number = the orthographic camera (scene.h's type ORTHOGRAPHIC) whose image is that high in world units (camera.py), fovy is then not read."""
     eye: Sequence[float] = (0.0, 0.0, -1000.0)   # `from` in the reference (a Python keyword)
     at: Sequence[float] = (0.0, 0.0, 0.0)
     up: Sequence[float] = (0.0, 1.0, 0.0)
     fovy: float = 60.0
+    orthographic_height: Optional[float] = None
 
 
 @dataclass
@@ -115,6 +117,7 @@ class DeviceHIP:
         self.current_scene: Optional[Scene] = None
         self.variance = float("inf")          # renderer.h:287
         self._fbsize = (0, 0)
+        self._committed_fbsize = (0, 0)       # what the last commit() made current: the size ovr_hip_camera_rays writes
         self._keep = []                        # keeps ctypes buffers alive across calls
         self._convergence_mode = L.CONVERGENCE_OFF
         self._light_dir = None                 # None = the reference's literal
@@ -143,7 +146,29 @@ class DeviceHIP:
         """set_camera(Camera) or set_camera(from, at, up).  The three-vector form builds Camera{from, at, up} whose fovy
         is the default 60 degrees - exactly what renderer.h:149-152 does (it discards a scene's fovy)."""
         cam = camera_or_from if isinstance(camera_or_from, Camera) else Camera(camera_or_from, at, up)
-        L.check(self._lib.ovr_hip_set_camera(self._h, _f3(cam.eye), _f3(cam.at), _f3(cam.up), float(cam.fovy)))
+        if cam.orthographic_height is not None:
+            L.check(self._lib.ovr_hip_set_camera_orthographic(self._h, _f3(cam.eye), _f3(cam.at), _f3(cam.up), float(cam.orthographic_height)))
+        else:
+            L.check(self._lib.ovr_hip_set_camera(self._h, _f3(cam.eye), _f3(cam.at), _f3(cam.up), float(cam.fovy)))
+
+    def get_camera(self):
+        """ovr_hip_get_camera, the COMMITTED camera: kind (0 perspective, 1 orthographic), eye / at / up, fovy, height as given, and pos / dir / hor / ver,
+        the basis the kernels read"""
+        c = L.CameraState()
+        L.check(self._lib.ovr_hip_get_camera(self._h, C.byref(c)))
+        return c
+
+    def camera_rays(self, frame_index=1, sample=0):
+        """the pixel rays as the kernels form them (ovr_hip_camera_rays; known-answer tests): (org, dir), each (H, W, 3) float32, of the given sample of the
+        given frame under the committed camera, framebuffer size, jitter mode and samples per pixel"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        w, h = self._committed_fbsize         # (a size queued by set_fbsize and not yet committed is not the entry's)
+        out = torch.empty((max(h, 0), max(w, 0), 6), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_camera_rays(self._h, int(frame_index), int(sample), out.data_ptr(), out.numel()))
+        o = out.cpu().numpy()
+        return o[..., :3].copy(), o[..., 3:].copy()
 
     def set_transfer_function(self, c, o, r):
         """c: flat RGB triples, o: flat (position, alpha) pairs, r: (lo, hi) in raw data units (renderer.h:154-161)."""
@@ -610,6 +635,7 @@ class DeviceHIP:
 
     def commit(self):
         L.check(self._lib.ovr_hip_commit(self._h))
+        self._committed_fbsize = self._fbsize
 
     def render(self):
         L.check(self._lib.ovr_hip_render(self._h))

@@ -14,12 +14,14 @@ _TYPE_NAME = {np.dtype(np.uint8): "UNSIGNED_BYTE", np.dtype(np.int8): "BYTE", np
 
 
 def write_scene(directory, name, volume, color_controls, alpha_table, scalar_range_normalized, camera, fovy=45.0,
-                sample_distance=1.0, clipping_box=None):
+                sample_distance=1.0, clipping_box=None, projection_mode="PERSPECTIVE"):
     """volume: (nz, ny, nx) array; color_controls: [(position, r, g, b)]; alpha_table: float32 opacities (its length is the
     TF resolution); scalar_range_normalized: (lo, hi) as a fraction of the type's maximum for integer data, raw for floats
     (scalarMappingRange, serializer_vidi3d.cpp:236-272); camera: (eye, center, up); clipping_box: (lower, upper) in world units
     (spacing 1: voxels) or None - written as `clippingBox` in the units of `boundingBox`, which spans (0, 0, 0) .. dims - 1 as in
-    the reference's shipped scenes (`read_scene` maps it back)."""
+    the reference's shipped scenes (`read_scene` maps it back); projection_mode: "PERSPECTIVE" or "ORTHOGRAPHIC", the camera's `projectionMode`."""
+    if projection_mode not in ("PERSPECTIVE", "ORTHOGRAPHIC"):
+        raise ValueError("projection_mode is PERSPECTIVE or ORTHOGRAPHIC")
     os.makedirs(directory, exist_ok=True)
     volume = np.ascontiguousarray(volume)
     raw = os.path.join(directory, name + ".raw")
@@ -35,7 +37,7 @@ def write_scene(directory, name, volume, color_controls, alpha_table, scalar_ran
             "type": _TYPE_NAME[volume.dtype]}],
         "snapshot": [],
         "view": {
-            "camera": {"center": xyz(center), "eye": xyz(eye), "fovy": float(fovy), "projectionMode": "PERSPECTIVE", "up": xyz(up),
+            "camera": {"center": xyz(center), "eye": xyz(eye), "fovy": float(fovy), "projectionMode": projection_mode, "up": xyz(up),
                        "zFar": 10000.0, "zNear": 1.0},
             "lightSource": {"ambient": {"a": 1, "b": 1, "g": 1, "r": 1}, "diffuse": {"a": 1, "b": 1, "g": 1, "r": 1},
                             "position": {"w": 0, "x": 0, "y": 0, "z": 1}, "specular": {"a": 1, "b": 1, "g": 1, "r": 1},
@@ -247,7 +249,7 @@ def read_scene(path, load_volume=True):
     return dict(volume=volume, dtype=dtype, dims=(nx, ny, nz), grid_origin=(0.0, 0.0, 0.0), grid_spacing=spacing,
                 tfn_color=color, tfn_opacity=opacity, value_range=(float(vr[0]), float(vr[1])),
                 camera=(xyz(cam["eye"]), xyz(cam["center"]), xyz(cam["up"]), float(cam["fovy"])), lights=lights,
-                volume_sampling_rate=float(rate), clipping_box=clipping_box)
+                volume_sampling_rate=float(rate), clipping_box=clipping_box, projection_mode=str(cam.get("projectionMode", "PERSPECTIVE")).upper())
 
 
 def scene_from_file(path):
@@ -256,6 +258,9 @@ def scene_from_file(path):
     d = read_scene(path)
     eye, at, up, fovy = d["camera"]
     cam = Camera(eye, at, up, fovy)
+    if d["projection_mode"] == "ORTHOGRAPHIC":  # the format has no height: the parallel view with the same extent at the plane through `center`
+        from . import camera
+        cam.orthographic_height = camera.auto_height(eye, at, fovy)
     scene = Scene(volume=d["volume"], grid_origin=d["grid_origin"], grid_spacing=d["grid_spacing"],
                   transfer_function=TransferFunction(color=d["tfn_color"], opacity=d["tfn_opacity"], value_range=d["value_range"]),
                   camera=cam, volume_sampling_rate=d["volume_sampling_rate"], clipping_box=d["clipping_box"])

@@ -11,6 +11,7 @@
 
 #include "../include/ovr_hip.h"
 #include "isovalues_env.hpp"
+#include "orthographic_env.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -213,7 +214,22 @@ public:
     if (params.camera.update()) {
       const ovr::scene::Camera& c = params.camera.ref();
       const float from[3] = { c.from.x, c.from.y, c.from.z }, at[3] = { c.at.x, c.at.y, c.at.z }, up[3] = { c.up.x, c.up.y, c.up.z };
-      check(ovr_hip_set_camera(h, from, at, up, c.perspective.fovy));
+      // The orthographic camera (ovr_hip_set_camera_orthographic): the interface's Camera::type, which the OSPRay device honours and the OptiX device never
+      // reads.  The batch app's scene loader never sets the type, so OVR_HIP_ORTHOGRAPHIC=<height>|auto forces it: the image's world height, or `auto` = the
+      // parallel view with the perspective view's extent at the plane through `at`, 2 |from - at| tan(fovy / 2).  Unset: the type decides
+      float height = 0.f;
+      int ortho = c.type == ovr::scene::Camera::ORTHOGRAPHIC ? ovrhip_plugin::kOrthographicHeight : 0;
+      if (ortho) height = c.orthographic.height;
+      if (const char* ov = std::getenv("OVR_HIP_ORTHOGRAPHIC")) {
+        ortho = ovrhip_plugin::parse_orthographic(ov, &height); // (the whole string: anything but a height > 0 or `auto` is an error)
+        if (ortho == ovrhip_plugin::kOrthographicError) throw std::runtime_error("[hip] OVR_HIP_ORTHOGRAPHIC expects the image's world height (> 0) or auto");
+        if (ortho == ovrhip_plugin::kOrthographicAuto) height = ovrhip_plugin::auto_orthographic_height(from, at, c.perspective.fovy);
+        const bool quiet = std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0';
+        if (!quiet && height != said_height) std::fprintf(stderr, "[hip] orthographic camera: image height %g%s\n", (double)height, ortho == ovrhip_plugin::kOrthographicAuto ? " (auto)" : "");
+        said_height = height;
+      }
+      if (ortho) check(ovr_hip_set_camera_orthographic(h, from, at, up, height));
+      else check(ovr_hip_set_camera(h, from, at, up, c.perspective.fovy));
     }
     if (params.tfn.update()) {
       const auto& t = params.tfn.ref();
@@ -299,6 +315,8 @@ private:
   bool angles_set = false;
   ovr_hip_renderer* h = nullptr;
   bool have_noise = false;
+  float said_height = 0.f; // OVR_HIP_ORTHOGRAPHIC: the height last reported on stderr (the camera is forwarded with every change; said once per value)
+
   int convergence_mode = OVR_HIP_CONVERGENCE_OFF;
 };
 

@@ -7,8 +7,9 @@ DESIGN.md section 12 and profiles/r09_clipping.md.
     --all                                                 every kernel of the library, not only the march / shade kernels; with --against the
                                                           kernels only PARENT has are listed by name (--removed N: exactly N of them are expected)
 
-A template parameter appended behind the existing ones with the value `false` (how MAT and CLIP were added) renames every kernel: names are compared
-with trailing `false` parameters removed."""
+A template parameter appended behind the existing ones with the value `false` (how MAT, CLIP and ORTHO were added) renames every kernel: names are
+compared with trailing `false` parameters removed - of the march and shade kernels, and of the projection, isosurface, schedule and shade-factor kernels,
+which the orthographic camera gave such a parameter."""
 import argparse
 import os
 import re
@@ -50,7 +51,7 @@ def read(lib, every=False):
 
 def key(name):
     """the instantiation without trailing `false` template parameters"""
-    m = re.match(r"(.*?(?:raymarch_kernel|shade_pool_kernel)I)((?:L[ib]\d+E)+)(E.*)", name)
+    m = re.match(r"(.*?(?:raymarch_kernel|shade_pool_kernel|project_kernel|isosurface_kernel|schedule_classify_kernel|shade_floats_kernel)I)((?:L[ib]\d+E)+)(E.*)", name)
     if not m:
         return name
     params = re.findall(r"L[ib]\d+E", m.group(2))

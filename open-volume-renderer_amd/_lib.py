@@ -145,6 +145,16 @@ class Isosurfaces(C.Structure):
     ]
 
 
+class IsosurfaceLayers(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("isovalues", C.c_float * MAX_ISOVALUES),
+        ("opacities", C.c_float * MAX_ISOVALUES),
+        ("translucent", C.c_int32),
+        ("range_skipping", C.c_int32),
+    ]
+
+
 CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC = 0, 1
 
 
@@ -248,6 +258,9 @@ SYMBOLS = {
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_isosurface_layers": (C.c_int, [_H, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
+    "ovr_hip_get_isosurface_layers": (C.c_int, [_H, C.POINTER(IsosurfaceLayers)]),
+    "ovr_hip_isosurface_layers_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "ovr_hip_update_volume": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ovr_hip_get_update_times": (C.c_int, [_H, C.POINTER(C.c_double)]),

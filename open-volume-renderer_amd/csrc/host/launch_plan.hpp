@@ -80,10 +80,12 @@ constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped,
 // layouts for up to kMaxIsovalues isovalues.  shade: the committed shading mode (0 colour alone, 1 gradient-shaded, 2 with the hard shadow walk); skip: the
 // range-skipping twin, which every shading mode has (primary and shadow walk skip alike); the material is a run-time argument, not a variant
 constexpr int kMaxIsovalues = 4; // include/ovr_hip.h OVR_HIP_MAX_ISOVALUES
-constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false)
+// translucent: every crossing composited with its isovalue's opacity - like the orthographic twins ON THE CLIPPED VARIANTS ALONE (a frame
+// without a clip box runs them with the unit box, whose bounds give the unclipped test's bits), for both cameras
+constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false, bool translucent = false)
 {
   (void)skip; // both walks and both box tests exist for every variant, the orthographic camera on the clipped test
-  if (orthographic && !clipped) return false;
+  if ((orthographic || translucent) && !clipped) return false;
   return shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
 }
 
@@ -137,6 +139,7 @@ struct LaunchFacts {
   bool ranges = false;                // the macrocells' value ranges are bound (RayMarchParams::mc_ranges): an extremum may skip by them
   bool orthographic = false;          // the committed camera is orthographic (ovr_hip_set_camera_orthographic): the frame takes the orthographic twins of the clipped variants
   int isosurfaces = 0;                // the number of committed isovalues; > 0: an isosurface frame - `projection` is kept but not drawn, pool, majorants and LDS staging are not read
+  bool translucent = false;           // one of the committed isovalues' opacities is below 1 (ovr_hip_set_isosurface_layers): an isosurface frame takes the translucent twins
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -153,7 +156,7 @@ struct LaunchPlan {
   // a projection frame (LaunchFacts::projection != 0): project_kernel in the march's place, nothing else of the plan but `am` is read
   struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
   // an isosurface frame (LaunchFacts::isosurfaces > 0): isosurface_kernel in the march's place, nothing else of the plan but `am` and `shading` is read
-  struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; } isosurface;
+  struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; bool translucent = false; } isosurface;
   size_t march_lds_bytes = 0, shade_lds_bytes = 0;
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
@@ -209,7 +212,8 @@ inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.isosurface.on = true;
   pl.isosurface.skip = f.ranges;
-  pl.isosurface.clipped = f.clip_on || f.orthographic;
+  pl.isosurface.translucent = f.translucent;
+  pl.isosurface.clipped = f.clip_on || f.orthographic || f.translucent; // (a translucent frame without a clip box: the clipped variant with the unit box, like an orthographic one)
   pl.orthographic = f.orthographic;
   pl.isosurface.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
   pl.march_lds_bytes = pl.isosurface.lds_bytes; // isosurface_kernel takes the in-place march's place in the launch sequence
@@ -271,7 +275,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
-  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic);
+  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent);
   if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
                               pl.cached && !pl.pooled, pl.orthographic) &&
@@ -286,5 +290,7 @@ static_assert(shade_variant_exists(1, 0, false, true, false, false, true) && sha
 static_assert(project_variant_exists(kProjectMaximum, 0, true, true, true) && !project_variant_exists(kProjectMaximum, 0, true, false, true)
                 && isosurface_variant_exists(2, 0, true, true, true) && !isosurface_variant_exists(2, 0, true, false, true),
               "the orthographic projection and isosurface kernels: on the clipped variants alone");
+static_assert(isosurface_variant_exists(2, 0, true, true, false, true) && isosurface_variant_exists(0, 4, false, true, true, true) && !isosurface_variant_exists(2, 0, true, false, false, true),
+              "the translucent isosurface kernels: on the clipped variants alone, for both cameras");
 
 } // namespace ovrhip

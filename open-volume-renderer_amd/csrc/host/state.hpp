@@ -68,7 +68,13 @@ struct TfnP { std::vector<float> colors, alphas; float lo = 1, hi = -1; };
 struct ShardP { int rank = 0, world = 1, tw = 64, th = 64; };
 struct Size2 { int w = 0, h = 0; };
 struct ConvP { int mode = OVR_HIP_CONVERGENCE_OFF; float threshold = 0.f; };
-struct IsoP { int n = 0; float v[OVR_HIP_MAX_ISOVALUES] = { 0.f, 0.f, 0.f, 0.f }; };
+// a: the isovalues' opacities in (0, 1], travelling with v (ovr_hip_set_isosurface_layers); 1 behind n and after ovr_hip_set_isosurfaces
+struct IsoP {
+  int n = 0;
+  float v[OVR_HIP_MAX_ISOVALUES] = { 0.f, 0.f, 0.f, 0.f };
+  float a[OVR_HIP_MAX_ISOVALUES] = { 1.f, 1.f, 1.f, 1.f };
+  bool translucent() const { for (int k = 0; k < n; ++k) if (a[k] < 1.f) return true; return false; }
+};
 // ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
 // and the 0.5 / 0.5 of its shade expression (shaders_raymarching.cu:138,156-157)
 struct LightP { float dir[3] = { -907.108f, 2205.875f, -400.0267f }; float intensity = 1.f; };

@@ -293,22 +293,45 @@ int ovr_hip_get_projection(const ovr_hip_renderer* r, ovr_hip_projection* out)
   return 0;
 }
 
-int ovr_hip_set_isosurfaces(ovr_hip_renderer* r, const float* isovalues, int32_t n)
+// both setters of the isosurfaces: one queued slot.  opacities == nullptr: all 1, the opaque level sets
+int ovr_hip_set_isosurface_layers(ovr_hip_renderer* r, const float* isovalues, const float* opacities, int32_t n)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
   if (n < 0 || n > OVR_HIP_MAX_ISOVALUES || (n > 0 && !isovalues)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: between 0 and 4 isovalues");
   IsoP p;
   p.n = n;
+  int order[OVR_HIP_MAX_ISOVALUES] = { 0, 1, 2, 3 };
   for (int k = 0; k < n; ++k) {
     if (!std::isfinite(isovalues[k])) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: the isovalues must be finite");
-    p.v[k] = isovalues[k];
+    if (opacities && !(std::isfinite(opacities[k]) && opacities[k] > 0.f && opacities[k] <= 1.f))
+      return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurface_layers: an opacity lies in (0, 1]");
   }
-  std::sort(p.v, p.v + n);
+  std::sort(order, order + n, [&](int a, int b) { return isovalues[a] < isovalues[b]; });
+  for (int k = 0; k < n; ++k) { // the opacities travel with their isovalues
+    p.v[k] = isovalues[order[k]];
+    p.a[k] = opacities ? opacities[order[k]] : 1.f;
+  }
   for (int k = 1; k < n; ++k)
     if (p.v[k] == p.v[k - 1]) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurfaces: two isovalues are equal");
   GroupLock gl(r);
   { std::lock_guard<std::mutex> lk(r->mtx); r->isosurfaces.set(p); }
-  GROUP_FORWARD(r, ovr_hip_set_isosurfaces(m, isovalues, n));
+  GROUP_FORWARD(r, ovr_hip_set_isosurface_layers(m, isovalues, opacities, n));
+  return 0;
+}
+
+int ovr_hip_set_isosurfaces(ovr_hip_renderer* r, const float* isovalues, int32_t n) { return ovr_hip_set_isosurface_layers(r, isovalues, nullptr, n); }
+
+int ovr_hip_get_isosurface_layers(const ovr_hip_renderer* r, ovr_hip_isosurface_layers* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_isosurface_layers: null argument");
+  const IsoP& p = r->isosurfaces.current;
+  out->n = p.n;
+  for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) {
+    out->isovalues[k] = k < p.n ? p.v[k] : 0.f;
+    out->opacities[k] = k < p.n ? p.a[k] : 0.f;
+  }
+  out->translucent = p.translucent() ? 1 : 0;
+  out->range_skipping = r->isosurface_skipped ? 1 : 0;
   return 0;
 }
 
@@ -1295,6 +1318,23 @@ int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_isosurface_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events, int32_t range_skipping)
+{
+  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_layers_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: no volume was set");
+  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: no isovalue is committed (ovr_hip_set_isosurface_layers)");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
+  fill_isosurface_params(r, q);
+  q.mc_ranges = projection_ranges(r);
+  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: the resident volume has no macrocell ranges");
+  HIP_TRY(launch_isosurface_layers_floats(q, org, dir, out, n, max_events, range_skipping != 0, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

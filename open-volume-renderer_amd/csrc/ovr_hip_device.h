@@ -2421,10 +2421,16 @@ struct IsoWalk {
   unsigned int fetched, skipped;  // THIS LANE's walked steps whose voxels were fetched / whose fetch was dropped
 };
 
+// what a resumed walk takes over from the walk before it (the translucent isosurfaces).  In: the side and tm of the step before the walk's
+// first one - the hit step of the walk before (side -1: there is none).  Out, on a hit: the hit step's ty, where the next walk's recurrence goes on
+// (tx_{i+1} = ty_i, CONTINUED, never recomputed from tm).  A resumed walk deals its steps to the lanes from its own start: the definition is per step
+struct IsoCarry { int side; float tm, ty; };
+
 // the first crossing along org + t dir: steps by the projection's recurrence from tx = tx0 to t1; live: the ray is walked (quad-uniform)
-template <int VT, int AM, bool SKIP>
+// RESUME: the walk may continue another one (carry), and hands back what the next one needs
+template <int VT, int AM, bool SKIP, bool RESUME = false>
 __device__ __forceinline__ IsoWalk iso_walk(const RayMarchParams& P, const VolConsts& vc, const MarchConsts& mc, f3 org, f3 dir, float tx0, float t1, bool live,
-                                            const SubMask& subm)
+                                            const SubMask& subm, IsoCarry* carry = nullptr)
 {
   constexpr int K = kProjectK;
   const int sub = subm.sub;
@@ -2433,10 +2439,12 @@ __device__ __forceinline__ IsoWalk iso_walk(const RayMarchParams& P, const VolCo
   unsigned int own = 0;
   int carry_side = -1; // the side of the step before the round's first; -1: there is none (step 0 has no predecessor)
   float carry_tm = 0.f;
+  if constexpr (RESUME) { carry_side = carry->side; carry_tm = carry->tm; }
   float tx = tx0, ty = fminf(t1, tx0 + mc.step);
   while (__ballot(live) != 0ull) {
     unsigned int vmask = 0;
     float tms[K];
+    [[maybe_unused]] float tys[K]; // RESUME: this lane's steps' ty
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       float txq[4], tyq[4];
@@ -2448,6 +2456,7 @@ __device__ __forceinline__ IsoWalk iso_walk(const RayMarchParams& P, const VolCo
         ty = fminf(tx + mc.step, t1);
       }
       tms[k] = 0.5f * (sel4(txq[0], txq[1], txq[2], txq[3], subm) + sel4(tyq[0], tyq[1], tyq[2], tyq[3], subm));
+      if constexpr (RESUME) tys[k] = sel4(tyq[0], tyq[1], tyq[2], tyq[3], subm);
     }
     Tap taps[K];
     bool mine[K], fetch[K];
@@ -2532,6 +2541,13 @@ __device__ __forceinline__ IsoWalk iso_walk(const RayMarchParams& P, const VolCo
       const float ta = wl > 0 ? ta_left : ta_carry;
       const int sb = quad_bcast_i(s_at, wl), sa = quad_bcast_i(s_before, wl);
       if (found) { w.hit = true; w.ta = ta; w.tb = tb; w.side_a = sa; w.side_b = sb; }
+      if constexpr (RESUME) {
+        float ty_at = tys[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) ty_at = k == kq ? tys[k] : ty_at;
+        const float ty_hit = quad_pick(ty_at, wl);
+        if (found) carry->ty = ty_hit;
+      }
     }
     carry_side = __builtin_amdgcn_update_dpp(0, sd[K - 1], 0xff, 0xf, 0xf, true);
     carry_tm = quad_bcast<3>(tms[K - 1]);
@@ -2552,6 +2568,184 @@ struct IsoResult {
   float shadow;                             // SHADE == 2: 1 iff the shadow ray crosses a level set
   unsigned int fetched, skipped, shadow_fetched, shadow_skipped; // THIS LANE's
 };
+
+// ---- translucent isosurfaces (include/ovr_hip.h ovr_hip_set_isosurface_layers; isosurface.py is the arithmetic).  The opaque path below
+// (isosurface_ray without TRANS) is kept as it was, text and code: what the translucent ray shares with it - the refinement, the gradient taps - is restated here
+// one crossing of a translucent ray
+struct IsoPoint {
+  float t;                                  // t* (quad-uniform, like pos ... shadow_steps)
+  f3 pos, n_w;                              // pos*, the world normal (SHADE >= 1)
+  float shadow;                             // SHADE == 2: the opacity the shadow ray accumulated
+  unsigned int shadow_steps;                // the steps of its shadow walks
+  unsigned int shadow_fetched, shadow_skipped; // THIS LANE's
+};
+
+// isovalue k and its opacity (k quad-uniform, 0 ... 3)
+__device__ __forceinline__ float iso_value(const RayMarchParams& P, int ks)
+{
+  float iso = P.iso_values[0];
+#pragma unroll
+  for (int k = 1; k < kMaxIsovalues; ++k) iso = ks == k ? P.iso_values[k] : iso;
+  return iso;
+}
+__device__ __forceinline__ float iso_opacity(const RayMarchParams& P, int ks)
+{
+  float a = P.iso_opacities[0];
+#pragma unroll
+  for (int k = 1; k < kMaxIsovalues; ++k) a = ks == k ? P.iso_opacities[k] : a;
+  return a;
+}
+// the events of a step from side sa to side sb != sa, in the order the ray meets them: the first isovalue crossed and the direction
+__device__ __forceinline__ void iso_step_events(int sa, int sb, int& k0, int& dk, int& n)
+{
+  const bool rising = sb > sa;
+  k0 = rising ? sa : sa - 1; // rising: the lowest isovalue crossed first; falling: the highest
+  dk = rising ? 1 : -1;
+  n = rising ? sb - sa : sa - sb;
+}
+
+// one crossing of the level iso on the walk's pair (ta, tb) of the ray org + t dir: refined, and under SHADE >= 1 its normal, under SHADE == 2 its shadow term -
+// by the opaque hit's operations.  hit: the quad has a crossing (the others tap along, clamped).  The shadow ray accumulates the opacities of the level sets it
+// crosses, walk by walk, until it saturates
+template <int VT, int AM, int SHADE, bool SKIP, bool CLIP>
+__device__ __forceinline__ void iso_point(const RayMarchParams& P, const VolConsts& vc, const MarchConsts& mc, f3 org, f3 dir, float iso, float ta, float tb, bool hit,
+                                          const SubMask& subm, IsoPoint& res)
+{
+  const int sub = subm.sub;
+  auto tap_at = [&](float t) {
+    const f3 p = mk3(fmaf(t, dir.x, org.x), fmaf(t, dir.y, org.y), fmaf(t, dir.z, org.z));
+    return sample_volume<VT, AM>(vc, to_object(mc, p));
+  };
+  // the pair's samples: lanes 0 and 1, one instruction (the other two lanes repeat them)
+  const float se = tap_at((sub & 1) ? tb : ta);
+  float sa = quad_bcast<0>(se), sb = quad_bcast<1>(se);
+#pragma unroll
+  for (int round = 0; round < 2; ++round) {
+    const float wd = tb - ta;
+    const float p1 = fmaf(0.2f, wd, ta), p2 = fmaf(0.4f, wd, ta), p3 = fmaf(0.6f, wd, ta), p4 = fmaf(0.8f, wd, ta);
+    const float q = tap_at(sel4(p1, p2, p3, p4, subm));
+    const float q1 = quad_bcast<0>(q), q2 = quad_bcast<1>(q), q3 = quad_bcast<2>(q), q4 = quad_bcast<3>(q);
+    const bool i0 = iso <= sa, i1 = iso <= q1, i2 = iso <= q2, i3 = iso <= q3, i4 = iso <= q4, i5 = iso <= sb;
+    float nta = ta, nsa = sa, ntb = tb, nsb = sb; // (the last assignment that fires is the FIRST pair that differs)
+    if (i4 != i5) { nta = p4; nsa = q4; ntb = tb; nsb = sb; }
+    if (i3 != i4) { nta = p3; nsa = q3; ntb = p4; nsb = q4; }
+    if (i2 != i3) { nta = p2; nsa = q2; ntb = p3; nsb = q3; }
+    if (i1 != i2) { nta = p1; nsa = q1; ntb = p2; nsb = q2; }
+    if (i0 != i1) { nta = ta; nsa = sa; ntb = p1; nsb = q1; }
+    ta = nta; sa = nsa; tb = ntb; sb = nsb;
+  }
+  const float ts = fminf(fmaxf(fmaf((iso - sa) / (sb - sa), tb - ta, ta), ta), tb);
+  res.t = ts;
+  const f3 pos = mk3(fmaf(ts, dir.x, org.x), fmaf(ts, dir.y, org.y), fmaf(ts, dir.z, org.z));
+  res.pos = pos;
+  if (SHADE == 0) return;
+  {
+    // shade_request's forward difference: lane 0 taps s*, lanes 1 ... 3 the three neighbours - one instruction
+    const f3 po = to_object(mc, pos);
+    const bool flx = (po.x + mc.gstep.x) > 1.f, fly = (po.y + mc.gstep.y) > 1.f, flz = (po.z + mc.gstep.z) > 1.f;
+    const float dx = flx ? -mc.gstep.x : mc.gstep.x, dy = fly ? -mc.gstep.y : mc.gstep.y, dz = flz ? -mc.gstep.z : mc.gstep.z;
+    const f3 pg = mk3(sub == 1 ? po.x + dx : po.x, sub == 2 ? po.y + dy : po.y, sub == 3 ? po.z + dz : po.z);
+    const float sg = sample_volume<VT, AM>(vc, pg);
+    const float ss = quad_bcast<0>(sg), sgx = quad_bcast<1>(sg), sgy = quad_bcast<2>(sg), sgz = quad_bcast<3>(sg);
+    f3 g;
+#if OVR_PARITY_EXACT
+    g.x = (sgx - ss) / dx; g.y = (sgy - ss) / dy; g.z = (sgz - ss) / dz;
+#else
+    g.x = (sgx - ss) * (flx ? -mc.ginv.x : mc.ginv.x);
+    g.y = (sgy - ss) * (fly ? -mc.ginv.y : mc.ginv.y);
+    g.z = (sgz - ss) * (flz ? -mc.ginv.z : mc.ginv.z);
+#endif
+    const f3 gn = normalize3(g);
+    res.n_w = normalize3(mk3(-gn.x * mc.otw_it.x, -gn.y * mc.otw_it.y, -gn.z * mc.otw_it.z));
+  }
+  if (SHADE == 2) {
+    // the hard shadow: the first crossing along pos* + t light from 1.5 steps on, nothing refined
+    const f3 oo = to_object(mc, pos);
+    const f3 od = mk3(mc.light.x * mc.inv_scale.x, mc.light.y * mc.inv_scale.y, mc.light.z * mc.inv_scale.z);
+    float s0 = 0.f, s1 = FLT_MAX;
+    const bool lit_ray = box_test<CLIP>(P, s0, s1, oo, od) && hit;
+    {
+      // the partial shadow: A_s = fma(1 - A_s, alpha_k, A_s) over the shadow ray's events, walk by walk, until it saturates.  Every pass of a ray that goes on
+      // has consumed at least one of its steps: the loop is bounded by the ray's step count
+      IsoCarry sc;
+      sc.side = -1; sc.tm = 0.f; sc.ty = 0.f;
+      float As = 0.f, stx = s0 + mc.step;
+      bool go = lit_ray;
+      while (__ballot(go) != 0ull) {
+        const IsoWalk sw = iso_walk<VT, AM, SKIP, true>(P, vc, mc, pos, mc.light, stx, s1, go, subm, &sc);
+        res.shadow_fetched += sw.fetched; res.shadow_skipped += sw.skipped; res.shadow_steps += sw.steps;
+        if (sw.hit) {
+          int k, dk, n;
+          iso_step_events(sw.side_a, sw.side_b, k, dk, n);
+#pragma unroll
+          for (int e = 0; e < kMaxIsovalues; ++e) {
+            if (e < n && !(As >= 0.9999f)) As = fmaf(1.f - As, iso_opacity(P, k), As);
+            k += dk;
+          }
+        }
+        go = sw.hit && !(As >= 0.9999f);
+        stx = sc.ty; sc.side = sw.side_b; sc.tm = sw.tb;
+      }
+      res.shadow = As;
+    }
+  }
+}
+
+// a translucent ray (open-volume-renderer_amd/isosurface.py is the arithmetic)
+struct IsoLayers {
+  unsigned int events;                      // quad-uniform, like A ... shadow_steps: the events composited
+  float A;                                  // the accumulated opacity
+  float iso, t;                             // the first event's isovalue and t*: the layer
+  unsigned int steps, shadow_steps;         // steps walked; the steps of all shadow walks
+  unsigned int fetched, skipped, shadow_fetched, shadow_skipped; // THIS LANE's
+};
+
+// every crossing of the ray composited front to back until A >= 0.9999f or the ray leaves the box: walk - the events of the hit step, each behind a wave-uniform
+// branch through iso_point - walk again from the hit step.  on_event(index, k, iso, alpha, tr = 1 - A before, A after, point) is called by the lanes of a quad
+// that takes the event: the caller composites its colour there.  Both loops are bounded: a walk that hits has consumed at least one step of the ray, a step
+// holds at most kMaxIsovalues events
+template <int VT, int AM, int SHADE, bool SKIP, bool CLIP, class OnEvent>
+__device__ __forceinline__ IsoLayers isosurface_layers(const RayMarchParams& P, const VolConsts& vc, const MarchConsts& mc, f3 org, f3 dir, float t0, float t1, bool live,
+                                                       const SubMask& subm, OnEvent&& on_event)
+{
+  IsoLayers L;
+  L.events = 0u; L.A = 0.f; L.iso = L.t = 0.f; L.steps = L.shadow_steps = 0u; L.fetched = L.skipped = L.shadow_fetched = L.shadow_skipped = 0u;
+  IsoCarry carry;
+  carry.side = -1; carry.tm = 0.f; carry.ty = t0;
+  float tx = t0;
+  bool go = live;
+  while (__ballot(go) != 0ull) {
+    const IsoWalk w = iso_walk<VT, AM, SKIP, true>(P, vc, mc, org, dir, tx, t1, go, subm, &carry);
+    L.steps += w.steps; L.fetched += w.fetched; L.skipped += w.skipped;
+    int k = 0, dk = 0, n = 0;
+    if (w.hit) iso_step_events(w.side_a, w.side_b, k, dk, n);
+    bool open = w.hit; // the ray takes the step's next event
+#pragma unroll 1
+    for (int e = 0; e < kMaxIsovalues; ++e) {
+      const bool ev = open && e < n;
+      if (__ballot(ev) == 0ull) break; // (wave-uniform: the quad exchanges of iso_point run with every lane)
+      const float iso = iso_value(P, k), alpha = iso_opacity(P, k);
+      IsoPoint pt;
+      pt.t = 0.f; pt.pos = org; pt.n_w = mk3(0, 0, 0); pt.shadow = 0.f; pt.shadow_steps = pt.shadow_fetched = pt.shadow_skipped = 0u;
+      iso_point<VT, AM, SHADE, SKIP, CLIP>(P, vc, mc, org, dir, iso, w.ta, w.tb, ev, subm, pt);
+      L.shadow_fetched += pt.shadow_fetched; L.shadow_skipped += pt.shadow_skipped; // (a quad without the event walked no shadow step)
+      if (ev) {
+        const float tr = 1.f - L.A;
+        const float A = fmaf(tr, alpha, L.A);
+        on_event(L.events, k, iso, alpha, tr, A, pt);
+        if (L.events == 0u) { L.iso = iso; L.t = pt.t; }
+        L.A = A;
+        ++L.events;
+        L.shadow_steps += pt.shadow_steps;
+        open = !(A >= 0.9999f);
+      }
+      k += dk;
+    }
+    go = w.hit && open;
+    tx = carry.ty; carry.side = w.side_b; carry.tm = w.tb;
+  }
+  return L;
+}
 
 // the ray org + t dir (world space) over [t0, t1]; live: the ray is walked (quad-uniform)
 template <int VT, int AM, int SHADE, bool SKIP, bool CLIP>
@@ -2632,6 +2826,14 @@ __device__ __forceinline__ IsoResult isosurface_ray(const RayMarchParams& P, con
   }
   return res;
 }
+// TRANS (an overload: the opaque function above is what it was, text and code): the translucent ray - an IsoLayers, and on_event per composited event
+template <int VT, int AM, int SHADE, bool SKIP, bool CLIP, bool TRANS, class OnEvent>
+__device__ __forceinline__ IsoLayers isosurface_ray(const RayMarchParams& P, const VolConsts& vc, const MarchConsts& mc, f3 org, f3 dir, float t0, float t1, bool live,
+                                                    const SubMask& subm, OnEvent&& on_event)
+{
+  static_assert(TRANS && isosurface_variant_exists(SHADE, AM, SKIP, CLIP, false, TRANS), "no such variant of the isosurface kernel (host/launch_plan.hpp)");
+  return isosurface_layers<VT, AM, SHADE, SKIP, CLIP>(P, vc, mc, org, dir, t0, t1, live, subm, on_event);
+}
 
 // the colour of an isovalue, once per hit, from the table in global memory: project_classify's colour half (the alpha table is not read)
 __device__ __forceinline__ f3 isosurface_colour(const RayMarchParams& P, float v)
@@ -2649,10 +2851,11 @@ __device__ __forceinline__ f3 isosurface_colour(const RayMarchParams& P, float v
 // an isosurface frame: project_kernel's frame around isosurface_ray; the layer is (iso, t*, 1).  The material is a run-time argument (shade_light<true> with
 // the reference's values IS the reference's expression, operation for operation): one instantiation per shading mode, none per material
 // ORTHO: the orthographic camera's rays (pixel_ray) and view vector (shade_light) - on the clipped variants alone
-template <int VT, int AM, int SHADE, bool SKIP, bool CLIP, bool ORTHO = false>
+// TRANS: the translucent frame - every crossing composited, the pixel un-premultiplied like the march's - on the clipped variants alone
+template <int VT, int AM, int SHADE, bool SKIP, bool CLIP, bool ORTHO = false, bool TRANS = false>
 __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams P)
 {
-  static_assert(isosurface_variant_exists(SHADE, AM, SKIP, CLIP, ORTHO) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the isosurface kernel (host/launch_plan.hpp)");
+  static_assert(isosurface_variant_exists(SHADE, AM, SKIP, CLIP, ORTHO, TRANS) && (AM != 4 || RowLoads<VT, 4>::on), "no such variant of the isosurface kernel (host/launch_plan.hpp)");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane & 3;
@@ -2701,21 +2904,47 @@ __global__ __launch_bounds__(kBlock) void isosurface_kernel(const RayMarchParams
     const bool live = active && primary_box_test<CLIP, ORTHO>(P, t0, t1, oo, od);
     if (active && owner) ++n_rays;
     if (live && owner && box_ignored_slab_outside<CLIP>(P, oo, od)) ++n_outside_hits;
-    const IsoResult ir = isosurface_ray<VT, AM, SHADE, SKIP, CLIP>(P, vc, mc, org, dir, t0, t1, live, subm);
-    n_samples += ir.fetched;
-    n_skipped += ir.skipped;
-    n_shadow += ir.shadow_fetched;
-    n_shadow_skipped += ir.shadow_skipped;
-    if (ir.hit && owner) {
-      f3 c = isosurface_colour(P, ir.iso);
-      if (SHADE != 0) {
-        const float shade = shade_factor<true>(P, shade_light<true, ORTHO>(P, mc.light, ir.n_w, ir.pos), ir.shadow);
-        c = mk3(clamp01(c.x * shade), clamp01(c.y * shade), clamp01(c.z * shade));
+    if constexpr (TRANS) {
+      // the colour lookup and the shade factor in front of the composite: C_ch = fma(tr * c_ch, alpha, C_ch), the march's expression
+      f3 cc = mk3(0, 0, 0);
+      auto on_event = [&](unsigned int, int, float iso, float alpha, float tr, float, const IsoPoint& pt) {
+        if (!owner) return;
+        f3 c = isosurface_colour(P, iso);
+        if (SHADE != 0) {
+          const float shade = shade_factor<true>(P, shade_light<true, ORTHO>(P, mc.light, pt.n_w, pt.pos), pt.shadow);
+          c = mk3(clamp01(c.x * shade), clamp01(c.y * shade), clamp01(c.z * shade));
+        }
+        cc.x = fmaf(tr * c.x, alpha, cc.x); cc.y = fmaf(tr * c.y, alpha, cc.y); cc.z = fmaf(tr * c.z, alpha, cc.z);
+      };
+      const IsoLayers il = isosurface_ray<VT, AM, SHADE, SKIP, CLIP, true>(P, vc, mc, org, dir, t0, t1, live, subm, on_event);
+      n_samples += il.fetched;
+      n_skipped += il.skipped;
+      n_shadow += il.shadow_fetched;
+      n_shadow_skipped += il.shadow_skipped;
+      if (il.events > 0u && owner) {
+        n_hits += il.events;
+        o_c.x += cc.x / il.A; o_c.y += cc.y / il.A; o_c.z += cc.z / il.A;
+        o_a += il.A;
+        o_g.x += il.iso; o_g.y += il.t; o_g.z += 1.f;
       }
-      ++n_hits;
-      o_c.x += c.x; o_c.y += c.y; o_c.z += c.z;
-      o_a += 1.f;
-      o_g.x += ir.iso; o_g.y += ir.t; o_g.z += 1.f;
+    }
+    else {
+      const IsoResult ir = isosurface_ray<VT, AM, SHADE, SKIP, CLIP>(P, vc, mc, org, dir, t0, t1, live, subm);
+      n_samples += ir.fetched;
+      n_skipped += ir.skipped;
+      n_shadow += ir.shadow_fetched;
+      n_shadow_skipped += ir.shadow_skipped;
+      if (ir.hit && owner) {
+        f3 c = isosurface_colour(P, ir.iso);
+        if (SHADE != 0) {
+          const float shade = shade_factor<true>(P, shade_light<true, ORTHO>(P, mc.light, ir.n_w, ir.pos), ir.shadow);
+          c = mk3(clamp01(c.x * shade), clamp01(c.y * shade), clamp01(c.z * shade));
+        }
+        ++n_hits;
+        o_c.x += c.x; o_c.y += c.y; o_c.z += c.z;
+        o_a += 1.f;
+        o_g.x += ir.iso; o_g.y += ir.t; o_g.z += 1.f;
+      }
     }
   }
   if (active && owner) {
@@ -2757,6 +2986,37 @@ __global__ __launch_bounds__(kBlock) void isosurface_floats_kernel(const RayMarc
   }
 }
 
+// its translucent twin (ovr_hip_isosurface_layers_floats): ray i through isosurface_ray<TRANS> as the translucent frame's kernel calls it with full shading ->
+// 4 + 8 max_events floats: (events composited, A, steps walked, shadow steps over all events), then per event e < min(events, max_events)
+// (k, t*, n_w.x, n_w.y, n_w.z, shadow, A after the event, 0).  The host zeroes `out` first: the rest stays zero
+template <int VT, int AM, bool SKIP>
+__global__ __launch_bounds__(kBlock) void isosurface_layers_floats_kernel(const RayMarchParams P, const float* org, const float* dir, float* out, long long n, int max_events)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int sub = threadIdx.x & 3;
+  const SubMask subm = make_submask(sub);
+  VolConsts vc;
+  MarchConsts mc;
+  setup_consts(P, vc, mc);
+  stage_tables<VT, AM>(P, lds_raw, vc);
+  __syncthreads();
+  const long long i = ((long long)blockIdx.x * kBlock + threadIdx.x) >> 2;
+  const bool valid = i < n;
+  const long long j = valid ? i : 0;
+  const f3 o = mk3(org[3 * j], org[3 * j + 1], org[3 * j + 2]), d = mk3(dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
+  const f3 oo = to_object(mc, o), od = mk3(d.x * mc.inv_scale.x, d.y * mc.inv_scale.y, d.z * mc.inv_scale.z);
+  float t0 = 0.f, t1 = FLT_MAX;
+  const bool live = valid && box_test<true>(P, t0, t1, oo, od);
+  float* q = out + (4 + 8 * (long long)max_events) * j;
+  auto on_event = [&](unsigned int e, int k, float, float, float, float A, const IsoPoint& pt) {
+    if (sub != 0 || e >= (unsigned int)max_events) return; // (called by live quads alone: valid holds)
+    float* p = q + 4 + 8 * e;
+    p[0] = (float)k; p[1] = pt.t; p[2] = pt.n_w.x; p[3] = pt.n_w.y; p[4] = pt.n_w.z; p[5] = pt.shadow; p[6] = A; p[7] = 0.f;
+  };
+  const IsoLayers il = isosurface_ray<VT, AM, 2, SKIP, true, true>(P, vc, mc, o, d, t0, t1, live, subm, on_event);
+  if (valid && sub == 0) { q[0] = (float)il.events; q[1] = il.A; q[2] = live ? (float)il.steps : 0.f; q[3] = (float)il.shadow_steps; }
+}
+
 typedef void (*IsosurfaceFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
 struct IsosurfaceKernels { FrameKernel frame = nullptr; IsosurfaceFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
 template <int VT, int AM, int SHADE>
@@ -2795,6 +3055,47 @@ IsosurfaceKernels isosurface_kernels_of(int am, int shade, bool skip, bool clipp
     }
   }
   return IsosurfaceKernels();
+}
+
+// the translucent kernels of a voxel type: a lookup and an object of their own beside the type's isosurface object (ovr_hip_isosurface.hip
+// compiled with -DOVR_ISO_LAYERS), so that the opaque kernels' object is compiled from what it was compiled from.  On the clipped box test alone
+// (isosurface_variant_exists): there is no `clipped` to ask for
+typedef void (*IsosurfaceLayersFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long, int);
+struct IsosurfaceLayersKernels { FrameKernel frame = nullptr; IsosurfaceLayersFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
+template <int VT, int AM, int SHADE>
+inline FrameKernel isosurface_layers_frame_kernel(bool skip, bool ortho)
+{
+  if (ortho) return skip ? isosurface_kernel<VT, AM, SHADE, true, true, true, true> : isosurface_kernel<VT, AM, SHADE, false, true, true, true>;
+  return skip ? isosurface_kernel<VT, AM, SHADE, true, true, false, true> : isosurface_kernel<VT, AM, SHADE, false, true, false, true>;
+}
+template <int VT, int AM>
+inline IsosurfaceLayersKernels isosurface_layers_kernels_of(int shade, bool skip, bool ortho)
+{
+  IsosurfaceLayersKernels k;
+  switch (shade) {
+  case 0: k.frame = isosurface_layers_frame_kernel<VT, AM, 0>(skip, ortho); break;
+  case 1: k.frame = isosurface_layers_frame_kernel<VT, AM, 1>(skip, ortho); break;
+  case 2: k.frame = isosurface_layers_frame_kernel<VT, AM, 2>(skip, ortho); break;
+  default: return k;
+  }
+  k.floats = skip ? isosurface_layers_floats_kernel<VT, AM, true> : isosurface_layers_floats_kernel<VT, AM, false>;
+  return k;
+}
+template <int VT>
+IsosurfaceLayersKernels isosurface_layers_kernels_of(int am, int shade, bool skip, bool ortho)
+{
+  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
+    switch (am) {
+    case 0: return isosurface_layers_kernels_of<VT, 0>(shade, skip, ortho);
+    case 1: return isosurface_layers_kernels_of<VT, 1>(shade, skip, ortho);
+    case 2: return isosurface_layers_kernels_of<VT, 2>(shade, skip, ortho);
+    case 3: return isosurface_layers_kernels_of<VT, 3>(shade, skip, ortho);
+    case 4:
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return isosurface_layers_kernels_of<VT, 4>(shade, skip, ortho);
+      else return IsosurfaceLayersKernels();
+    }
+  }
+  return IsosurfaceLayersKernels();
 }
 
 // one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~160 kernel

@@ -1,5 +1,7 @@
 // ovr_hip_isosurface.hip - the isosurface kernels of one voxel type of the general layout (explicit instantiation; see ovr_hip_device.h).  Compiled once per such
 // type with -DOVR_MARCH_VT=<its enumerator>, each into an object of its own beside the type's march object (Makefile): the march objects are what they were
+// With -DOVR_ISO_LAYERS the unit instantiates the type's TRANSLUCENT kernels instead, into a second object per type: the opaque kernels'
+// object is compiled from what it was compiled from, and the two compile in parallel
 #include "ovr_hip_device.h"
 
 #ifndef OVR_MARCH_VT
@@ -8,5 +10,9 @@
 
 namespace ovrhip {
 static_assert(kVoxelTypes[OVR_MARCH_VT].layout == LAYOUT_GENERAL, "the isosurface kernels read the general layout");
+#ifdef OVR_ISO_LAYERS
+template IsosurfaceLayersKernels isosurface_layers_kernels_of<OVR_MARCH_VT>(int, int, bool, bool);
+#else
 template IsosurfaceKernels isosurface_kernels_of<OVR_MARCH_VT>(int, int, bool, bool, bool);
+#endif
 }

@@ -268,6 +268,10 @@ struct RayMarchParams {
   // the camera's kind (ovr_hip_set_camera_orthographic; open-volume-renderer_amd/camera.py is the arithmetic): 1 = cam_pos ... cam_ver are the orthographic
   // camera's and the host launches the orthographic twins of the clipped kernels (the kernels do not read it).  Behind everything else, like the isovalues
   int cam_orthographic;
+  // the isovalues' opacities (ovr_hip_set_isosurface_layers), in (0, 1], travelling with iso_values; iso_translucent: one of the committed
+  // ones is below 1 and the host launches the translucent twins, the only kernels that read the opacities.  Behind everything else, like the camera's kind
+  float iso_opacities[4];
+  int iso_translucent;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -323,6 +327,10 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
 // each: hit, isovalue, t*, steps walked, the world normal, the shadow term (zeros for a ray without a hit, but the steps walked), four lanes per ray.  p.iso_n /
 // p.iso_values: the isovalues; p.mc_ranges: the ranges if range_skipping (hipErrorInvalidValue without them, without isovalues or for a replica's type)
 hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream);
+// its translucent twin (isosurface_ray<TRANS>, the function the translucent frame's kernel calls): 4 + 8 max_events floats per ray - (events composited, A, steps
+// walked, shadow steps), then (k, t*, the world normal, shadow, A after the event, 0) per event, the rest zeros - with p.iso_opacities, whatever p.iso_translucent says
+hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int range_skipping,
+                                           hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

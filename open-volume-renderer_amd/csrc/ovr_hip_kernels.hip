@@ -1014,6 +1014,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.shadow_cache = p.shadow_lattice != nullptr;
   f.projection = p.projection; f.ranges = p.mc_ranges != nullptr;
   f.isosurfaces = p.iso_n;
+  f.translucent = p.iso_n > 0 && p.iso_translucent != 0;
   f.orthographic = p.cam_orthographic != 0;
   return plan_launch(f, o);
 }
@@ -1094,6 +1095,17 @@ static IsosurfaceKernels isosurface_kernels(const RayMarchParams& p, const Launc
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.isosurface.clipped, plan.orthographic); });
   return k;
 }
+// (the translucent twins: an object of their own per such type, from the same unit - DESIGN.md section 19)
+#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceLayersKernels isosurface_layers_kernels_of<E>(int, int, bool, bool);
+OVR_VOXEL_TYPES(OVR_X)
+#undef OVR_X
+static IsosurfaceLayersKernels isosurface_layers_kernels(const RayMarchParams& p, const LaunchPlan& plan)
+{
+  IsosurfaceLayersKernels k;
+  if (!plan.error && plan.isosurface.on && plan.isosurface.translucent && plan.isosurface.clipped)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_layers_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.orthographic); });
+  return k;
+}
 
 hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipStream_t stream, const hipEvent_t* ev)
 {
@@ -1102,7 +1114,7 @@ hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipS
   FrameKernels k;
   // a projection frame: project_kernel in the in-place march's place (its plan is neither pooled nor LDS-staged, march_lds_bytes is the projection's), then
   // the same reduction and publish steps
-  if (plan.isosurface.on) k.march = isosurface_kernels(p, plan).frame; // an isosurface frame: the same place, the same steps behind it
+  if (plan.isosurface.on) k.march = plan.isosurface.translucent ? isosurface_layers_kernels(p, plan).frame : isosurface_kernels(p, plan).frame; // an isosurface frame: the same place, the same steps behind it
   else if (plan.project.mode != 0) k.march = project_kernels(p, plan).frame;
   else dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
   const hipError_t e = k.march && (k.shade || !plan.pooled) ? launch_sequence(p, plan, k, stream, ev) : hipErrorInvalidValue;
@@ -2124,6 +2136,7 @@ hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, c
   RayMarchParams q = p;
   q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
   if (!range_skipping) q.mc_ranges = nullptr;
+  q.iso_translucent = 0; // (the first crossing, opaque, whatever opacities are committed)
   const LaunchPlan pl = plan_raymarch(q);
   const IsosurfaceFloatsKernel kern = isosurface_kernels(q, pl).floats;
   if (!kern) return hipErrorInvalidValue;
@@ -2132,6 +2145,29 @@ hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, c
   if (pl.isosurface.lds_bytes > 64 * 1024)
     if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.isosurface.lds_bytes)) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.isosurface.lds_bytes, stream, q, org, dir, out, (long long)n);
+  return hipGetLastError();
+}
+
+// known-answer entry of the translucent isosurfaces: the twin of the kernel above, at the addressing mode a translucent frame takes.  out is zeroed first: the
+// kernel writes a ray's header and the events it composited
+hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int range_skipping,
+                                           hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16) return hipErrorInvalidValue;
+  RayMarchParams q = p;
+  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  if (!range_skipping) q.mc_ranges = nullptr;
+  q.iso_translucent = 1;
+  const LaunchPlan pl = plan_raymarch(q);
+  const IsosurfaceLayersFloatsKernel kern = isosurface_layers_kernels(q, pl).floats;
+  if (!kern) return hipErrorInvalidValue;
+  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(4 + 8 * max_events) * sizeof(float), stream)) return e;
+  if (pl.isosurface.lds_bytes > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.isosurface.lds_bytes)) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.isosurface.lds_bytes, stream, q, org, dir, out, (long long)n, max_events);
   return hipGetLastError();
 }
 

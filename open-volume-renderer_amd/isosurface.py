@@ -28,6 +28,17 @@ Skipping   (primary and shadow walks, while range skipping is on) with [lo, hi] 
 Counters   samples / skipped_samples = the walked steps whose fetch the WALK made / dropped (their sum: the steps walked); shaded_samples = hits; shadow_samples /
            skipped_shadow_samples = the same of the shadow walks.  Refinement, end-point and gradient taps are not counted.
 
+Translucent (ovr_hip_set_isosurface_layers with an opacity below 1): each isovalue has an opacity alpha_k in (0, 1].
+Events     every step i >= 1 with side(s_{i-1}) != side(s_i) holds one event per isovalue crossed, in the order the ray meets them: rising from side a to b > a
+           k = a ... b - 1, falling to b < a k = a - 1 ... b.  The opaque hit is the first event of the first such step.  Each event is refined from the step's own
+           pair with iso = iso_k (in(sa) != in(sb) holds for every crossed k), and shaded and shadowed as the hit is; c_k = its colour (clamp01(rgb * shade)).
+Composite  the march's recurrence (oracle/ovr_oracle.c:608-615) from A = 0, C = 0: tr = 1 - A, C_ch = fma(tr * c_ch, alpha_k, C_ch), A = fma(tr, alpha_k, A).  The
+           first event sets the layer.  A >= 0.9999f behind an event ends the ray there (later events of the step are not taken; steps walked = i + 1), else the
+           walk goes on with step i + 1 whose predecessor is step i.  Sample: rgb = C / A per channel, a = A; zeros without an event.
+Shadow     today's shadow ray and steps; A_s = fma(1 - A_s, alpha_k, A_s) over its events until A_s >= 0.9999f; shadow = A_s.
+Counters   steps walked count once however many events they hold; shaded_samples = events composited; the shadow counters sum the shadow walks of all events.
+With every alpha_k = 1 the first event gives C = c, A = 1 and the shadow 1.0f: the opaque text above, bit for bit.
+
 The 8-bit voxel types: the product filters the stored integers and normalises once behind the filter (s = filter(raw) * (1 / 255)), the exact-parity build and
 projection.sample normalise voxel by voxel.  `product_sampler` restates the former, so that hit, isovalue, t* and the steps walked of the product are this model's
 bits too."""
@@ -42,6 +53,7 @@ F = np.float32
 MAX_ISOVALUES = 4
 NONE, GRADIENT, FULL = 0, 1, 2
 C = (F(0.2), F(0.4), F(0.6), F(0.8))
+SATURATED = F(0.9999)   # the march's early-termination bound (oracle/ovr_oracle.c:608-615): a translucent ray ends behind the event that reaches it
 
 
 def isovalues(values):
@@ -80,9 +92,49 @@ def skipped_side(lo, hi, iso):
     return ~(below | above).all(-1), below.sum(-1)
 
 
-def walk(s, count, iso, ranges=None):
+def opacities_of(opacities, iso_as_given):
+    """the opacities as the setter stores them: float32, travelling with their isovalues into ascending order; ValueError for what it refuses"""
+    v = np.asarray(iso_as_given, F).ravel()
+    a = np.asarray(opacities, F).ravel()
+    if a.size != v.size or not np.isfinite(a).all() or (a <= 0).any() or (a > 1).any():
+        raise ValueError("one opacity in (0, 1] per isovalue")
+    return a[np.argsort(v, kind="stable")]
+
+
+def events_of_step(before, at):
+    """the isovalues a step crosses, in the order the ray meets them: rising from side a to b > a: a ... b - 1; falling to b < a: a - 1 ... b"""
+    return range(before, at) if at > before else range(before - 1, at - 1, -1)
+
+
+def walk_events(sd, fetch, count, alpha):
+    """the translucent walk over the sides sd (n, width) of the steps: every crossing composited front to back until A >= 0.9999f or the ray's last step.
+    -> dict(hit, i, k - the first event's -, walked, fetched, events: per ray a list of (step, k, A after the event))"""
+    n, width = sd.shape
+    one = F(1)
+    hit, first_i, first_k, walked, events = np.zeros(n, bool), np.zeros(n, np.int64), np.zeros(n, np.int64), np.asarray(count, np.int64).copy(), []
+    for r in range(n):
+        ev, A, done = [], F(0), False
+        row, c = sd[r], int(count[r])
+        for i in (np.flatnonzero(row[1:c] != row[:c - 1]) + 1 if c > 1 else ()):
+            for k in events_of_step(int(row[i - 1]), int(row[i])):
+                A = F(fma(F(one - A), alpha[k], A))
+                ev.append((int(i), int(k), A))
+                if A >= SATURATED:
+                    done = True
+                    break
+            if done:
+                walked[r] = i + 1
+                break
+        if ev:
+            hit[r], first_i[r], first_k[r] = True, ev[0][0], ev[0][1]
+        events.append(ev)
+    fetched = (fetch & (np.arange(width)[None, :] < walked[:, None])).sum(1)
+    return dict(hit=hit, i=first_i, k=first_k, walked=walked, fetched=fetched, events=events)
+
+
+def walk(s, count, iso, ranges=None, opacities=None):
     """s (n, width) samples, count (n,) -> dict(hit, i - the hit's step -, k - k* -, walked, fetched): the first crossing.  ranges = (lo, hi), each (n, width): the
-    skipping walk, which never looks at a dropped step's sample"""
+    skipping walk, which never looks at a dropped step's sample.  opacities (one per isovalue, ascending with them): the translucent walk (walk_events)"""
     s = np.asarray(s, F)
     n, width = s.shape
     count = np.asarray(count, np.int64)
@@ -91,6 +143,8 @@ def walk(s, count, iso, ranges=None):
     if ranges is not None:
         fetch, below = skipped_side(ranges[0], ranges[1], iso)
         sd = np.where(fetch, sd, below)
+    if opacities is not None:
+        return walk_events(sd, fetch, count, np.asarray(opacities, F))
     idx = np.arange(width)[None, :]
     cross = np.zeros((n, width), bool)
     if width > 1:
@@ -143,14 +197,18 @@ def normals(tap_object, po, s, dims, inv_scale, vertex_centred=False):
 
 
 def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, shadows=True, light=None,
-               sampler=None, camera_kind=0):
+               sampler=None, camera_kind=0, opacities=None):
     """world rays org, direction (n, 3) - the direction used as given - -> what ovr_hip_isosurface_floats returns per ray, and the counters' parts:
     dict(hit, iso, t, steps, normal (n, 3), shadow, fetched, pos (n, 3), shadow_steps, shadow_fetched, tm_before, tm_at, k); zeros for a ray without a hit.
     light: the raw vector towards the light (normalised here as the host does); sampler(po) replaces projection.sample (product_sampler);
-    camera_kind = camera.ORTHOGRAPHIC: the rays are that camera's primary rays (camera.hits: a ray outside an ignored slab misses; shadow rays are untouched)"""
+    camera_kind = camera.ORTHOGRAPHIC: the rays are that camera's primary rays (camera.hits: a ray outside an ignored slab misses; shadow rays are untouched).
+    opacities (one per isovalue as given): the translucent walk - the keys above describe the ray's FIRST event (steps, fetched: the whole walk; shadow_steps,
+    shadow_fetched: the shadow walks of all events), and A (n,), n_events (n,), events (per ray a list of dict(i - the step -, k, t, normal, shadow, A - after the
+    event)) and flat (the events of all rays in order: ray, i, k, iso, alpha, t, pos, normal, shadow, A, tm_before, tm_at) are added"""
     vol = np.asarray(volume)
     nz, ny, nx = vol.shape
     dims = (nx, ny, nz)
+    alpha = None if opacities is None else opacities_of(opacities, iso)
     iso = isovalues(iso)
     org, direction = np.asarray(org, F).reshape(-1, 3), np.asarray(direction, F).reshape(-1, 3)
     inv, wp = clipping.volume_constants(dims, spacing, origin, vertex_centred)
@@ -169,7 +227,7 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
             c = tap_cell(tap_coordinates(po, dims, vertex_centred)[0], dims)
             r = rng[c[:, 2], c[:, 1], c[:, 0]].reshape(n, width, 2)
             ranges = (r[..., 0], r[..., 1])
-        return s, walk(s, count, iso, ranges)
+        return s, walk(s, count, iso, ranges, alpha)
 
     if camera_kind:
         from . import camera
@@ -181,6 +239,8 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
     if tm.shape[1] == 0:
         tm = np.zeros((n, 1), F)
     s, w = first_crossing(org, direction, tm, count)
+    if alpha is not None:
+        return _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light)
     hit, r = w["hit"], np.arange(n)
     i = w["i"]
     ta, tb, sa, sb = tm[r, np.maximum(i - 1, 0)], tm[r, i], s[r, np.maximum(i - 1, 0)], s[r, i]
@@ -217,9 +277,77 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
     return out
 
 
+def _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light):
+    """trace_rays behind the translucent walk w: every event refined, shaded and shadowed as the opaque hit is"""
+    n = len(org)
+    ev = [(r, i, k, A) for r, row in enumerate(w["events"]) for (i, k, A) in row]
+    er, ei, ek = (np.array([e[j] for e in ev], np.int64) for j in range(3))
+    eA = np.array([e[3] for e in ev], F)
+    m = len(ev)
+    n_events = np.array([len(row) for row in w["events"]], np.int64)
+    flat = dict(ray=er, i=ei, k=ek, iso=iso[ek] if m else np.zeros(0, F), alpha=alpha[ek] if m else np.zeros(0, F), t=np.zeros(m, F), pos=np.zeros((m, 3), F),
+                normal=np.zeros((m, 3), F), shadow=np.zeros(m, F), A=eA, tm_before=tm[er, ei - 1] if m else np.zeros(0, F), tm_at=tm[er, ei] if m else np.zeros(0, F))
+    shadow_steps, shadow_fetched = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    if m:
+        oh, dh = org[er], direction[er]
+
+        def tap_ray(t):
+            with np.errstate(invalid="ignore", over="ignore"):
+                return tap_object(clipping.to_object(fma(t[:, None], dh, oh), inv, wp))
+
+        t, _, _ = refine(tap_ray, flat["iso"], tm[er, ei - 1], s[er, ei - 1], tm[er, ei], s[er, ei])
+        with np.errstate(invalid="ignore", over="ignore"):
+            pos = fma(t[:, None], dh, oh)
+        po = clipping.to_object(pos, inv, wp)
+        flat["t"], flat["pos"] = t, pos
+        flat["normal"] = normals(tap_object, po, tap_object(po), dims, inv, vertex_centred)
+        if shadows:
+            L = lighting.normalize(np.asarray(lighting.LITERAL_LIGHT if light is None else light, F))
+            Ld = np.broadcast_to(L, pos.shape)
+            s0, s1, sbox = clipping.world_intervals(pos, Ld, inv, wp, lo, hi)
+            stm, scount = steps((s0 + step).astype(F), s1, step, sbox)
+            if stm.shape[1] == 0:
+                stm = np.zeros((m, 1), F)
+            _, sw = first_crossing(pos, Ld, stm, scount)
+            flat["shadow"] = np.array([row[-1][2] if row else F(0) for row in sw["events"]], F)
+            shadow_steps, shadow_fetched = np.where(sbox, sw["walked"], 0), np.where(sbox, sw["fetched"], 0)
+    first = np.concatenate([[0], np.cumsum(n_events)[:-1]]).astype(np.int64)   # a ray's first event in the flat order
+    hit = n_events > 0
+    f = first[hit]
+    out = dict(hit=hit, k=w["k"], iso=np.zeros(n, F), steps=np.where(box, w["walked"], 0), fetched=np.where(box, w["fetched"], 0), t=np.zeros(n, F),
+               normal=np.zeros((n, 3), F), shadow=np.zeros(n, F), pos=np.zeros((n, 3), F), shadow_steps=np.zeros(n, np.int64), shadow_fetched=np.zeros(n, np.int64),
+               tm_before=np.zeros(n, F), tm_at=np.zeros(n, F), A=np.zeros(n, F), n_events=n_events, flat=flat)
+    for key in ("iso", "t", "normal", "shadow", "pos"):
+        out[key][hit] = flat[key][f]
+    out["tm_before"][hit], out["tm_at"][hit] = tm[er[f], ei[f] - 1], tm[er[f], ei[f]]
+    np.add.at(out["shadow_steps"], er, shadow_steps)
+    np.add.at(out["shadow_fetched"], er, shadow_fetched)
+    last = first + n_events - 1
+    out["A"][hit] = eA[last[hit]]
+    out["events"] = [[dict(i=int(ei[j]), k=int(ek[j]), t=flat["t"][j], normal=flat["normal"][j], shadow=flat["shadow"][j], A=eA[j]) for j in range(first[r], first[r] + n_events[r])]
+                     for r in range(n)]
+    return out
+
+
+def composite(flat, rgb, n):
+    """the events' colours rgb (m, 3) composited per ray front to back by the march's recurrence -> C (n, 3) premultiplied, A (n,)"""
+    Cc, A = np.zeros((n, 3), F), np.zeros(n, F)
+    ray, alpha = flat["ray"], flat["alpha"]
+    if len(ray) == 0:
+        return Cc, A
+    ordinal = np.arange(len(ray)) - np.searchsorted(ray, ray, side="left")   # (the flat order is by ray, then along the ray)
+    for e in range(int(ordinal.max()) + 1):
+        j = np.flatnonzero(ordinal == e)
+        r = ray[j]
+        tr = (F(1) - A[r]).astype(F)
+        Cc[r] = fma((tr[:, None] * rgb[j]).astype(F), alpha[j][:, None], Cc[r])
+        A[r] = fma(tr, alpha[j], A[r])
+    return Cc, A
+
+
 def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=None, intensity=1.0, material=lighting.REFERENCE_MATERIAL, spacing=(1, 1, 1),
-          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None, camera_kind=0):
-    """one isosurface frame: rgba (H, W, 4), layer (H, W, 3) and counters.  basis = (pos, dir, hor, ver); tf_range in the samples' units
+          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None, camera_kind=0, opacities=None):
+    """one isosurface frame: rgba (H, W, 4), layer (H, W, 3) and counters (opacities: the translucent frame - `hits` counts the events composited).  basis = (pos, dir, hor, ver); tf_range in the samples' units
     (projection.normalized_range); noise = the blue-noise tile switches that jitter on - without it spp must be 1, as in projection.frame;
     camera_kind = camera.ORTHOGRAPHIC: the basis is an orthographic camera's - rays from camera.pixel_rays, the view vector -dir (the default: today's frame)"""
     w, h = size
@@ -239,20 +367,26 @@ def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=
             from . import camera
             org, d = (a.reshape(-1, 3) for a in camera.pixel_rays(basis, w, h, xi, camera_kind))
             view = camera.view_vector(basis) if camera_kind == camera.ORTHOGRAPHIC else None
-        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler, camera_kind)
+        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler, camera_kind, opacities)
         m = r["hit"]
-        rgb = classify(r["iso"], colors, np.zeros(2, F), *tf_range)[:, :3]
+        e = r if opacities is None else r["flat"]   # what is coloured and shaded: the hit, or every event
+        rgb = classify(e["iso"], colors, np.zeros(2, F), *tf_range)[:, :3]
         if shading != NONE:
-            f = lighting.shade(r["normal"], r["pos"], r["shadow"], L, basis[0], ka, kd, ks, shin, intensity, view=view)
+            f = lighting.shade(e["normal"], e["pos"], e["shadow"], L, basis[0], ka, kd, ks, shin, intensity, view=view)
             with np.errstate(invalid="ignore", over="ignore"):
                 rgb = clamp01((rgb * f[:, None]).astype(F))
-        c = np.concatenate([rgb, np.ones((h * w, 1), F)], 1)
+        if opacities is None:
+            c = np.concatenate([rgb, np.ones((h * w, 1), F)], 1)
+        else:   # un-premultiplied, like the march's pixel
+            Cc, A = composite(e, rgb, h * w)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                c = np.concatenate([(Cc / A[:, None]).astype(F), A[:, None]], 1)
         rgba = (rgba + np.where(m[:, None], c, F(0))).astype(F)
         layer = (layer + np.where(m[:, None], np.stack([r["iso"], r["t"], np.ones(h * w, F)], 1), F(0))).astype(F)
         counters["rays"] += h * w
         counters["steps"] += int(r["steps"].sum())
         counters["fetched"] += int(r["fetched"].sum())
-        counters["hits"] += int(m.sum())
+        counters["hits"] += int(m.sum()) if opacities is None else len(e["ray"])
         counters["shadow_steps"] += int(r["shadow_steps"].sum())
         counters["shadow_fetched"] += int(r["shadow_fetched"].sum())
     rspp = F(1) / F(spp)

@@ -381,10 +381,43 @@ class DeviceHIP:
 
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
-    def set_isosurfaces(self, values=()):
-        """up to four finite, distinct isovalues in the samples' units (8-bit types normalised); none: off, the default"""
+    def set_isosurfaces(self, values=(), opacities=None):
+        """up to four finite, distinct isovalues in the samples' units (8-bit types normalised); none: off, the default.  opacities (one per isovalue, in (0, 1],
+        ovr_hip_set_isosurface_layers): with one below 1 the level sets are translucent - every crossing of a ray composited front to back; None: opaque"""
         v = np.ascontiguousarray(values, dtype=np.float32).ravel()
-        L.check(self._lib.ovr_hip_set_isosurfaces(self._h, v.ctypes.data_as(C.POINTER(C.c_float)) if v.size else None, int(v.size)))
+        pv = v.ctypes.data_as(C.POINTER(C.c_float)) if v.size else None
+        if opacities is None:
+            L.check(self._lib.ovr_hip_set_isosurfaces(self._h, pv, int(v.size)))
+            return
+        a = np.ascontiguousarray(opacities, dtype=np.float32).ravel()
+        if a.size != v.size:
+            raise RuntimeError("set_isosurfaces: one opacity per isovalue")
+        L.check(self._lib.ovr_hip_set_isosurface_layers(self._h, pv, a.ctypes.data_as(C.POINTER(C.c_float)) if a.size else None, int(v.size)))
+
+    def get_isosurface_layers(self):
+        """ovr_hip_isosurface_layers, the COMMITTED state: n, isovalues (ascending), opacities, translucent (1: a committed opacity is below 1), range_skipping"""
+        c = L.IsosurfaceLayers()
+        L.check(self._lib.ovr_hip_get_isosurface_layers(self._h, C.byref(c)))
+        return c
+
+    def isosurface_layer_rays(self, org, direction, max_events=8, range_skipping=False):
+        """translucent isosurface rays as the kernels evaluate them (ovr_hip_isosurface_layers_floats; known-answer tests): world rays (n, 3), (n, 3) ->
+        dict(events (n,) int64 - composited -, A (n,) float32, steps, shadow_steps (n,) int64, and per event slot e < max_events k (n, e) int64, t, shadow,
+        A_after (n, e) float32, normal (n, e, 3); zeros behind a ray's events) with the committed isovalues, opacities, volume, sampling rate, light and clip box"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("isosurface_layer_rays: org and direction hold three floats per ray")
+        m = int(max_events)
+        out = torch.empty((n, 4 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_isosurface_layers_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m, int(bool(range_skipping))))
+        o = out.cpu().numpy()
+        e = o[:, 4:].reshape(n, m, 8)
+        return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), k=e[:, :, 0].astype(np.int64),
+                    t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy())
 
     def get_isosurfaces(self):
         """ovr_hip_isosurfaces, the COMMITTED state: n, isovalues (ascending), range_skipping (1: the last isosurface frame ran the range-skipping kernel)"""

@@ -194,10 +194,20 @@ public:
         float v[OVR_HIP_MAX_ISOVALUES + 1];
         const int n = ovrhip_plugin::parse_isovalues(iv, v, OVR_HIP_MAX_ISOVALUES); // (the whole string: trailing text is an error, not a shorter list)
         if (n < 1) throw std::runtime_error("[hip] OVR_HIP_ISOVALUES expects one to four isovalues separated by commas");
-        check(ovr_hip_set_isosurfaces(h, v, n));
+        // OVR_HIP_ISO_OPACITIES=0.3,1 beside it (ovr_hip_set_isosurface_layers): one opacity in (0, 1] per isovalue, in the isovalues' order - translucent level
+        // sets, every crossing composited.  Unset: the opaque call, nothing changes
+        float a[OVR_HIP_MAX_ISOVALUES + 1];
+        const char* ov = std::getenv("OVR_HIP_ISO_OPACITIES");
+        if (ov && ovrhip_plugin::parse_iso_opacities(ov, a, n) != n)
+          throw std::runtime_error("[hip] OVR_HIP_ISO_OPACITIES expects one opacity in (0, 1] per isovalue of OVR_HIP_ISOVALUES, separated by commas");
+        check(ov ? ovr_hip_set_isosurface_layers(h, v, a, n) : ovr_hip_set_isosurfaces(h, v, n));
         if (!quiet) {
           std::fprintf(stderr, "[hip] isosurfaces at");
           for (int k = 0; k < n; ++k) std::fprintf(stderr, "%s %g", k ? "," : "", (double)v[k]);
+          if (ov) {
+            std::fprintf(stderr, " with opacities");
+            for (int k = 0; k < n; ++k) std::fprintf(stderr, "%s %g", k ? "," : "", (double)a[k]);
+          }
           std::fprintf(stderr, "\n");
         }
       }

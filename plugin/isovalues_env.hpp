@@ -22,4 +22,15 @@ inline int parse_isovalues(const char* text, float* v, int max)
   return n;
 }
 
+// OVR_HIP_ISO_OPACITIES beside OVR_HIP_ISOVALUES: "0.3,1" -> one opacity in (0, 1] per isovalue, parsed like the isovalues (the whole string).  `count`: the number
+// of isovalues.  Returns count, or -1 for anything else: a list parse_isovalues refuses, another count than the isovalues', a value outside (0, 1] (a NaN included)
+inline int parse_iso_opacities(const char* text, float* a, int count)
+{
+  const int n = parse_isovalues(text, a, count);
+  if (n != count) return -1;
+  for (int k = 0; k < n; ++k)
+    if (!(a[k] > 0.f && a[k] <= 1.f)) return -1;
+  return n;
+}
+
 } // namespace ovrhip_plugin

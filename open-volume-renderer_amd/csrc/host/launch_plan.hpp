@@ -154,6 +154,7 @@ struct LaunchPlan {
   bool orthographic = false;          // every kernel of the frame that forms a primary ray or a view vector is the orthographic twin (of the clipped variant)
   bool cached = false;                // the kernels that shade take the shadow term from the lattice: SHADE 1, material, no box test while shading
   // a projection frame (LaunchFacts::projection != 0): project_kernel in the march's place, nothing else of the plan but `am` is read
+  // (lds_bytes, here and below: march_lds_bytes on such a frame and 0 on any other - the launches read march_lds_bytes, the plan tests pin both)
   struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
   // an isosurface frame (LaunchFacts::isosurfaces > 0): isosurface_kernel in the march's place, nothing else of the plan but `am` and `shading` is read
   struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; bool translucent = false; } isosurface;
@@ -174,49 +175,57 @@ inline bool deep_rounds_pay(const LaunchFacts& f, const LaunchOverrides& o)
   return f.world > 1 && f.n_blocks_owned <= kDeepMaxBlocks;
 }
 
-// a projection frame: the general layout's addressing (the same rule, override and row loads as the march), one kernel, in place.  The transfer function is
-// read from global memory, once per ray: LDS holds the axis tables alone (and the counter reduction's words)
+// the addressing step of every plan: the layout's mode, a more general one on request (OVR_HIP_ADDRESSING), then the row loads on mode 0 - mode 4: layouts the
+// caches do not serve (by size), or forced either way.  error: the mode's tables or the dense frame's block list are missing
+struct Addressing { int am; bool error; };
+inline Addressing plan_addressing(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
+  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
+  const bool error = (am < 3 && !f.tables) || (!f.sparse && f.n_schedule > 0 && !f.schedule);
+  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
+  return { am, error };
+}
+
+// what a projection and an isosurface frame share - the frames of the walk: one kernel of the general layout, in place, in the in-place march's place in the
+// launch sequence (march_lds_bytes is its LDS).  The transfer function is read from global memory, once per ray: LDS holds the axis tables alone (and the counter
+// reduction's words).  clipped: a clip box, or a twin that exists on the clipped variants alone - a frame without a clip box runs those with the unit box
+struct WalkFrame { bool clipped; size_t lds_bytes; };
+inline WalkFrame plan_walk_frame(LaunchPlan& pl, const LaunchFacts& f, int am, bool translucent = false)
+{
+  pl.am = am;
+  pl.orthographic = f.orthographic;
+  pl.march_lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
+  return { f.clip_on || f.orthographic || translucent, pl.march_lds_bytes };
+}
+
+// a projection frame: the skipping twin where the ranges are bound and the mode is an extremum
 inline LaunchPlan plan_projection(const LaunchFacts& f, const LaunchOverrides& o)
 {
   LaunchPlan pl;
-  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
-  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
-  if (f.projection < kProjectMaximum || f.projection > kProjectMean || f.quad || (am < 3 && !f.tables) || (!f.sparse && f.n_schedule > 0 && !f.schedule)) {
-    pl.error = true;
-    return pl;
-  }
-  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
-  pl.am = am;
+  const Addressing a = plan_addressing(f, o);
+  if (a.error || f.projection < kProjectMaximum || f.projection > kProjectMean || f.quad) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am);
   pl.project.mode = f.projection;
   pl.project.skip = f.ranges && f.projection != kProjectMean;
-  pl.project.clipped = f.clip_on || f.orthographic; // (an orthographic frame without a clip box: the clipped variant with the unit box)
-  pl.orthographic = f.orthographic;
-  pl.project.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
-  pl.march_lds_bytes = pl.project.lds_bytes; // project_kernel takes the in-place march's place in the launch sequence
+  pl.project.clipped = w.clipped;
+  pl.project.lds_bytes = w.lds_bytes;
   return pl;
 }
 
-// an isosurface frame: plan_projection's addressing and LDS (the axis tables alone; the colour of a hit is read from global memory), the committed shading
-// mode as the kernel's, the skipping twin whenever the ranges are bound
+// an isosurface frame: the committed shading mode as the kernel's, the skipping twin whenever the ranges are bound
 inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o)
 {
   LaunchPlan pl;
-  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
-  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
-  if (f.isosurfaces < 1 || f.isosurfaces > kMaxIsovalues || f.quad || (am < 3 && !f.tables) || (!f.sparse && f.n_schedule > 0 && !f.schedule)) {
-    pl.error = true;
-    return pl;
-  }
-  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
-  pl.am = am;
+  const Addressing a = plan_addressing(f, o);
+  if (a.error || f.isosurfaces < 1 || f.isosurfaces > kMaxIsovalues || f.quad) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am, f.translucent);
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.isosurface.on = true;
   pl.isosurface.skip = f.ranges;
   pl.isosurface.translucent = f.translucent;
-  pl.isosurface.clipped = f.clip_on || f.orthographic || f.translucent; // (a translucent frame without a clip box: the clipped variant with the unit box, like an orthographic one)
-  pl.orthographic = f.orthographic;
-  pl.isosurface.lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, am)), (size_t)kWaves * kCounterWords * 4);
-  pl.march_lds_bytes = pl.isosurface.lds_bytes; // isosurface_kernel takes the in-place march's place in the launch sequence
+  pl.isosurface.clipped = w.clipped;
+  pl.isosurface.lds_bytes = w.lds_bytes;
   return pl;
 }
 
@@ -233,14 +242,10 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   pl.cached = pl.shading == 2 && f.shadow_cache;
   if (pl.cached) pl.shading = 1;
   const int sh = pl.shading;
-  // addressing: the layout's mode, a more general one on request, then the row loads on mode 0
-  int am = addressing_mode(f.stored_bytes, f.elem_bytes, f.nx, f.ny, f.nz, f.n_color, f.n_alpha);
-  if (o.addressing >= 0) am = std::min(std::max(am, o.addressing), 3);
+  const Addressing a = plan_addressing(f, o);
   const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
-  if ((am < 3 && !f.tables) || tf == 0 || (!f.sparse && f.n_schedule > 0 && !f.schedule)) { pl.error = true; return pl; }
-  // mode 4: layouts the caches do not serve (by size), or forced either way
-  if (row_load_layout(f.elem_bytes, f.quad) && am == 0 && (f.row_loads > 0 ? f.row_loads != 1 : f.stored_bytes > (128ull << 20))) am = 4;
-  pl.am = am;
+  if (a.error || tf == 0) { pl.error = true; return pl; }
+  const int am = pl.am = a.am;
   pl.skip = f.skipping;
   pl.pooled = sh != 0 && f.pool;
   const size_t tables = align16(axis_table_bytes(f.nx, f.ny, f.nz, am));
@@ -271,7 +276,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   return pl;
 }
 
-// the plan's variants exist - what frame_kernels / project_kernels_of / isosurface_kernels_of then look up (f32_general decides the LDS-staged march alone)
+// the plan's variants exist - what frame_kernels / project_kernels_of / isosurface_kernels_of (ovr_hip_device.h: tables these predicates fill) then look up (f32_general decides the LDS-staged march alone)
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;

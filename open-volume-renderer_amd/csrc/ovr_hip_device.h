@@ -10,6 +10,8 @@
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 namespace ovrhip {
 
@@ -353,7 +355,7 @@ __device__ __forceinline__ unsigned int tap_cell(const VolConsts& vc, const Tap&
 // Which launches take the row loads: the 16-bit and 8-bit volumes whose layout is too large for the caches to serve (addressing modes 1 and 2, and mode 4 = mode 0's
 // 32-bit byte offsets + row loads: plan_launch upgrades a 16-bit or 8-bit layout of more than 128 MB).  Small 16-bit volumes are bound by vector issue and keep the
 // 4-byte loads (a 256 x 256 x 226 u16 volume, all samples shaded in place: 0.88 -> 1.08 ms WITH the row loads; the 1024 x 1024 x 1080 one 34 -> 24 ms).
-template <int VT, int AM> struct RowLoads { static constexpr bool on = sizeof(typename Vox<VT>::T) <= 2 && !Vox<VT>::kQuad && (AM == 1 || AM == 2 || AM == 4); };
+template <int VT, int AM> struct RowLoads { static constexpr bool on = row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad) && (AM == 1 || AM == 2 || AM == 4); };
 template <int VT, int AM, typename B>
 __device__ __forceinline__ typename Vox<VT>::P load_pair(const B* base, unsigned long long off) // off in units of B (bytes for char, else elements)
 {
@@ -1969,7 +1971,7 @@ __global__ __launch_bounds__(kBlock) void shade_pool_kernel(const RayMarchParams
 
 
 // ------------------------------------------------------------------------------------------------------------------
-// a launch plan's two kernels.  SHADE and AM come from a switch each, the plan's flags become template arguments through ONE constant, a set of
+// a launch plan's two kernels.  SHADE comes from a switch, AM from dispatch_addressing, the plan's flags become template arguments through ONE constant, a set of
 // bits: every combination for which march_variant_exists / shade_variant_exists (host/launch_plan.hpp) holds is instantiated, and nothing else
 // ------------------------------------------------------------------------------------------------------------------
 typedef void (*FrameKernel)(const RayMarchParams);
@@ -1995,30 +1997,48 @@ constexpr FrameKernel shade_variant()
     return shade_pool_kernel<VT, SHADE, AM, skip, material, clipped, cached, ortho>;
   else return nullptr;
 }
+// a run-time addressing mode as a compile-time one: f(std::integral_constant<int, AM>{}) for the modes the voxel type's kernels exist at - 0 to 3, and 4 exactly
+// where row_load_layout (host/launch_plan.hpp) holds for the type.  R() - no such variant - for any other mode, and with GENERAL_ONLY for a replica's type: the
+// kernels that exist for the general layouts alone (the layout that is always resident) are looked up through it, as dispatch_voxel_type<true> names their types
+template <typename R, int VT, bool GENERAL_ONLY = false, typename F>
+inline R dispatch_addressing(int am, F&& f)
+{
+  if constexpr (!GENERAL_ONLY || kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
+    switch (am) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4:
+      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) { // (mode 4 is RowLoads' own)
+        static_assert(RowLoads<VT, 4>::on, "row_load_layout (host/launch_plan.hpp) names the layouts RowLoads is on for");
+        return f(std::integral_constant<int, 4>{});
+      }
+    }
+  }
+  return R();
+}
+// entry i of the table { G::at<0>(), G::at<1>(), ... }: a lookup's variants by ONE constant, each entry an `if constexpr (<the predicate of host/launch_plan.hpp>)
+// <the kernel> else nullptr` - the predicate decides which kernels are instantiated
+template <typename G, unsigned... I>
+inline auto variant_at(unsigned i, std::integer_sequence<unsigned, I...>) -> decltype(G::template at<0>())
+{
+  static constexpr decltype(G::template at<0>()) table[] = { G::template at<I>()... };
+  return table[i];
+}
+
 template <int VT, int SHADE, int AM, unsigned... BITS>
 inline FrameKernels variants_of(unsigned march_bits, unsigned shade_bits, std::integer_sequence<unsigned, BITS...>)
 {
-  FrameKernels k;
-  if constexpr (AM != 4 || row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) { // (mode 4 is RowLoads' own)
-    static_assert(AM != 4 || RowLoads<VT, 4>::on, "row_load_layout (host/launch_plan.hpp) names the layouts RowLoads is on for");
-    static constexpr FrameKernel march[] = { march_variant<VT, SHADE, AM, BITS>()... }, shade[] = { shade_variant<VT, SHADE, AM, BITS>()... };
-    k.march = march[march_bits];
-    k.shade = shade[shade_bits];
-  }
-  return k;
+  static constexpr FrameKernel march[] = { march_variant<VT, SHADE, AM, BITS>()... }, shade[] = { shade_variant<VT, SHADE, AM, BITS>()... };
+  return { march[march_bits], shade[shade_bits] };
 }
 template <int VT, int SHADE>
 inline FrameKernels variants_of(int am, unsigned march_bits, unsigned shade_bits)
 {
-  const auto all = std::make_integer_sequence<unsigned, kVariantBitsEnd>();
-  switch (am) {
-  case 0: return variants_of<VT, SHADE, 0>(march_bits, shade_bits, all);
-  case 1: return variants_of<VT, SHADE, 1>(march_bits, shade_bits, all);
-  case 2: return variants_of<VT, SHADE, 2>(march_bits, shade_bits, all);
-  case 3: return variants_of<VT, SHADE, 3>(march_bits, shade_bits, all);
-  case 4: return variants_of<VT, SHADE, 4>(march_bits, shade_bits, all);
-  default: return FrameKernels();
-  }
+  return dispatch_addressing<FrameKernels, VT>(am, [&](auto m) {
+    return variants_of<VT, SHADE, decltype(m)::value>(march_bits, shade_bits, std::make_integer_sequence<unsigned, kVariantBitsEnd>());
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2071,18 +2091,7 @@ typedef void (*ShadowCacheKernel)(const RayMarchParams, const ShadowBuildArgs);
 template <int VT>
 ShadowCacheKernel shadow_cache_kernel_of(int am)
 {
-  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
-    switch (am) {
-    case 0: return shadow_cache_kernel<VT, 0>;
-    case 1: return shadow_cache_kernel<VT, 1>;
-    case 2: return shadow_cache_kernel<VT, 2>;
-    case 3: return shadow_cache_kernel<VT, 3>;
-    case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return shadow_cache_kernel<VT, 4>;
-      else return nullptr;
-    }
-  }
-  return nullptr;
+  return dispatch_addressing<ShadowCacheKernel, VT, true>(am, [](auto m) -> ShadowCacheKernel { return shadow_cache_kernel<VT, decltype(m)::value>; });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2338,49 +2347,26 @@ __global__ __launch_bounds__(kBlock) void project_floats_kernel(const RayMarchPa
 
 typedef void (*ProjectFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
 struct ProjectKernels { FrameKernel frame = nullptr; ProjectFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
-template <int VT, int AM, int MODE>
-inline ProjectKernels project_kernels_of(bool skip, bool clipped, bool ortho)
-{
-  ProjectKernels k;
-  if (ortho && !clipped) return k; // (project_variant_exists)
-  if constexpr (MODE != kProjectMean) {
-    if (skip) {
-      k.frame = ortho ? project_kernel<VT, AM, MODE, true, true, true> : clipped ? project_kernel<VT, AM, MODE, true, true> : project_kernel<VT, AM, MODE, true, false>;
-      k.floats = project_floats_kernel<VT, AM, MODE, true>;
-      return k;
-    }
+// the flags of a projection's or an isosurface's variant as one constant: these bits, above them the mode (from kProjectMaximum) or the shading mode
+enum WalkBits : unsigned { kWalkSkip = 1, kWalkClipped = 2, kWalkOrtho = 4, kWalkBitsEnd = 8 };
+inline unsigned walk_bits(bool skip, bool clipped, bool ortho) { return (skip ? kWalkSkip : 0u) | (clipped ? kWalkClipped : 0u) | (ortho ? kWalkOrtho : 0u); }
+template <int VT, int AM> struct ProjectVariants {
+  template <unsigned I> static constexpr ProjectKernels at()
+  {
+    constexpr int mode = kProjectMaximum + (int)(I / kWalkBitsEnd);
+    constexpr bool skip = I & kWalkSkip, clipped = I & kWalkClipped, ortho = I & kWalkOrtho;
+    if constexpr (project_variant_exists(mode, AM, skip, clipped, ortho)) return { project_kernel<VT, AM, mode, skip, clipped, ortho>, project_floats_kernel<VT, AM, mode, skip> };
+    else return {};
   }
-  if (skip) return k;
-  k.frame = ortho ? project_kernel<VT, AM, MODE, false, true, true> : clipped ? project_kernel<VT, AM, MODE, false, true> : project_kernel<VT, AM, MODE, false, false>;
-  k.floats = project_floats_kernel<VT, AM, MODE, false>;
-  return k;
-}
-template <int VT, int AM>
-inline ProjectKernels project_kernels_of(int mode, bool skip, bool clipped, bool ortho)
-{
-  switch (mode) {
-  case kProjectMaximum: return project_kernels_of<VT, AM, kProjectMaximum>(skip, clipped, ortho);
-  case kProjectMinimum: return project_kernels_of<VT, AM, kProjectMinimum>(skip, clipped, ortho);
-  case kProjectMean: return project_kernels_of<VT, AM, kProjectMean>(skip, clipped, ortho);
-  default: return ProjectKernels();
-  }
-}
-// the projection kernels of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads), like shadow_cache_kernel_of
+};
+// a projection plan's kernels of a voxel type; nullptr for a replica's type (or mode 4 on a layout without row loads), like shadow_cache_kernel_of
 template <int VT>
-ProjectKernels project_kernels_of(int am, int mode, bool skip, bool clipped, bool ortho)
+ProjectKernels project_kernels_of(const LaunchPlan& pl)
 {
-  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
-    switch (am) {
-    case 0: return project_kernels_of<VT, 0>(mode, skip, clipped, ortho);
-    case 1: return project_kernels_of<VT, 1>(mode, skip, clipped, ortho);
-    case 2: return project_kernels_of<VT, 2>(mode, skip, clipped, ortho);
-    case 3: return project_kernels_of<VT, 3>(mode, skip, clipped, ortho);
-    case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return project_kernels_of<VT, 4>(mode, skip, clipped, ortho);
-      else return ProjectKernels();
-    }
-  }
-  return ProjectKernels();
+  constexpr unsigned n = (kProjectMean - kProjectMaximum + 1) * kWalkBitsEnd;
+  const unsigned i = (unsigned)(pl.project.mode - kProjectMaximum) * kWalkBitsEnd + walk_bits(pl.project.skip, pl.project.clipped, pl.orthographic);
+  if (pl.error || i >= n) return ProjectKernels(); // (a plan without a projection: mode 0)
+  return dispatch_addressing<ProjectKernels, VT, true>(pl.am, [&](auto m) { return variant_at<ProjectVariants<VT, decltype(m)::value>>(i, std::make_integer_sequence<unsigned, n>()); });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3017,85 +3003,38 @@ __global__ __launch_bounds__(kBlock) void isosurface_layers_floats_kernel(const 
   if (valid && sub == 0) { q[0] = (float)il.events; q[1] = il.A; q[2] = live ? (float)il.steps : 0.f; q[3] = (float)il.shadow_steps; }
 }
 
+// the isosurface kernels of a voxel type, TRANS: the translucent ones - ONE LOOKUP, TWO EXPLICIT INSTANTIATIONS PER TYPE, each in an object
+// of its own (ovr_hip_isosurface.hip without and with -DOVR_ISO_LAYERS): beside the translucent kernels the opaque ones took other registers, so the opaque
+// kernels' object is compiled from what it was compiled from.  The translucent kernels exist on the clipped box test alone (isosurface_variant_exists)
 typedef void (*IsosurfaceFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long);
-struct IsosurfaceKernels { FrameKernel frame = nullptr; IsosurfaceFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
-template <int VT, int AM, int SHADE>
-inline FrameKernel isosurface_frame_kernel(bool skip, bool clipped, bool ortho)
-{
-  if (ortho) return !clipped ? nullptr : skip ? isosurface_kernel<VT, AM, SHADE, true, true, true> : isosurface_kernel<VT, AM, SHADE, false, true, true>; // (isosurface_variant_exists)
-  if (skip) return clipped ? isosurface_kernel<VT, AM, SHADE, true, true> : isosurface_kernel<VT, AM, SHADE, true, false>;
-  return clipped ? isosurface_kernel<VT, AM, SHADE, false, true> : isosurface_kernel<VT, AM, SHADE, false, false>;
-}
-template <int VT, int AM>
-inline IsosurfaceKernels isosurface_kernels_of(int shade, bool skip, bool clipped, bool ortho)
-{
-  IsosurfaceKernels k;
-  switch (shade) {
-  case 0: k.frame = isosurface_frame_kernel<VT, AM, 0>(skip, clipped, ortho); break;
-  case 1: k.frame = isosurface_frame_kernel<VT, AM, 1>(skip, clipped, ortho); break;
-  case 2: k.frame = isosurface_frame_kernel<VT, AM, 2>(skip, clipped, ortho); break;
-  default: return k;
-  }
-  k.floats = skip ? isosurface_floats_kernel<VT, AM, true> : isosurface_floats_kernel<VT, AM, false>;
-  return k;
-}
-// the isosurface kernels of a voxel type at an addressing mode; nullptr for a replica's type (or mode 4 on a layout without row loads), like project_kernels_of
-template <int VT>
-IsosurfaceKernels isosurface_kernels_of(int am, int shade, bool skip, bool clipped, bool ortho)
-{
-  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
-    switch (am) {
-    case 0: return isosurface_kernels_of<VT, 0>(shade, skip, clipped, ortho);
-    case 1: return isosurface_kernels_of<VT, 1>(shade, skip, clipped, ortho);
-    case 2: return isosurface_kernels_of<VT, 2>(shade, skip, clipped, ortho);
-    case 3: return isosurface_kernels_of<VT, 3>(shade, skip, clipped, ortho);
-    case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return isosurface_kernels_of<VT, 4>(shade, skip, clipped, ortho);
-      else return IsosurfaceKernels();
-    }
-  }
-  return IsosurfaceKernels();
-}
-
-// the translucent kernels of a voxel type: a lookup and an object of their own beside the type's isosurface object (ovr_hip_isosurface.hip
-// compiled with -DOVR_ISO_LAYERS), so that the opaque kernels' object is compiled from what it was compiled from.  On the clipped box test alone
-// (isosurface_variant_exists): there is no `clipped` to ask for
 typedef void (*IsosurfaceLayersFloatsKernel)(const RayMarchParams, const float*, const float*, float*, long long, int);
-struct IsosurfaceLayersKernels { FrameKernel frame = nullptr; IsosurfaceLayersFloatsKernel floats = nullptr; }; // nullptr: no such variant of this type
-template <int VT, int AM, int SHADE>
-inline FrameKernel isosurface_layers_frame_kernel(bool skip, bool ortho)
-{
-  if (ortho) return skip ? isosurface_kernel<VT, AM, SHADE, true, true, true, true> : isosurface_kernel<VT, AM, SHADE, false, true, true, true>;
-  return skip ? isosurface_kernel<VT, AM, SHADE, true, true, false, true> : isosurface_kernel<VT, AM, SHADE, false, true, false, true>;
-}
-template <int VT, int AM>
-inline IsosurfaceLayersKernels isosurface_layers_kernels_of(int shade, bool skip, bool ortho)
-{
-  IsosurfaceLayersKernels k;
-  switch (shade) {
-  case 0: k.frame = isosurface_layers_frame_kernel<VT, AM, 0>(skip, ortho); break;
-  case 1: k.frame = isosurface_layers_frame_kernel<VT, AM, 1>(skip, ortho); break;
-  case 2: k.frame = isosurface_layers_frame_kernel<VT, AM, 2>(skip, ortho); break;
-  default: return k;
+template <bool TRANS> struct IsosurfaceKernelsOf { // nullptr: no such variant of this type
+  FrameKernel frame = nullptr;
+  std::conditional_t<TRANS, IsosurfaceLayersFloatsKernel, IsosurfaceFloatsKernel> floats = nullptr;
+};
+typedef IsosurfaceKernelsOf<false> IsosurfaceKernels;
+typedef IsosurfaceKernelsOf<true> IsosurfaceLayersKernels;
+template <int VT, int AM, bool TRANS> struct IsosurfaceVariants {
+  template <unsigned I> static constexpr IsosurfaceKernelsOf<TRANS> at()
+  {
+    constexpr int shade = (int)(I / kWalkBitsEnd);
+    constexpr bool skip = I & kWalkSkip, clipped = I & kWalkClipped, ortho = I & kWalkOrtho;
+    if constexpr (!isosurface_variant_exists(shade, AM, skip, clipped, ortho, TRANS)) return {};
+    else if constexpr (TRANS) return { isosurface_kernel<VT, AM, shade, skip, clipped, ortho, true>, isosurface_layers_floats_kernel<VT, AM, skip> };
+    else return { isosurface_kernel<VT, AM, shade, skip, clipped, ortho>, isosurface_floats_kernel<VT, AM, skip> };
   }
-  k.floats = skip ? isosurface_layers_floats_kernel<VT, AM, true> : isosurface_layers_floats_kernel<VT, AM, false>;
-  return k;
-}
-template <int VT>
-IsosurfaceLayersKernels isosurface_layers_kernels_of(int am, int shade, bool skip, bool ortho)
+};
+// an isosurface plan's kernels of a voxel type - the opaque ones for an opaque plan, the translucent ones for a translucent plan; nullptr otherwise, for a
+// replica's type and for mode 4 on a layout without row loads, like project_kernels_of
+template <int VT, bool TRANS>
+IsosurfaceKernelsOf<TRANS> isosurface_kernels_of(const LaunchPlan& pl)
 {
-  if constexpr (kVoxelTypes[VT].layout == LAYOUT_GENERAL) {
-    switch (am) {
-    case 0: return isosurface_layers_kernels_of<VT, 0>(shade, skip, ortho);
-    case 1: return isosurface_layers_kernels_of<VT, 1>(shade, skip, ortho);
-    case 2: return isosurface_layers_kernels_of<VT, 2>(shade, skip, ortho);
-    case 3: return isosurface_layers_kernels_of<VT, 3>(shade, skip, ortho);
-    case 4:
-      if constexpr (row_load_layout((int)sizeof(typename Vox<VT>::T), Vox<VT>::kQuad)) return isosurface_layers_kernels_of<VT, 4>(shade, skip, ortho);
-      else return IsosurfaceLayersKernels();
-    }
-  }
-  return IsosurfaceLayersKernels();
+  constexpr unsigned n = 3 * kWalkBitsEnd;
+  const unsigned i = (unsigned)pl.shading * kWalkBitsEnd + walk_bits(pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic);
+  if (pl.error || !pl.isosurface.on || pl.isosurface.translucent != TRANS || i >= n) return IsosurfaceKernelsOf<TRANS>();
+  return dispatch_addressing<IsosurfaceKernelsOf<TRANS>, VT, true>(pl.am, [&](auto m) {
+    return variant_at<IsosurfaceVariants<VT, decltype(m)::value, TRANS>>(i, std::make_integer_sequence<unsigned, n>());
+  });
 }
 
 // one explicit instantiation per voxel type, each an object of its own (ovr_hip_march.hip, compiled once per type): the ~160 kernel

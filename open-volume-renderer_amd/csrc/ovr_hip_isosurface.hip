@@ -11,8 +11,8 @@
 namespace ovrhip {
 static_assert(kVoxelTypes[OVR_MARCH_VT].layout == LAYOUT_GENERAL, "the isosurface kernels read the general layout");
 #ifdef OVR_ISO_LAYERS
-template IsosurfaceLayersKernels isosurface_layers_kernels_of<OVR_MARCH_VT>(int, int, bool, bool);
+template IsosurfaceLayersKernels isosurface_kernels_of<OVR_MARCH_VT, true>(const LaunchPlan&);
 #else
-template IsosurfaceKernels isosurface_kernels_of<OVR_MARCH_VT>(int, int, bool, bool, bool);
+template IsosurfaceKernels isosurface_kernels_of<OVR_MARCH_VT, false>(const LaunchPlan&);
 #endif
 }

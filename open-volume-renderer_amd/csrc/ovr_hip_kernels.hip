@@ -956,18 +956,23 @@ __global__ __launch_bounds__(256) void shade_order_kernel(const RayMarchParams P
   }
 }
 
+// every launch with dynamic LDS: one needing 64 KiB of it or more raises the kernel's limit first (from 64 KiB: a kernel's static words count against the same
+// limit; per launch: the attribute belongs to the current device's copy of the kernel).  An empty grid launches nothing
+template <typename... Params, typename... Args>
+static hipError_t launch_variant(void (*kern)(Params...), dim3 grid, int block, size_t lds, hipStream_t stream, const Args&... args)
+{
+  if (lds >= 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
+  if (grid.x > 0) hipLaunchKernelGGL(kern, grid, dim3(block), lds, stream, static_cast<Params>(args)...);
+  return hipGetLastError();
+}
+
 static hipError_t launch_shade_order(const RayMarchParams& q, hipStream_t stream)
 {
   const unsigned int slots = q.pool.capacity / (unsigned int)kRun;
   const dim3 grid((slots + 256u * kOrderSlots - 1u) / (256u * kOrderSlots));
   if (grid.x == 0) return hipSuccess;
-  const size_t lds = (size_t)q.pool.order_grid * q.pool.order_grid * sizeof(unsigned int);
-  if (lds >= 48 * 1024) { // 128 x 128 beams: 64 KiB of offsets + the static words (per launch: the attribute belongs to the current device's copy of the kernel)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(shade_order_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(shade_order_kernel, grid, dim3(256), lds, stream, q);
-  return hipGetLastError();
+  return launch_variant(shade_order_kernel, grid, 256, (size_t)q.pool.order_grid * q.pool.order_grid * sizeof(unsigned int), stream, q); // (128 x 128 beams: 64 KiB of offsets)
 }
 
 constexpr int kReduceBlocks = 64;
@@ -979,10 +984,6 @@ static hipError_t launch_reduce_counters(const unsigned int* partials, int n_blo
                      done ? publish : nullptr, done, conv_asked);
   return hipGetLastError();
 }
-
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template FrameKernels frame_kernels<E>(const LaunchPlan&);
-OVR_VOXEL_TYPES(OVR_X)
-#undef OVR_X
 
 size_t pool_shade_blocks() { return kShadeBlocks; }
 
@@ -1019,15 +1020,6 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   return plan_launch(f, o);
 }
 
-// a launch needing more than 64 KiB of LDS raises the kernel's limit first (per launch: the attribute belongs to the current device's copy of the kernel)
-static hipError_t launch_variant(FrameKernel kern, dim3 grid, size_t lds, hipStream_t stream, const RayMarchParams& prm)
-{
-  if (lds > 64 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
-  if (grid.x > 0) hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, stream, prm);
-  return hipSuccess;
-}
-
 // the frame's kernels between its first and last event: in place march -> reduction; pooled, once per sample-per-pixel generation,
 // march -> (order) -> shade -> composite -> reduction
 static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& plan, const FrameKernels& k, hipStream_t stream, const hipEvent_t* ev)
@@ -1037,8 +1029,7 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   if (!plan.pooled) {
     RayMarchParams q = p;
     if (plan.march.lds_staged) q.lds_brick_offset = plan.lds_brick_offset; // the bricks follow the tables and the TF
-    if ((e = launch_variant(k.march, grid, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_variant(k.march, grid, kBlock, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
     if (ev && ev[1] && ev[2]) { (void)hipEventRecord(ev[1], stream); (void)hipEventRecord(ev[2], stream); }
     if (p.block_counters && p.counters) {
       if (!p.publish || p.zero_first)
@@ -1059,12 +1050,10 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   for (int g = 0; g < p.spp; ++g) {
     q.spp_index = g;
     if (g > 0 && (e = hipMemsetAsync(p.pool.ctrl, 0, (size_t)32 * (kPoolSubs + 1) * sizeof(unsigned int), stream)) != hipSuccess) return e; // all but the frame's maximum
-    if ((e = launch_variant(k.march, grid, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_variant(k.march, grid, kBlock, plan.march_lds_bytes, stream, q)) != hipSuccess) return e;
     if (ev && ev[1] && g == p.spp - 1) (void)hipEventRecord(ev[1], stream);
     if (q.pool.order && (e = launch_shade_order(q, stream)) != hipSuccess) return e; // runs sorted by light beam (PoolDesc)
-    if ((e = launch_variant(k.shade, dim3((unsigned)plan.shade_grid_blocks), plan.shade_lds_bytes, stream, q)) != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_variant(k.shade, dim3((unsigned)plan.shade_grid_blocks), kBlock, plan.shade_lds_bytes, stream, q)) != hipSuccess) return e;
     if (ev && ev[2] && g == p.spp - 1) (void)hipEventRecord(ev[2], stream);
     if (grid.x > 0 && (e = launch_composite(q, grid, stream)) != hipSuccess) return e;
     if (p.block_counters && p.counters)
@@ -1074,36 +1063,36 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   return hipGetLastError();
 }
 
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template ProjectKernels project_kernels_of<E>(int, int, bool, bool, bool);
+// the lookups of ovr_hip_device.h, instantiated once per voxel type in objects of their own: ovr_hip_march.hip (every type), ovr_hip_isosurface.hip (the general
+// layout's types alone, the opaque and the translucent kernels each in an object of their own - DESIGN.md section 19)
+#define OVR_X(E, NAME, BASE, LAYOUT)                                                          \
+  extern template FrameKernels frame_kernels<E>(const LaunchPlan&);                           \
+  extern template ShadowCacheKernel shadow_cache_kernel_of<E>(int);                           \
+  extern template ProjectKernels project_kernels_of<E>(const LaunchPlan&);                    \
+  extern template IsosurfaceKernels isosurface_kernels_of<E, false>(const LaunchPlan&);       \
+  extern template IsosurfaceLayersKernels isosurface_kernels_of<E, true>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 #undef OVR_X
-static ProjectKernels project_kernels(const RayMarchParams& p, const LaunchPlan& plan)
-{
-  ProjectKernels k;
-  if (!plan.error) dispatch_voxel_type(p.vol.type, [&](auto vt) { k = project_kernels_of<decltype(vt)::value>(plan.am, plan.project.mode, plan.project.skip, plan.project.clipped, plan.orthographic); });
-  return k;
-}
 
-// (the isosurface kernels exist for the general layout's types alone: ovr_hip_isosurface.hip, one object per such type)
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceKernels isosurface_kernels_of<E>(int, int, bool, bool, bool);
-OVR_VOXEL_TYPES(OVR_X)
-#undef OVR_X
-static IsosurfaceKernels isosurface_kernels(const RayMarchParams& p, const LaunchPlan& plan)
+// a plan's kernels for the volume's voxel type: the frame's two - a projection's or an isosurface's kernel in the in-place march's place (such a plan is neither
+// pooled nor LDS-staged, march_lds_bytes is that kernel's) - and the known-answer entry's of such a plan.  All nullptr: the plan is an error, or no such variant
+struct PlanKernels {
+  FrameKernels frame;
+  ProjectFloatsKernel project_floats = nullptr;
+  IsosurfaceFloatsKernel isosurface_floats = nullptr;
+  IsosurfaceLayersFloatsKernel isosurface_layers_floats = nullptr;
+};
+static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
-  IsosurfaceKernels k;
-  if (!plan.error && plan.isosurface.on)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.isosurface.clipped, plan.orthographic); });
-  return k;
-}
-// (the translucent twins: an object of their own per such type, from the same unit - DESIGN.md section 19)
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template IsosurfaceLayersKernels isosurface_layers_kernels_of<E>(int, int, bool, bool);
-OVR_VOXEL_TYPES(OVR_X)
-#undef OVR_X
-static IsosurfaceLayersKernels isosurface_layers_kernels(const RayMarchParams& p, const LaunchPlan& plan)
-{
-  IsosurfaceLayersKernels k;
-  if (!plan.error && plan.isosurface.on && plan.isosurface.translucent && plan.isosurface.clipped)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { k = isosurface_layers_kernels_of<decltype(vt)::value>(plan.am, plan.shading, plan.isosurface.skip, plan.orthographic); });
+  PlanKernels k;
+  if (plan.error) return k;
+  if (plan.isosurface.on && plan.isosurface.translucent)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, true>(plan); k.frame.march = v.frame; k.isosurface_layers_floats = v.floats; });
+  else if (plan.isosurface.on)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, false>(plan); k.frame.march = v.frame; k.isosurface_floats = v.floats; });
+  else if (plan.project.mode != 0)
+    dispatch_voxel_type(p.vol.type, [&](auto vt) { const auto v = project_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.project_floats = v.floats; });
+  else dispatch_voxel_type(p.vol.type, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); });
   return k;
 }
 
@@ -1111,12 +1100,7 @@ hipError_t launch_raymarch(const RayMarchParams& p, const LaunchPlan& plan, hipS
 {
   // ev (optional): ev[0] before the first kernel, ev[1] after the march, ev[2] after the shade kernel (both may be null: no per-phase times), ev[3] at the end
   if (ev) (void)hipEventRecord(ev[0], stream);
-  FrameKernels k;
-  // a projection frame: project_kernel in the in-place march's place (its plan is neither pooled nor LDS-staged, march_lds_bytes is the projection's), then
-  // the same reduction and publish steps
-  if (plan.isosurface.on) k.march = plan.isosurface.translucent ? isosurface_layers_kernels(p, plan).frame : isosurface_kernels(p, plan).frame; // an isosurface frame: the same place, the same steps behind it
-  else if (plan.project.mode != 0) k.march = project_kernels(p, plan).frame;
-  else dispatch_voxel_type(p.vol.type, [&](auto vt) { k = frame_kernels<decltype(vt)::value>(plan); });
+  const FrameKernels k = plan_kernels(p, plan).frame; // (a projection or an isosurface frame: the same reduction and publish steps behind its kernel)
   const hipError_t e = k.march && (k.shade || !plan.pooled) ? launch_sequence(p, plan, k, stream, ev) : hipErrorInvalidValue;
   if (ev) (void)hipEventRecord(ev[3], stream);
   return e;
@@ -2057,18 +2041,30 @@ hipError_t launch_shade_floats(const RayMarchParams& p, const float* normal_w, c
   return hipGetLastError();
 }
 
+// a frame's parameters as those of a known-answer query (or of the shadow cache's build): the frame's own machinery - request pool, majorants, sample list, block
+// list, LDS staging - is not the query's; the macrocells' value ranges stay bound only where the query skips by them
+static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
+{
+  RayMarchParams q = p;
+  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  if (!keep_ranges) q.mc_ranges = nullptr;
+  return q;
+}
+// the grid of a query kernel with four lanes per ray (n > 0); 0: more workgroups than a grid holds
+static unsigned int quad_ray_blocks(int64_t n)
+{
+  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
+  return blocks > 0x7fffffffll ? 0u : (unsigned int)blocks;
+}
+
 // the shadow cache's build and the shadow march's known-answer entry (ShadowBuildArgs): the kernel of the general layout's type at the addressing mode the
 // frame's kernels take for that layout (plan_launch: the layout's mode, the environment's override, the row loads)
-#define OVR_X(E, NAME, BASE, LAYOUT) extern template ShadowCacheKernel shadow_cache_kernel_of<E>(int);
-OVR_VOXEL_TYPES(OVR_X)
-#undef OVR_X
 hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a, hipStream_t stream)
 {
   if (a.n <= 0) return hipSuccess;
   if (!a.out && !(a.pos_out && !a.pos)) return hipErrorInvalidValue; // nothing to write: out, or the nodes' positions alone
-  RayMarchParams q = p;
-  q.shading = 0; q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
-  q.shadow_lattice = nullptr;
+  RayMarchParams q = query_params(p, true);
+  q.shading = 0; q.shadow_lattice = nullptr;
   q.iso_n = 0; // (p may be a frame's parameters: the plan asked here is the march's, whatever the last frame drew)
   const LaunchPlan pl = plan_raymarch(q);
   if (pl.error) return hipErrorInvalidValue;
@@ -2076,8 +2072,6 @@ hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a
   dispatch_voxel_type(q.vol.type, [&](auto vt) { kern = shadow_cache_kernel_of<decltype(vt)::value>(pl.am); });
   if (!kern) return hipErrorInvalidValue;
   const size_t lds = align16(axis_table_bytes(q.vol.nx, q.vol.ny, q.vol.nz, pl.am)) + (size_t)q.n_alpha * 4 + 64;
-  if (lds > 64 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
   long long blocks;
   if (a.pos) blocks = (a.n + kBlock - 1) / kBlock;
   else {
@@ -2086,8 +2080,7 @@ hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a
     blocks = (tiles + kWaves - 1) / kWaves;
   }
   if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), lds, stream, q, a);
-  return hipGetLastError();
+  return launch_variant(kern, dim3((unsigned)blocks), kBlock, lds, stream, q, a);
 }
 
 // known-answer entry of the lattice lookup: to_object as shade_request forms po, then shadow_lookup exactly as the cached kernels call it
@@ -2113,19 +2106,13 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
 {
   if (n <= 0) return hipSuccess;
   if (range_skipping && !p.mc_ranges) return hipErrorInvalidValue;
-  RayMarchParams q = p;
+  RayMarchParams q = query_params(p, range_skipping != 0);
   q.projection = mode; q.iso_n = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
-  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
-  if (!range_skipping) q.mc_ranges = nullptr;
   const LaunchPlan pl = plan_raymarch(q);
-  const ProjectFloatsKernel kern = project_kernels(q, pl).floats;
-  if (!kern) return hipErrorInvalidValue;
-  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-  if (pl.project.lds_bytes > 64 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.project.lds_bytes)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.project.lds_bytes, stream, q, org, dir, out, (long long)n);
-  return hipGetLastError();
+  const ProjectFloatsKernel kern = plan_kernels(q, pl).project_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
 }
 
 // known-answer entry of the isosurfaces: the kernel of the general layout's type at the addressing mode an isosurface frame takes for it
@@ -2133,19 +2120,13 @@ hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, c
 {
   if (n <= 0) return hipSuccess;
   if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues) return hipErrorInvalidValue;
-  RayMarchParams q = p;
-  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
-  if (!range_skipping) q.mc_ranges = nullptr;
+  RayMarchParams q = query_params(p, range_skipping != 0);
   q.iso_translucent = 0; // (the first crossing, opaque, whatever opacities are committed)
   const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceFloatsKernel kern = isosurface_kernels(q, pl).floats;
-  if (!kern) return hipErrorInvalidValue;
-  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
-  if (pl.isosurface.lds_bytes > 64 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.isosurface.lds_bytes)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.isosurface.lds_bytes, stream, q, org, dir, out, (long long)n);
-  return hipGetLastError();
+  const IsosurfaceFloatsKernel kern = plan_kernels(q, pl).isosurface_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
 }
 
 // known-answer entry of the translucent isosurfaces: the twin of the kernel above, at the addressing mode a translucent frame takes.  out is zeroed first: the
@@ -2155,20 +2136,14 @@ hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float*
 {
   if (n <= 0) return hipSuccess;
   if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16) return hipErrorInvalidValue;
-  RayMarchParams q = p;
-  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
-  if (!range_skipping) q.mc_ranges = nullptr;
+  RayMarchParams q = query_params(p, range_skipping != 0);
   q.iso_translucent = 1;
   const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceLayersFloatsKernel kern = isosurface_layers_kernels(q, pl).floats;
-  if (!kern) return hipErrorInvalidValue;
-  const long long blocks = ((long long)n * 4 + kBlock - 1) / kBlock;
-  if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+  const IsosurfaceLayersFloatsKernel kern = plan_kernels(q, pl).isosurface_layers_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
   if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(4 + 8 * max_events) * sizeof(float), stream)) return e;
-  if (pl.isosurface.lds_bytes > 64 * 1024)
-    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.isosurface.lds_bytes)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kBlock), pl.isosurface.lds_bytes, stream, q, org, dir, out, (long long)n, max_events);
-  return hipGetLastError();
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
 }
 
 // known-answer entry of the box test: the object-space ray as the march forms it (to_object of the origin, the direction scaled by inv_scale, not

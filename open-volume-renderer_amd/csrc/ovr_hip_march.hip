@@ -9,5 +9,5 @@
 namespace ovrhip {
 template FrameKernels frame_kernels<OVR_MARCH_VT>(const LaunchPlan&);
 template ShadowCacheKernel shadow_cache_kernel_of<OVR_MARCH_VT>(int);
-template ProjectKernels project_kernels_of<OVR_MARCH_VT>(int, int, bool, bool, bool);
+template ProjectKernels project_kernels_of<OVR_MARCH_VT>(const LaunchPlan&);
 }

@@ -16,7 +16,8 @@ sys.path.insert(0, ROOT)
 INF = float("inf")
 N, SIZE = 24, (96, 64)
 
-# name -> (environment, settings): dtype, shading, pipeline (1 in place, 2 pooled), skip, material, clip, spp, shard, sparse, lds, layout
+# name -> (environment, settings): dtype, shading, pipeline (1 in place, 2 pooled), skip, material, clip, spp, shard, sparse, lds, layout, projection (mode),
+# iso (isovalues of a [0, 1] field) with opacities, ortho, cache (the shadow cache: its build, then a cached frame), query (a known-answer entry, 8 rays)
 STATES = [
     ("unshaded_f32_lds_staged", {}, dict(shading=0, lds=True)),
     ("unshaded_f32_plain", {}, dict(shading=0, lds=False)),
@@ -50,6 +51,50 @@ STATES += [
     ("f32_thin_layout", {}, dict(shading=2, pipeline=2, layout=1)),
     ("u16_quad_layout", {}, dict(dtype="uint16", shading=2, pipeline=1, layout=3)),
 ]
+ISO, LAYERS = (0.4, 0.6), dict(iso=(0.4, 0.6), opacities=(0.5, 1.0))
+U16_ROWS = {"OVR_HIP_ROW_LOADS": "1"}
+STATES += [
+    ("projection_maximum", {}, dict(shading=0, projection=1)),
+    ("projection_minimum", {}, dict(shading=0, projection=2)),
+    ("projection_mean", {}, dict(shading=0, projection=3)),
+    ("projection_maximum_range_skipping", {}, dict(shading=0, projection=1, skip=True)),
+    ("projection_mean_skipping_on", {}, dict(shading=0, projection=3, skip=True)),
+    ("projection_maximum_clipped", {}, dict(shading=0, projection=1, clip=True)),
+    ("projection_maximum_orthographic", {}, dict(shading=0, projection=1, ortho=True)),
+    ("projection_minimum_range_skipping_orthographic_clipped", {}, dict(shading=0, projection=2, skip=True, ortho=True, clip=True)),
+    ("projection_u16_row_loads", U16_ROWS, dict(dtype="uint16", shading=0, projection=1)),
+]
+STATES += [(f"projection_addressing{_a}", {"OVR_HIP_ADDRESSING": str(_a)}, dict(shading=0, projection=1)) for _a in (1, 2, 3)]
+STATES += [(f"isosurface_shading{_s}", {}, dict(shading=_s, iso=ISO)) for _s in (0, 1, 2)]
+STATES += [
+    ("isosurface_range_skipping", {}, dict(shading=2, iso=ISO, skip=True)),
+    ("isosurface_clipped", {}, dict(shading=2, iso=ISO, clip=True)),
+    ("isosurface_orthographic", {}, dict(shading=2, iso=ISO, ortho=True)),
+    ("isosurface_range_skipping_orthographic", {}, dict(shading=1, iso=ISO, skip=True, ortho=True)),
+    ("isosurface_u8", {}, dict(dtype="uint8", shading=2, iso=ISO)),
+    ("isosurface_u16_row_loads", U16_ROWS, dict(dtype="uint16", shading=2, iso=ISO)),
+    ("isosurface_addressing3", {"OVR_HIP_ADDRESSING": "3"}, dict(shading=2, iso=ISO)),
+    ("translucent_shading0", {}, dict(shading=0, **LAYERS)),
+    ("translucent_shading2", {}, dict(shading=2, **LAYERS)),
+    ("translucent_shading0_orthographic", {}, dict(shading=0, ortho=True, **LAYERS)),
+    ("translucent_shading2_orthographic", {}, dict(shading=2, ortho=True, **LAYERS)),
+    ("translucent_range_skipping", {}, dict(shading=2, skip=True, **LAYERS)),
+    ("translucent_u16_row_loads_clipped", U16_ROWS, dict(dtype="uint16", shading=1, clip=True, **LAYERS)),
+    ("orthographic_unshaded", {}, dict(shading=0, lds=True, ortho=True)),
+    ("orthographic_shading2_inplace", {}, dict(shading=2, pipeline=1, ortho=True)),
+    ("orthographic_shading2_pooled", {}, dict(shading=2, pipeline=2, ortho=True)),
+    ("orthographic_shading1_pooled_skipping", {}, dict(shading=1, pipeline=2, skip=True, ortho=True)),
+    ("shadow_cache_inplace", {}, dict(shading=2, pipeline=1, cache=True)),
+    ("shadow_cache_pooled", {}, dict(shading=2, pipeline=2, cache=True)),
+    ("shadow_cache_u16_row_loads_orthographic", U16_ROWS, dict(dtype="uint16", shading=2, pipeline=2, cache=True, ortho=True)),
+    ("query_project_rays", {}, dict(shading=0, query="project")),
+    ("query_project_rays_u16_row_loads", U16_ROWS, dict(dtype="uint16", shading=0, query="project")),
+    ("query_isosurface_rays", {}, dict(shading=2, iso=ISO, query="isosurface")),
+    ("query_isosurface_rays_addressing2", {"OVR_HIP_ADDRESSING": "2"}, dict(shading=2, iso=ISO, query="isosurface")),
+    ("query_isosurface_layer_rays", {}, dict(shading=2, query="layers", **LAYERS)),
+    ("query_shadow_floats", {}, dict(shading=2, pipeline=1, query="shadow")),
+    ("query_shadow_floats_u8_addressing1", {"OVR_HIP_ADDRESSING": "1"}, dict(dtype="uint8", shading=2, pipeline=1, query="shadow")),
+]
 ENV_KEYS = ("OVR_HIP_ADDRESSING", "OVR_HIP_ROW_LOADS")
 
 
@@ -57,7 +102,8 @@ def run_state(ovr, np, name, env, s):
     for k in ENV_KEYS:
         os.environ.pop(k, None)
     os.environ.update(env)
-    vol = ovr.synth.make_volume(N, dtype=np.dtype(s.get("dtype", "float32")))
+    dtype = np.dtype(s.get("dtype", "float32"))
+    vol = ovr.synth.make_volume(N, dtype=dtype)
     colors, alphas, vr = ovr.synth.make_tfn("sparse", 256)
     ren = ovr.create_renderer("hip", 0)
     ren.set_fbsize(SIZE)
@@ -82,12 +128,35 @@ def run_state(ovr, np, name, env, s):
         ren.set_sparse_sampling(True)
     if s.get("shard"):
         ren.set_image_shard(*s["shard"])
-    ren.init(ovr.Scene(volume=vol, transfer_function=None), ovr.Camera(*ovr.synth.make_camera("oblique", N)))
+    eye, at, up = ovr.synth.make_camera("oblique", N)
+    ren.init(ovr.Scene(volume=vol, transfer_function=None), ovr.Camera(eye, at, up, orthographic_height=ovr.camera.auto_height(eye, at, 60.0) if s.get("ortho") else None))
     if s.get("clip"):
         ren.set_clip_box((-INF, -INF, -INF), (N / 2.0, INF, INF))
+    if "projection" in s:
+        ren.set_projection(s["projection"])
+    if "iso" in s:  # (in the samples' units: the 16-bit types' are raw)
+        ren.set_isosurfaces([v * (65535.0 if dtype == np.uint16 else 1.0) for v in s["iso"]], s.get("opacities"))
+    if s.get("cache"):
+        ren.set_shadow_cache(1)
     ren.commit()
     for _ in range(2 if s.get("sparse") else 1):
         ren.render()
+    if "query" in s:  # 8 rays from the eye into the volume (the entries take the last frame's parameters)
+        org = np.tile(np.asarray(eye, np.float32), (8, 1))
+        aim = np.asarray(at, np.float32) + np.linspace(-0.2 * N, 0.2 * N, 8, dtype=np.float32)[:, None] * np.asarray([1.0, 0.5, 0.25], np.float32)
+        d = aim - org
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        if s["query"] == "project":
+            for mode, rs in ((1, False), (2, False), (3, False), (1, True), (2, True), (3, True)):
+                ren.project_rays(org, d, mode, range_skipping=rs)
+        elif s["query"] == "isosurface":
+            for rs in (False, True):
+                ren.isosurface_rays(org, d, range_skipping=rs)
+        elif s["query"] == "layers":
+            for rs in (False, True):
+                ren.isosurface_layer_rays(org, d, max_events=4, range_skipping=rs)
+        else:
+            ren.shadow_floats(aim, 0)
     ren.close()
     print(name, flush=True)
 

@@ -17,7 +17,8 @@ INF = float("inf")
 N, SIZE = 24, (96, 64)
 
 # name -> (environment, settings): dtype, shading, pipeline (1 in place, 2 pooled), skip, material, clip, spp, shard, sparse, lds, layout, projection (mode),
-# iso (isovalues of a [0, 1] field) with opacities, ortho, cache (the shadow cache: its build, then a cached frame), query (a known-answer entry, 8 rays)
+# iso (isovalues of a [0, 1] field) with opacities, ortho, cache (the shadow cache: its build, then a cached frame), query (a known-answer entry, 8 rays),
+# light, jitter (blue noise), convergence (mode, threshold), reconstruction (mode), frames (accumulated frames rendered: 1, two for a sparse state)
 STATES = [
     ("unshaded_f32_lds_staged", {}, dict(shading=0, lds=True)),
     ("unshaded_f32_plain", {}, dict(shading=0, lds=False)),
@@ -95,6 +96,21 @@ STATES += [
     ("query_shadow_floats", {}, dict(shading=2, pipeline=1, query="shadow")),
     ("query_shadow_floats_u8_addressing1", {"OVR_HIP_ADDRESSING": "1"}, dict(dtype="uint8", shading=2, pipeline=1, query="shadow")),
 ]
+# the frame-shaping setters tests/mode_walk.py walks that had no state here: light (direction and intensity; `material` above is the material alone), the
+# blue-noise jitter, the convergence modes (`frames` accumulated frames: the estimate runs on even frames, ADAPTIVE retires blocks behind frame 2) and the
+# reconstruction of a sparse frame
+STATES += [
+    ("other_light_inplace", {}, dict(shading=2, pipeline=1, light=True)),
+    ("other_light_pooled", {}, dict(shading=2, pipeline=2, light=True)),
+    ("isosurface_other_light", {}, dict(shading=2, iso=ISO, light=True)),
+    ("blue_noise_jitter", {}, dict(shading=2, pipeline=2, jitter=True)),
+    ("projection_blue_noise_jitter_spp2", {}, dict(shading=0, projection=1, jitter=True, spp=2)),
+    ("convergence_estimate", {}, dict(shading=2, pipeline=2, convergence=(1, 0.0), frames=2)),
+    ("convergence_adaptive", {}, dict(shading=2, pipeline=2, convergence=(2, 0.0), frames=4)),
+    ("translucent_convergence_adaptive", {}, dict(shading=2, convergence=(2, 0.0), frames=4, **LAYERS)),
+    ("sparse_reconstruction_fill", {}, dict(shading=2, pipeline=2, sparse=True, reconstruction=1)),
+    ("projection_sparse_reconstruction_fill", {}, dict(shading=0, projection=1, sparse=True, reconstruction=1)),
+]
 ENV_KEYS = ("OVR_HIP_ADDRESSING", "OVR_HIP_ROW_LOADS")
 
 
@@ -122,6 +138,15 @@ def run_state(ovr, np, name, env, s):
         ren.set_layout_choice(0)
     if s.get("material"):
         ren.set_material(0.3, 0.6, 0.4, 12.0)
+    if s.get("light"):
+        ren.set_light_direction((0.3, 0.8, -0.52), 1.5)
+    if s.get("jitter"):
+        ren.set_noise_tile(ovr.synth.make_noise_tile(16))
+        ren.set_pixel_jitter(1)
+    if "convergence" in s:
+        ren.set_convergence(*s["convergence"])
+    if "reconstruction" in s:
+        ren.set_reconstruction(s["reconstruction"])
     if s.get("sparse"):
         ren.set_noise_tile(ovr.synth.make_noise_tile(16))
         ren.set_focus((0.5, 0.45), 0.35, 0.15)
@@ -139,7 +164,7 @@ def run_state(ovr, np, name, env, s):
     if s.get("cache"):
         ren.set_shadow_cache(1)
     ren.commit()
-    for _ in range(2 if s.get("sparse") else 1):
+    for _ in range(s.get("frames", 2 if s.get("sparse") else 1)):
         ren.render()
     if "query" in s:  # 8 rays from the eye into the volume (the entries take the last frame's parameters)
         org = np.tile(np.asarray(eye, np.float32), (8, 1))

@@ -486,6 +486,41 @@ typedef struct ovr_hip_isosurface_layers {
 /* the COMMITTED state, not the queued one */
 int ovr_hip_get_isosurface_layers(const ovr_hip_renderer* r, ovr_hip_isosurface_layers* out);
 
+/* Ambient occlusion of the isosurface frames (added within ABI v11: new entry points and one new struct only).  While samples = K > 0 is
+ * committed, every event of an isosurface frame under OVR_HIP_SHADE_GRADIENT or OVR_HIP_SHADE_FULL casts K occlusion walks into the hemisphere that faces the
+ * viewer, and the event's ambient coefficient is scaled by what they find.  open-volume-renderer_amd/isosurface.py stays the normative text; float32 throughout.
+ *   table      D[m][j], m = 0 ... 15, j = 0 ... K - 1: local (x, y, z), z along the normal, cosine-weighted, a sunflower spiral turned sixteen times - in float64
+ *              on the host r2 = (j + 0.5) / K, phi = 2 pi (j g + m / 16) with g = 0.6180339887498949, (sqrt(r2) cos phi, sqrt(r2) sin phi, sqrt(1 - r2)), each
+ *              component rounded to float32.  ovr_hip_get_ambient_occlusion_directions hands the COMMITTED table back (16 x K x 3 floats).
+ *   rotation   sample k of frame frame_index (1-based) at pixel (x, y): m = ((x & 3) + 4 (y & 3) + (frame_index - 1) spp + k) & 15.
+ *   normal     N = n_w if dot(n_w, dir) <= 0 else -n_w (dir: the event's primary ray; a NaN normal stays NaN, its walks miss the box).
+ *   frame      s = copysign(1, N.z), a = -1 / (s + N.z), b = (N.x N.y) a, T = (1 + ((s N.x) N.x) a, s b, -(s N.x)), B = (b, s + (N.y N.y) a, -N.y).
+ *   ray j      d_c = fma(x, T_c, fma(y, B_c, z N_c)) per component, not renormalised.
+ *   walk       the translucent shadow walk with d_j in the light's place: (a0, a1, hit) from the (clipped) box test of pos* + t d_j from (0, FLT_MAX),
+ *              a1 = fmin(a1, distance), steps by the projection's recurrence from a0 + step; A_j = fma(1 - A_j, alpha_k, A_j) over its events until
+ *              A_j >= 0.9999f or its last step; the range-skipping rule is the shadow walk's; nothing is refined.
+ *   shade      S = A_0 + ... + A_{K-1} in that order, O = S / (float)K; the event's shade factor takes ambient = ka * (1 - O).  O = 0 gives today's bits.
+ *   counters   the AO walks' fetched steps are added to shadow_samples, their dropped steps to skipped_shadow_samples; everything else is unchanged.
+ * An opaque frame runs the translucent kernels' AO twins with its all-ones opacities (the identity above makes that the opaque frame apart from the ambient
+ * term).  March frames, projections and isosurface frames under OVR_HIP_SHADE_NONE never change: a committed K is kept and not used there.  samples in
+ * 0 ... OVR_HIP_MAX_AO_SAMPLES, 0 (the default) = off: until the setter is called with K > 0 every frame, counter and kernel is what it was.  distance in world
+ * units of t along a unit direction, finite and > 0, or +inf for the whole box; ignored (and stored as +inf) while samples == 0.  Recorded and applied like the
+ * isovalues; every call resets the accumulation.  EINVAL, the state kept: samples < 0 or > 16, and with samples > 0 a distance that is NaN or <= 0.  A device
+ * group forwards the call.  An occluder nearer than 1.5 steps to the event, or thinner than a step, is not seen: the shadow ray's caveat. */
+#define OVR_HIP_MAX_AO_SAMPLES 16
+#define OVR_HIP_AO_ROTATIONS 16
+int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance);
+typedef struct ovr_hip_ambient_occlusion {
+  int32_t samples;                             /* the COMMITTED K */
+  float distance;                              /* and radius (+inf: the whole box) */
+  int32_t rotations;                           /* OVR_HIP_AO_ROTATIONS */
+  int32_t active;                              /* 1: the next isosurface frame takes the AO kernels - K > 0, isovalues committed, shading GRADIENT or FULL */
+} ovr_hip_ambient_occlusion;
+/* the COMMITTED state, not the queued one */
+int ovr_hip_get_ambient_occlusion(const ovr_hip_renderer* r, ovr_hip_ambient_occlusion* out);
+/* the COMMITTED direction table as the host formed it: 16 x K x 3 floats, [m][j][x, y, z] (host memory).  EINVAL: a null pointer, a capacity below that */
+int ovr_hip_get_ambient_occlusion_directions(const ovr_hip_renderer* r, float* out, size_t capacity_floats);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -645,6 +680,14 @@ int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org_device, cons
  * in 1 ... 16.  Per ray 4 + 8 * max_events floats: (events composited, A, steps walked, shadow steps over all events), then per event e < min(events, max_events)
  * (k, t*, n_w.x, n_w.y, n_w.z, shadow, A after the event, 0); the rest zeros.  ESTATE without a volume or isovalues; EINVAL: a null pointer, n < 0, a bad max_events. */
 int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t max_events, int32_t range_skipping);
+/* an isosurface ray with ambient occlusion as the kernels evaluate it (added with the ambient occlusion): four lanes per ray through the device function the AO
+ * frame's kernel calls, under full shading, with the COMMITTED isovalues, opacities, AO samples and distance, light, sampling rate and clip box, every ray at the
+ * rotation `rotation` (0 ... 15) of the direction table.  max_events in 1 ... 16.  Per ray 8 + 8 * max_events floats: the layers entry's header (events composited,
+ * A, steps walked, shadow steps over all events) followed by (the AO walks' steps walked, the AO walks' fetched steps, 0, 0), then per event
+ * e < min(events, max_events) the layers entry's record with O in its last slot: (k, t*, n_w.x, n_w.y, n_w.z, shadow, A after the event, O); the rest zeros.
+ * ESTATE without a volume, isovalues or committed AO samples; EINVAL: a null pointer, n < 0, a bad max_events or rotation. */
+int ovr_hip_isosurface_ao_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t max_events, int32_t rotation,
+                                 int32_t range_skipping);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -155,6 +155,18 @@ class IsosurfaceLayers(C.Structure):
     ]
 
 
+MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
+
+
+class AmbientOcclusion(C.Structure):
+    _fields_ = [
+        ("samples", C.c_int32),
+        ("distance", C.c_float),
+        ("rotations", C.c_int32),
+        ("active", C.c_int32),
+    ]
+
+
 CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC = 0, 1
 
 
@@ -261,6 +273,10 @@ SYMBOLS = {
     "ovr_hip_set_isosurface_layers": (C.c_int, [_H, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurface_layers": (C.c_int, [_H, C.POINTER(IsosurfaceLayers)]),
     "ovr_hip_isosurface_layers_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "ovr_hip_set_ambient_occlusion": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "ovr_hip_get_ambient_occlusion": (C.c_int, [_H, C.POINTER(AmbientOcclusion)]),
+    "ovr_hip_get_ambient_occlusion_directions": (C.c_int, [_H, C.POINTER(C.c_float), C.c_size_t]),
+    "ovr_hip_isosurface_ao_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "ovr_hip_reconstruct_image": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "ovr_hip_update_volume": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ovr_hip_get_update_times": (C.c_int, [_H, C.POINTER(C.c_double)]),

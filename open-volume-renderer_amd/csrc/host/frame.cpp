@@ -297,6 +297,10 @@ void fill_isosurface_params(const ovr_hip_renderer* r, RayMarchParams& q)
   for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) q.iso_values[k] = k < p.n ? p.v[k] : 0.f;
   for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) q.iso_opacities[k] = k < p.n ? p.a[k] : 1.f;
   q.iso_translucent = p.translucent() ? 1 : 0;
+  const AoP& ao = r->ambient_occlusion.current; // (the known-answer entries and the lattice's build clear K: launch_*_floats, launch_shadow_cache)
+  q.ao_samples = r->d_ao_dirs ? ao.samples : 0;
+  q.ao_distance = ao.distance;
+  q.ao_dirs = r->d_ao_dirs;
 }
 // a frame drawn by one kernel in the march's place, from the general layout: a projection or the isosurfaces
 static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0; }

@@ -82,10 +82,13 @@ constexpr bool project_variant_exists(int mode, int am, bool skip, bool clipped,
 constexpr int kMaxIsovalues = 4; // include/ovr_hip.h OVR_HIP_MAX_ISOVALUES
 // translucent: every crossing composited with its isovalue's opacity - like the orthographic twins ON THE CLIPPED VARIANTS ALONE (a frame
 // without a clip box runs them with the unit box, whose bounds give the unclipped test's bits), for both cameras
-constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false, bool translucent = false)
+// ao (ambient occlusion): K hemisphere walks per event scale the ambient term - twins of the TRANSLUCENT kernels alone (an opaque frame runs
+// them with its all-ones opacities, section 19's identity), under a shading mode that has an ambient term
+constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false, bool translucent = false, bool ao = false)
 {
   (void)skip; // both walks and both box tests exist for every variant, the orthographic camera on the clipped test
   if ((orthographic || translucent) && !clipped) return false;
+  if (ao && !(translucent && shade >= 1)) return false;
   return shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
 }
 
@@ -140,6 +143,7 @@ struct LaunchFacts {
   bool orthographic = false;          // the committed camera is orthographic (ovr_hip_set_camera_orthographic): the frame takes the orthographic twins of the clipped variants
   int isosurfaces = 0;                // the number of committed isovalues; > 0: an isosurface frame - `projection` is kept but not drawn, pool, majorants and LDS staging are not read
   bool translucent = false;           // one of the committed isovalues' opacities is below 1 (ovr_hip_set_isosurface_layers): an isosurface frame takes the translucent twins
+  bool ambient_occlusion = false;     // ambient-occlusion samples are committed (ovr_hip_set_ambient_occlusion, K > 0): a shaded isosurface frame takes the AO twins
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -162,6 +166,7 @@ struct LaunchPlan {
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
   bool error = false;                 // the frame cannot be launched (hipErrorInvalidValue)
+  bool ambient_occlusion = false;     // an isosurface frame's kernel is the AO twin of the translucent one (isosurface.translucent and isosurface.clipped are set)
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -219,11 +224,14 @@ inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o
   LaunchPlan pl;
   const Addressing a = plan_addressing(f, o);
   if (a.error || f.isosurfaces < 1 || f.isosurfaces > kMaxIsovalues || f.quad) { pl.error = true; return pl; }
-  const WalkFrame w = plan_walk_frame(pl, f, a.am, f.translucent);
-  pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  const int shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
+  const bool ao = f.ambient_occlusion && shading >= 1; // without an ambient term on the surface the committed samples are kept and not used
+  const WalkFrame w = plan_walk_frame(pl, f, a.am, f.translucent || ao);
+  pl.shading = shading;
   pl.isosurface.on = true;
   pl.isosurface.skip = f.ranges;
-  pl.isosurface.translucent = f.translucent;
+  pl.isosurface.translucent = f.translucent || ao; // the AO twins are the translucent path's: an opaque frame runs it with its all-ones opacities
+  pl.ambient_occlusion = ao;
   pl.isosurface.clipped = w.clipped;
   pl.isosurface.lds_bytes = w.lds_bytes;
   return pl;
@@ -280,7 +288,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
-  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent);
+  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion);
   if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
                               pl.cached && !pl.pooled, pl.orthographic) &&
@@ -297,5 +305,8 @@ static_assert(project_variant_exists(kProjectMaximum, 0, true, true, true) && !p
               "the orthographic projection and isosurface kernels: on the clipped variants alone");
 static_assert(isosurface_variant_exists(2, 0, true, true, false, true) && isosurface_variant_exists(0, 4, false, true, true, true) && !isosurface_variant_exists(2, 0, true, false, false, true),
               "the translucent isosurface kernels: on the clipped variants alone, for both cameras");
+static_assert(isosurface_variant_exists(1, 0, false, true, false, true, true) && isosurface_variant_exists(2, 4, true, true, true, true, true) && !isosurface_variant_exists(0, 0, false, true, false, true, true)
+                && !isosurface_variant_exists(2, 0, false, true, false, false, true) && !isosurface_variant_exists(2, 0, false, false, false, true, true),
+              "the ambient-occlusion isosurface kernels: twins of the translucent ones, under a shading mode with an ambient term");
 
 } // namespace ovrhip

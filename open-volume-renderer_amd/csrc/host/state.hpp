@@ -75,6 +75,8 @@ struct IsoP {
   float a[OVR_HIP_MAX_ISOVALUES] = { 1.f, 1.f, 1.f, 1.f };
   bool translucent() const { for (int k = 0; k < n; ++k) if (a[k] < 1.f) return true; return false; }
 };
+// ovr_hip_set_ambient_occlusion: K and the radius (+inf while K == 0: the radius is not read then)
+struct AoP { int samples = 0; float distance = INFINITY; };
 // ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
 // and the 0.5 / 0.5 of its shade expression (shaders_raymarching.cu:138,156-157)
 struct LightP { float dir[3] = { -907.108f, 2205.875f, -400.0267f }; float intensity = 1.f; };
@@ -215,6 +217,9 @@ struct ovr_hip_renderer {
   bool projection_skipped = false; // the last projection frame ran the range-skipping kernel (ovr_hip_get_projection)
   Queued<ovrhip::host::IsoP> isosurfaces; // ovr_hip_set_isosurfaces: sorted ascending; recorded under kShading like the projection mode.  n > 0: isosurface frames
   bool isosurface_skipped = false; // the last isosurface frame ran the range-skipping kernel (ovr_hip_get_isosurfaces)
+  Queued<ovrhip::host::AoP> ambient_occlusion; // ovr_hip_set_ambient_occlusion; recorded under kShading like the isovalues
+  std::vector<float> ao_table;     // the direction table of the committed K, [16][K][3], as uploaded to d_ao_dirs (both follow K at commit)
+  float* d_ao_dirs = nullptr;
   Queued<float> rate;
   Queued<ovrhip::host::ShardP> shard;
   Queued<ovrhip::host::LightP> light;        // the raw vector: normalised when it is applied (unit_light)

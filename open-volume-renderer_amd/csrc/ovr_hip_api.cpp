@@ -109,6 +109,7 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->ev_tf) (void)hipEventDestroy(r->ev_tf);
   if (r->d_noise) (void)hipFree(r->d_noise);
   if (r->d_mc_minmax) (void)hipFree(r->d_mc_minmax);
+  if (r->d_ao_dirs) (void)hipFree(r->d_ao_dirs);
   if (r->d_mc_majorant) (void)hipFree(r->d_mc_majorant);
   if (r->d_mc_occupancy) (void)hipFree(r->d_mc_occupancy);
   if (r->d_mc_fine) (void)hipFree(r->d_mc_fine);
@@ -342,6 +343,39 @@ int ovr_hip_get_isosurfaces(const ovr_hip_renderer* r, ovr_hip_isosurfaces* out)
   out->n = p.n;
   for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) out->isovalues[k] = k < p.n ? p.v[k] : 0.f;
   out->range_skipping = r->isosurface_skipped ? 1 : 0;
+  return 0;
+}
+
+int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (samples < 0 || samples > OVR_HIP_MAX_AO_SAMPLES) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_ambient_occlusion: between 0 and 16 samples");
+  if (samples > 0 && !(distance > 0.f)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_ambient_occlusion: the distance must be positive (+inf: the whole box)");
+  AoP p;
+  p.samples = samples;
+  p.distance = samples > 0 ? distance : INFINITY; // (not read while K == 0)
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->ambient_occlusion.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_ambient_occlusion(m, samples, distance));
+  return 0;
+}
+
+int ovr_hip_get_ambient_occlusion(const ovr_hip_renderer* r, ovr_hip_ambient_occlusion* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_ambient_occlusion: null argument");
+  const AoP& p = r->ambient_occlusion.current;
+  out->samples = p.samples;
+  out->distance = p.distance;
+  out->rotations = OVR_HIP_AO_ROTATIONS;
+  out->active = p.samples > 0 && r->isosurfaces.current.n > 0 && r->shading.current != OVR_HIP_SHADE_NONE ? 1 : 0;
+  return 0;
+}
+
+int ovr_hip_get_ambient_occlusion_directions(const ovr_hip_renderer* r, float* out, size_t capacity_floats)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_ambient_occlusion_directions: null argument");
+  if (capacity_floats < r->ao_table.size()) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_ambient_occlusion_directions: the buffer holds fewer than 16 x K x 3 floats");
+  std::copy(r->ao_table.begin(), r->ao_table.end(), out);
   return 0;
 }
 
@@ -659,6 +693,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (!(a->rate.current == b->rate.current)) return false;
   if (a->shading.current != b->shading.current || a->projection.current != b->projection.current) return false;
   if (!same_bytes(a->isosurfaces.current, b->isosurfaces.current)) return false;
+  if (!same_bytes(a->ambient_occlusion.current, b->ambient_occlusion.current)) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -719,6 +754,23 @@ bool consume(commit::Changes& ch, commit::Source s, Queued<TfnP>& q)
   return true;
 }
 
+// the direction table of K ambient-occlusion samples (include/ovr_hip.h): formed in float64, each component rounded to float32; on the device behind it
+int upload_ao_table(ovr_hip_renderer* r, int K)
+{
+  const double g = 0.6180339887498949, pi = 3.141592653589793;
+  r->ao_table.assign((size_t)OVR_HIP_AO_ROTATIONS * (size_t)K * 3, 0.f);
+  for (int m = 0; m < OVR_HIP_AO_ROTATIONS; ++m)
+    for (int j = 0; j < K; ++j) {
+      const double r2 = ((double)j + 0.5) / (double)K, phi = 2.0 * pi * ((double)j * g + (double)m / 16.0);
+      float* d = &r->ao_table[((size_t)m * K + j) * 3];
+      d[0] = (float)(std::sqrt(r2) * std::cos(phi)); d[1] = (float)(std::sqrt(r2) * std::sin(phi)); d[2] = (float)std::sqrt(1.0 - r2);
+    }
+  if (K == 0) return 0; // (no frame reads the table: the buffer, if any, is kept for the next K)
+  if (!r->d_ao_dirs) HIP_TRY(hipMalloc((void**)&r->d_ao_dirs, (size_t)OVR_HIP_AO_ROTATIONS * OVR_HIP_MAX_AO_SAMPLES * 3 * sizeof(float)));
+  HIP_TRY(hipMemcpy(r->d_ao_dirs, r->ao_table.data(), r->ao_table.size() * sizeof(float), hipMemcpyHostToDevice)); // (a commit has finished the frame: nothing reads it)
+  return 0;
+}
+
 // the first part of a commit: every queued value, in today's order, with the steps that can fail (or touch the device) where the value is consumed
 int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
 {
@@ -736,12 +788,16 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
   consume(ch, kSparse, r->sparse);         // :180-183
   consume(ch, kAccumulation, r->accumulate); // :185-188
   consume(ch, kSamplingRate, r->rate);     // :190-196
-  { // the projection mode and the isovalues are recorded with the shading mode: set if any of the setters was called, differs if any value differs
+  { // the projection mode, the isovalues and the AO state are recorded with the shading mode: set if any of the setters was called, differs if any value differs
     const int shading = r->shading.current, projection = r->projection.current;
     const IsoP iso = r->isosurfaces.current;
-    const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update();
-    ch.note(kShading, set_s || set_p || set_i,
-            shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0);
+    const AoP ao = r->ambient_occlusion.current;
+    const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update(), set_a = r->ambient_occlusion.update();
+    ch.note(kShading, set_s || set_p || set_i || set_a,
+            shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0 ||
+              std::memcmp(&ao, &r->ambient_occlusion.current, sizeof(AoP)) != 0);
+    if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
+      if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
   }
   consume(ch, kJitter, r->jitter);
   {
@@ -1335,6 +1391,25 @@ int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org, cons
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_isosurface_layers_floats(q, org, dir, out, n, max_events, range_skipping != 0, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_isosurface_ao_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events, int32_t rotation, int32_t range_skipping)
+{
+  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16 || rotation < 0 || rotation >= OVR_HIP_AO_ROTATIONS)
+    return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_ao_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no volume was set");
+  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no isovalue is committed (ovr_hip_set_isosurface_layers)");
+  if (r->ambient_occlusion.current.samples < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no ambient-occlusion sample is committed (ovr_hip_set_ambient_occlusion)");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
+  fill_isosurface_params(r, q);
+  q.mc_ranges = projection_ranges(r);
+  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: the resident volume has no macrocell ranges");
+  HIP_TRY(launch_isosurface_ao_floats(q, org, dir, out, n, max_events, rotation, range_skipping != 0, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

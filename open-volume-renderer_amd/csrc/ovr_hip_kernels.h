@@ -272,6 +272,12 @@ struct RayMarchParams {
   // ones is below 1 and the host launches the translucent twins, the only kernels that read the opacities.  Behind everything else, like the camera's kind
   float iso_opacities[4];
   int iso_translucent;
+  // ambient occlusion (ovr_hip_set_ambient_occlusion): ao_samples = K > 0 = a shaded isosurface frame is the AO twins', which cast K walks
+  // of at most ao_distance (world units of t; +inf: the whole box) per event along the directions ao_dirs[(16 rotations)][K][3] (device memory; local coordinates,
+  // z along the facing normal).  Behind everything else, the pointer last: no other kernel reads them
+  int ao_samples;
+  float ao_distance;
+  const float* ao_dirs;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -331,6 +337,11 @@ hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, c
 // walked, shadow steps), then (k, t*, the world normal, shadow, A after the event, 0) per event, the rest zeros - with p.iso_opacities, whatever p.iso_translucent says
 hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int range_skipping,
                                            hipStream_t stream);
+// the ambient-occlusion twin (isosurface_layers_ao in ovr_hip_isosurface_ao.h, the function the AO frame's kernel calls, with full shading): 8 + 8 max_events floats
+// per ray - (events composited, A, steps walked, shadow steps, the AO walks' steps, the AO walks' fetched steps, 0, 0), then (k, t*, the world normal, shadow, A
+// after the event, O) per event, the rest zeros - with p.ao_samples / p.ao_distance / p.ao_dirs and every ray at the table's rotation `rotation` (0 ... 15)
+hipError_t launch_isosurface_ao_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int rotation, int range_skipping,
+                                       hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

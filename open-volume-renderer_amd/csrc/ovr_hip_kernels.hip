@@ -15,6 +15,7 @@
 // composites in ray order (pooled pipeline), or that the tile's own wave shades (in-place pipeline).  The transfer
 // function (colour float4 table + alpha table, 20 KiB at the shipped resolution of 1024), the per-axis brick-offset tables,
 #include "ovr_hip_device.h"
+#include "ovr_hip_isosurface_ao.h"
 #include "ovr_hip_update.h"
 
 namespace ovrhip {
@@ -1016,6 +1017,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.projection = p.projection; f.ranges = p.mc_ranges != nullptr;
   f.isosurfaces = p.iso_n;
   f.translucent = p.iso_n > 0 && p.iso_translucent != 0;
+  f.ambient_occlusion = p.iso_n > 0 && p.ao_samples > 0;
   f.orthographic = p.cam_orthographic != 0;
   return plan_launch(f, o);
 }
@@ -1071,8 +1073,11 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template ProjectKernels project_kernels_of<E>(const LaunchPlan&);                    \
   extern template IsosurfaceKernels isosurface_kernels_of<E, false>(const LaunchPlan&);       \
   extern template IsosurfaceLayersKernels isosurface_kernels_of<E, true>(const LaunchPlan&);
+#define OVR_X_AO(E, NAME, BASE, LAYOUT) extern template IsosurfaceAoKernels isosurface_ao_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
+OVR_VOXEL_TYPES(OVR_X_AO)
 #undef OVR_X
+#undef OVR_X_AO
 
 // a plan's kernels for the volume's voxel type: the frame's two - a projection's or an isosurface's kernel in the in-place march's place (such a plan is neither
 // pooled nor LDS-staged, march_lds_bytes is that kernel's) - and the known-answer entry's of such a plan.  All nullptr: the plan is an error, or no such variant
@@ -1081,12 +1086,17 @@ struct PlanKernels {
   ProjectFloatsKernel project_floats = nullptr;
   IsosurfaceFloatsKernel isosurface_floats = nullptr;
   IsosurfaceLayersFloatsKernel isosurface_layers_floats = nullptr;
+  IsosurfaceAoFloatsKernel isosurface_ao_floats = nullptr;
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   PlanKernels k;
   if (plan.error) return k;
-  if (plan.isosurface.on && plan.isosurface.translucent)
+  if (plan.isosurface.on && plan.ambient_occlusion) {
+    if (p.ao_dirs && p.ao_samples > 0 && p.ao_samples <= kAoMaxSamples) // (the AO kernels read the direction table: no table, no kernel)
+      dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_ao_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_ao_floats = v.floats; });
+  }
+  else if (plan.isosurface.on && plan.isosurface.translucent)
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, true>(plan); k.frame.march = v.frame; k.isosurface_layers_floats = v.floats; });
   else if (plan.isosurface.on)
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, false>(plan); k.frame.march = v.frame; k.isosurface_floats = v.floats; });
@@ -2065,7 +2075,7 @@ hipError_t launch_shadow_cache(const RayMarchParams& p, const ShadowBuildArgs& a
   if (!a.out && !(a.pos_out && !a.pos)) return hipErrorInvalidValue; // nothing to write: out, or the nodes' positions alone
   RayMarchParams q = query_params(p, true);
   q.shading = 0; q.shadow_lattice = nullptr;
-  q.iso_n = 0; // (p may be a frame's parameters: the plan asked here is the march's, whatever the last frame drew)
+  q.iso_n = 0; q.ao_samples = 0; // (p may be a frame's parameters: the plan asked here is the march's, whatever the last frame drew)
   const LaunchPlan pl = plan_raymarch(q);
   if (pl.error) return hipErrorInvalidValue;
   ShadowCacheKernel kern = nullptr;
@@ -2107,7 +2117,7 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
   if (n <= 0) return hipSuccess;
   if (range_skipping && !p.mc_ranges) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, range_skipping != 0);
-  q.projection = mode; q.iso_n = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
+  q.projection = mode; q.iso_n = 0; q.ao_samples = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
   const LaunchPlan pl = plan_raymarch(q);
   const ProjectFloatsKernel kern = plan_kernels(q, pl).project_floats;
   const unsigned int blocks = quad_ray_blocks(n);
@@ -2121,7 +2131,7 @@ hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, c
   if (n <= 0) return hipSuccess;
   if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, range_skipping != 0);
-  q.iso_translucent = 0; // (the first crossing, opaque, whatever opacities are committed)
+  q.iso_translucent = 0; q.ao_samples = 0; // (the first crossing, opaque, whatever opacities and AO samples are committed)
   const LaunchPlan pl = plan_raymarch(q);
   const IsosurfaceFloatsKernel kern = plan_kernels(q, pl).isosurface_floats;
   const unsigned int blocks = quad_ray_blocks(n);
@@ -2137,13 +2147,32 @@ hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float*
   if (n <= 0) return hipSuccess;
   if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, range_skipping != 0);
-  q.iso_translucent = 1;
+  q.iso_translucent = 1; q.ao_samples = 0; // (without ambient occlusion, whatever is committed)
   const LaunchPlan pl = plan_raymarch(q);
   const IsosurfaceLayersFloatsKernel kern = plan_kernels(q, pl).isosurface_layers_floats;
   const unsigned int blocks = quad_ray_blocks(n);
   if (!kern || !blocks) return hipErrorInvalidValue;
   if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(4 + 8 * max_events) * sizeof(float), stream)) return e;
   return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
+}
+
+// known-answer entry of the ambient occlusion: the AO twin of the kernel above with full shading, every ray at the rotation `rotation` of the direction table.
+// out is zeroed first
+hipError_t launch_isosurface_ao_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int rotation, int range_skipping,
+                                       hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16 || rotation < 0 || rotation >= kAoRotations ||
+      p.ao_samples < 1 || p.ao_samples > kAoMaxSamples || !p.ao_dirs)
+    return hipErrorInvalidValue;
+  RayMarchParams q = query_params(p, range_skipping != 0);
+  q.iso_translucent = 1; q.shading = 2;
+  const LaunchPlan pl = plan_raymarch(q);
+  const IsosurfaceAoFloatsKernel kern = plan_kernels(q, pl).isosurface_ao_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(8 + 8 * max_events) * sizeof(float), stream)) return e;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events, rotation);
 }
 
 // known-answer entry of the box test: the object-space ray as the march forms it (to_object of the origin, the direction scaled by inv_scale, not

@@ -39,6 +39,24 @@ Shadow     today's shadow ray and steps; A_s = fma(1 - A_s, alpha_k, A_s) over i
 Counters   steps walked count once however many events they hold; shaded_samples = events composited; the shadow counters sum the shadow walks of all events.
 With every alpha_k = 1 the first event gives C = c, A = 1 and the shadow 1.0f: the opaque text above, bit for bit.
 
+Ambient occlusion (ovr_hip_set_ambient_occlusion(K, R)): under GRADIENT / FULL every event casts K occlusion walks into the hemisphere that
+faces the viewer; K in 0 ... 16, R > 0 in world units of t (inf: the whole box).  K = 0: the text above.
+Table      D[m][j], m = 0 ... 15, j = 0 ... K - 1 (`ao_directions`): in float64 r2 = (j + 0.5) / K, phi = 2 pi (j g + m / 16), g = 0.6180339887498949,
+           (sqrt(r2) cos phi, sqrt(r2) sin phi, sqrt(1 - r2)), each component rounded to float32: cosine-weighted, z along the normal, sixteen rotations.
+Rotation   sample k of frame frame_index (1-based) at pixel (x, y): m = ((x & 3) + 4 (y & 3) + (frame_index - 1) spp + k) & 15 (`ao_rotation`).
+Normal     N = n_w if lighting.dot(n_w, dir) <= 0 else -n_w, dir the event's primary ray (a NaN normal stays NaN; its walks miss the box: O = 0).
+Frame      Duff et al.'s basis, every operation on its own: s = copysign(1, N.z), a = -1 / (s + N.z), b = (N.x N.y) a,
+           T = (1 + ((s N.x) N.x) a, s b, -(s N.x)), B = (b, s + (N.y N.y) a, -N.y).
+Ray j      d_c = fma(x, T_c, fma(y, B_c, z N_c)) per component with (x, y, z) = D[m][j]; not renormalised.
+Walk       the translucent shadow walk with d_j in the light's place: (a0, a1, hit) from the (clipped) box test of pos* + t d_j from (0, FLT_MAX), a1 = fmin(a1, R),
+           steps from a0 + step, A_j = fma(1 - A_j, alpha_k, A_j) over its events until A_j >= 0.9999f or its last step; skipping as the shadow walk; nothing refined.
+Shade      S = A_0 + ... + A_{K-1} in that order, O = S / (float)K; the event's shade factor is lighting.shade with ambient = ka * (1 - O).  O = 0: ka, today's bits.
+Opaque     a frame without opacities runs this text with all-ones opacities (the identity above: the opaque frame apart from the ambient term).
+Counters   the AO walks' steps are reported apart (ao_steps, ao_fetched); the product adds their fetched steps to shadow_samples and the dropped ones to
+           skipped_shadow_samples.
+This issue left open, fixed here: the operation order of the basis (above); a direction d_j for which the box test fails contributes A_j = 0; under NONE nothing
+is cast; the known-answer entry casts under full shading whatever mode is committed.
+
 The 8-bit voxel types: the product filters the stored integers and normalises once behind the filter (s = filter(raw) * (1 / 255)), the exact-parity build and
 projection.sample normalise voxel by voxel.  `product_sampler` restates the former, so that hit, isovalue, t* and the steps walked of the product are this model's
 bits too."""
@@ -54,6 +72,56 @@ MAX_ISOVALUES = 4
 NONE, GRADIENT, FULL = 0, 1, 2
 C = (F(0.2), F(0.4), F(0.6), F(0.8))
 SATURATED = F(0.9999)   # the march's early-termination bound (oracle/ovr_oracle.c:608-615): a translucent ray ends behind the event that reaches it
+
+
+MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
+GOLDEN = 0.6180339887498949
+
+
+def ao_directions(K):
+    """the direction table D[m][j] -> (16, K, 3) float32: formed in float64, each component rounded once"""
+    K = int(K)
+    if K < 0 or K > MAX_AO_SAMPLES:
+        raise ValueError("between 0 and 16 ambient-occlusion samples")
+    j = np.arange(K, dtype=np.float64)[None, :]
+    m = np.arange(AO_ROTATIONS, dtype=np.float64)[:, None]
+    r2 = np.broadcast_to((j + 0.5) / K if K else j, (AO_ROTATIONS, K))
+    phi = 2.0 * np.pi * (j * GOLDEN + m / 16.0)
+    return np.stack([np.sqrt(r2) * np.cos(phi), np.sqrt(r2) * np.sin(phi), np.sqrt(1.0 - r2)], -1).astype(F)
+
+
+def ao_rotation(x, y, frame_index, spp, k):
+    """the table's rotation for sample k of frame frame_index (1-based) at the pixels (x, y): integers only"""
+    return ((np.asarray(x, np.int64) & 3) + 4 * (np.asarray(y, np.int64) & 3) + (int(frame_index) - 1) * int(spp) + int(k)) & 15
+
+
+def ao_facing(n_w, direction):
+    """the normal that faces the viewer: n_w where dot(n_w, dir) <= 0, else -n_w (NaN stays NaN)"""
+    n_w = np.asarray(n_w, F)
+    with np.errstate(invalid="ignore", over="ignore"):
+        front = lighting.dot(n_w, np.asarray(direction, F)) <= 0
+    return np.where(front[..., None], n_w, -n_w).astype(F)
+
+
+def ao_basis(N):
+    """Duff et al.'s branch-free orthonormal basis around N (n, 3) -> T, B (n, 3), every operation rounding on its own"""
+    N = np.asarray(N, F)
+    x, y, z = N[..., 0], N[..., 1], N[..., 2]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        s = np.copysign(F(1), z).astype(F)
+        a = (F(-1) / (s + z).astype(F)).astype(F)
+        b = ((x * y).astype(F) * a).astype(F)
+        sx = (s * x).astype(F)
+        T = np.stack([(F(1) + ((sx * x).astype(F) * a).astype(F)).astype(F), (s * b).astype(F), -sx], -1)
+        B = np.stack([b, (s + ((y * y).astype(F) * a).astype(F)).astype(F), -y], -1)
+    return T.astype(F), B.astype(F)
+
+
+def ao_ray(local, N, T, B):
+    """d_c = fma(x, T_c, fma(y, B_c, z N_c)) for the local directions (n, 3)"""
+    local = np.asarray(local, F)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return fma(local[:, 0:1], T, fma(local[:, 1:2], B, (local[:, 2:3] * N).astype(F)))
 
 
 def isovalues(values):
@@ -197,17 +265,21 @@ def normals(tap_object, po, s, dims, inv_scale, vertex_centred=False):
 
 
 def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, shadows=True, light=None,
-               sampler=None, camera_kind=0, opacities=None):
+               sampler=None, camera_kind=0, opacities=None, ao=None):
     """world rays org, direction (n, 3) - the direction used as given - -> what ovr_hip_isosurface_floats returns per ray, and the counters' parts:
     dict(hit, iso, t, steps, normal (n, 3), shadow, fetched, pos (n, 3), shadow_steps, shadow_fetched, tm_before, tm_at, k); zeros for a ray without a hit.
     light: the raw vector towards the light (normalised here as the host does); sampler(po) replaces projection.sample (product_sampler);
     camera_kind = camera.ORTHOGRAPHIC: the rays are that camera's primary rays (camera.hits: a ray outside an ignored slab misses; shadow rays are untouched).
     opacities (one per isovalue as given): the translucent walk - the keys above describe the ray's FIRST event (steps, fetched: the whole walk; shadow_steps,
     shadow_fetched: the shadow walks of all events), and A (n,), n_events (n,), events (per ray a list of dict(i - the step -, k, t, normal, shadow, A - after the
-    event)) and flat (the events of all rays in order: ray, i, k, iso, alpha, t, pos, normal, shadow, A, tm_before, tm_at) are added"""
+    event)) and flat (the events of all rays in order: ray, i, k, iso, alpha, t, pos, normal, shadow, A, tm_before, tm_at) are added.
+    ao = (table (16, K, 3) - ao_directions(K) or the host's -, R, rotation (n,) - the table's rotation per ray): ambient occlusion (without opacities: all ones) -
+    flat and the events gain O, the ray ao_steps and ao_fetched (the AO walks of all its events)"""
     vol = np.asarray(volume)
     nz, ny, nx = vol.shape
     dims = (nx, ny, nz)
+    if ao is not None and opacities is None:
+        opacities = np.ones(np.asarray(iso).size, F)
     alpha = None if opacities is None else opacities_of(opacities, iso)
     iso = isovalues(iso)
     org, direction = np.asarray(org, F).reshape(-1, 3), np.asarray(direction, F).reshape(-1, 3)
@@ -240,7 +312,7 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
         tm = np.zeros((n, 1), F)
     s, w = first_crossing(org, direction, tm, count)
     if alpha is not None:
-        return _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light)
+        return _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light, ao)
     hit, r = w["hit"], np.arange(n)
     i = w["i"]
     ta, tb, sa, sb = tm[r, np.maximum(i - 1, 0)], tm[r, i], s[r, np.maximum(i - 1, 0)], s[r, i]
@@ -277,7 +349,7 @@ def trace_rays(volume, org, direction, rate, iso, spacing=(1, 1, 1), origin=(0, 
     return out
 
 
-def _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light):
+def _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp, dims, vertex_centred, lo, hi, step, first_crossing, shadows, light, ao=None):
     """trace_rays behind the translucent walk w: every event refined, shaded and shadowed as the opaque hit is"""
     n = len(org)
     ev = [(r, i, k, A) for r, row in enumerate(w["events"]) for (i, k, A) in row]
@@ -311,6 +383,27 @@ def _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp
             _, sw = first_crossing(pos, Ld, stm, scount)
             flat["shadow"] = np.array([row[-1][2] if row else F(0) for row in sw["events"]], F)
             shadow_steps, shadow_fetched = np.where(sbox, sw["walked"], 0), np.where(sbox, sw["fetched"], 0)
+    ao_steps, ao_fetched = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    if ao is not None:
+        flat["O"] = np.zeros(m, F)
+    if m and ao is not None:
+        table, R, rot = np.asarray(ao[0], F), F(ao[1]), np.asarray(ao[2], np.int64).ravel()
+        K = table.shape[1]
+        N = ao_facing(flat["normal"], dh)
+        T, B = ao_basis(N)
+        local = table[rot[er] & 15]   # (m, K, 3)
+        S = np.zeros(m, F)
+        for j in range(K):
+            d = ao_ray(local[:, j], N, T, B)
+            a0, a1, abox = clipping.world_intervals(pos, d, inv, wp, lo, hi)
+            atm, acount = steps((a0 + step).astype(F), fmin(a1, R), step, abox)
+            if atm.shape[1] == 0:
+                atm = np.zeros((m, 1), F)
+            _, aw = first_crossing(pos, np.where(abox[:, None], d, F(0)).astype(F), atm, acount)   # (a ray that misses the box has no step: its direction is not read)
+            S = (S + np.array([row[-1][2] if row else F(0) for row in aw["events"]], F)).astype(F)
+            ao_steps += np.where(abox, aw["walked"], 0)
+            ao_fetched += np.where(abox, aw["fetched"], 0)
+        flat["O"] = (S / F(K)).astype(F)
     first = np.concatenate([[0], np.cumsum(n_events)[:-1]]).astype(np.int64)   # a ray's first event in the flat order
     hit = n_events > 0
     f = first[hit]
@@ -322,10 +415,14 @@ def _trace_layers(org, direction, tm, s, w, box, iso, alpha, tap_object, inv, wp
     out["tm_before"][hit], out["tm_at"][hit] = tm[er[f], ei[f] - 1], tm[er[f], ei[f]]
     np.add.at(out["shadow_steps"], er, shadow_steps)
     np.add.at(out["shadow_fetched"], er, shadow_fetched)
+    if ao is not None:
+        out["ao_steps"], out["ao_fetched"] = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        np.add.at(out["ao_steps"], er, ao_steps)
+        np.add.at(out["ao_fetched"], er, ao_fetched)
     last = first + n_events - 1
     out["A"][hit] = eA[last[hit]]
-    out["events"] = [[dict(i=int(ei[j]), k=int(ek[j]), t=flat["t"][j], normal=flat["normal"][j], shadow=flat["shadow"][j], A=eA[j]) for j in range(first[r], first[r] + n_events[r])]
-                     for r in range(n)]
+    out["events"] = [[dict(i=int(ei[j]), k=int(ek[j]), t=flat["t"][j], normal=flat["normal"][j], shadow=flat["shadow"][j], A=eA[j], **({} if ao is None else dict(O=flat["O"][j])))
+                      for j in range(first[r], first[r] + n_events[r])] for r in range(n)]
     return out
 
 
@@ -346,15 +443,21 @@ def composite(flat, rgb, n):
 
 
 def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=None, intensity=1.0, material=lighting.REFERENCE_MATERIAL, spacing=(1, 1, 1),
-          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None, camera_kind=0, opacities=None):
+          origin=(0, 0, 0), vertex_centred=False, clip=None, skipping=False, spp=1, noise=None, frame_index=1, sampler=None, camera_kind=0, opacities=None, ao=None):
     """one isosurface frame: rgba (H, W, 4), layer (H, W, 3) and counters (opacities: the translucent frame - `hits` counts the events composited).  basis = (pos, dir, hor, ver); tf_range in the samples' units
     (projection.normalized_range); noise = the blue-noise tile switches that jitter on - without it spp must be 1, as in projection.frame;
-    camera_kind = camera.ORTHOGRAPHIC: the basis is an orthographic camera's - rays from camera.pixel_rays, the view vector -dir (the default: today's frame)"""
+    camera_kind = camera.ORTHOGRAPHIC: the basis is an orthographic camera's - rays from camera.pixel_rays, the view vector -dir (the default: today's frame);
+    ao = (table (16, K, 3), R): ambient occlusion under GRADIENT / FULL (K = 0 or NONE: not cast) - the counters' ao_steps / ao_fetched are its walks' steps"""
     w, h = size
     if noise is None and spp != 1:
         raise ValueError("without the blue-noise jitter the model forms the rays of one sample per pixel")
     rgba, layer = np.zeros((h * w, 4), F), np.zeros((h * w, 3), F)
-    counters = dict(rays=0, active_pixels=h * w, steps=0, fetched=0, hits=0, shadow_steps=0, shadow_fetched=0)
+    counters = dict(rays=0, active_pixels=h * w, steps=0, fetched=0, hits=0, shadow_steps=0, shadow_fetched=0, ao_steps=0, ao_fetched=0)
+    if ao is not None and (shading == NONE or np.asarray(ao[0]).shape[1] == 0):
+        ao = None
+    if ao is not None and opacities is None:
+        opacities = np.ones(np.asarray(iso).size, F)   # the opaque frame through the translucent text
+    py, px = np.mgrid[0:h, 0:w]
     org = np.broadcast_to(np.asarray(basis[0], F), (h * w, 3))
     raw_light = lighting.LITERAL_LIGHT if light is None else light
     L = lighting.normalize(np.asarray(raw_light, F))
@@ -367,12 +470,14 @@ def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=
             from . import camera
             org, d = (a.reshape(-1, 3) for a in camera.pixel_rays(basis, w, h, xi, camera_kind))
             view = camera.view_vector(basis) if camera_kind == camera.ORTHOGRAPHIC else None
-        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler, camera_kind, opacities)
+        rays_ao = None if ao is None else (ao[0], ao[1], ao_rotation(px, py, frame_index, spp, k).ravel())
+        r = trace_rays(volume, org, d, rate, iso, spacing, origin, vertex_centred, clip, skipping, shading == FULL, raw_light, sampler, camera_kind, opacities, rays_ao)
         m = r["hit"]
         e = r if opacities is None else r["flat"]   # what is coloured and shaded: the hit, or every event
         rgb = classify(e["iso"], colors, np.zeros(2, F), *tf_range)[:, :3]
         if shading != NONE:
-            f = lighting.shade(e["normal"], e["pos"], e["shadow"], L, basis[0], ka, kd, ks, shin, intensity, view=view)
+            amb = ka if ao is None else (F(ka) * (F(1) - e["O"]).astype(F)).astype(F)
+            f = lighting.shade(e["normal"], e["pos"], e["shadow"], L, basis[0], amb, kd, ks, shin, intensity, view=view)
             with np.errstate(invalid="ignore", over="ignore"):
                 rgb = clamp01((rgb * f[:, None]).astype(F))
         if opacities is None:
@@ -389,5 +494,8 @@ def frame(volume, basis, size, rate, iso, colors, tf_range, shading=FULL, light=
         counters["hits"] += int(m.sum()) if opacities is None else len(e["ray"])
         counters["shadow_steps"] += int(r["shadow_steps"].sum())
         counters["shadow_fetched"] += int(r["shadow_fetched"].sum())
+        if ao is not None:
+            counters["ao_steps"] += int(r["ao_steps"].sum())
+            counters["ao_fetched"] += int(r["ao_fetched"].sum())
     rspp = F(1) / F(spp)
     return (rgba * rspp).astype(F).reshape(h, w, 4), (layer * rspp).astype(F).reshape(h, w, 3), counters

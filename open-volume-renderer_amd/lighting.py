@@ -132,7 +132,7 @@ def shade(normal_w, pos, shadow, light, cam_pos, ambient=0.5, diffuse=0.5, specu
     sample, used as given (the orthographic camera's -dir, camera.py); None = normalize(cam_pos - pos), the perspective camera's"""
     n_w, pos, shadow = np.asarray(normal_w, F), np.asarray(pos, F), np.asarray(shadow, F)
     L, cam = np.asarray(light, F), np.asarray(cam_pos, F)
-    ka, kd, ks, i2 = F(ambient), F(diffuse), F(specular), F(2) * F(intensity)
+    ka, kd, ks, i2 = np.asarray(ambient, F), F(diffuse), F(specular), F(2) * F(intensity)   # (ambient: a scalar, or one per sample - isosurface.py's occlusion)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         cosNL = np.abs(dot(np.broadcast_to(L, n_w.shape), n_w))
         d = ((kd * cosNL).astype(F) * i2).astype(F)

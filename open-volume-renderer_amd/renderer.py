@@ -419,6 +419,49 @@ class DeviceHIP:
         return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), k=e[:, :, 0].astype(np.int64),
                     t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy())
 
+    # ambient occlusion of the isosurface frames (include/ovr_hip.h ovr_hip_set_ambient_occlusion; isosurface.py is the arithmetic).  Queued, applied at commit;
+    # every call resets the accumulation.
+    def set_ambient_occlusion(self, samples, distance=float("inf")):
+        """samples = K in 0 ... 16 occlusion walks per event of a GRADIENT- or FULL-shaded isosurface frame, each at most `distance` long (world units; inf: the
+        whole box); 0: off, the default"""
+        L.check(self._lib.ovr_hip_set_ambient_occlusion(self._h, int(samples), float(distance)))
+
+    def get_ambient_occlusion(self):
+        """ovr_hip_ambient_occlusion, the COMMITTED state: samples, distance, rotations (16), active (1: the next isosurface frame takes the AO kernels)"""
+        c = L.AmbientOcclusion()
+        L.check(self._lib.ovr_hip_get_ambient_occlusion(self._h, C.byref(c)))
+        return c
+
+    def ambient_occlusion_directions(self):
+        """the COMMITTED direction table as the host formed it: (16, K, 3) float32"""
+        k = int(self.get_ambient_occlusion().samples)
+        out = np.zeros((L.AO_ROTATIONS, k, 3), np.float32)
+        buf = (C.c_float * max(out.size, 1))()
+        L.check(self._lib.ovr_hip_get_ambient_occlusion_directions(self._h, buf, out.size))
+        if out.size:
+            out[...] = np.frombuffer(buf, np.float32, out.size).reshape(out.shape)
+        return out
+
+    def isosurface_ao_rays(self, org, direction, rotation=0, max_events=8, range_skipping=False):
+        """isosurface rays with ambient occlusion as the kernels evaluate them (ovr_hip_isosurface_ao_floats; known-answer tests): world rays (n, 3), (n, 3), every
+        ray at the rotation `rotation` of the direction table -> isosurface_layer_rays' dict plus O (n, e) float32 per event slot and ao_steps, ao_fetched (n,)
+        int64: the steps the AO walks of all events walked and fetched"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("isosurface_ao_rays: org and direction hold three floats per ray")
+        m = int(max_events)
+        out = torch.empty((n, 8 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_isosurface_ao_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m, int(rotation), int(bool(range_skipping))))
+        o = out.cpu().numpy()
+        e = o[:, 8:].reshape(n, m, 8)
+        return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64),
+                    ao_steps=o[:, 4].astype(np.int64), ao_fetched=o[:, 5].astype(np.int64), k=e[:, :, 0].astype(np.int64), t=e[:, :, 1].copy(),
+                    normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy(), O=e[:, :, 7].copy())
+
     def get_isosurfaces(self):
         """ovr_hip_isosurfaces, the COMMITTED state: n, isovalues (ascending), range_skipping (1: the last isosurface frame ran the range-skipping kernel)"""
         c = L.Isosurfaces()

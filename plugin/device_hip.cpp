@@ -211,6 +211,17 @@ public:
           std::fprintf(stderr, "\n");
         }
       }
+      // Ambient occlusion of the isosurface frames (ovr_hip_set_ambient_occlusion): OVR_HIP_AO_SAMPLES=8 casts that many occlusion walks per event,
+      // OVR_HIP_AO_DISTANCE=12 cuts them at that many world units (unset: the whole box).  Unset: nothing is called (the scene's own ao_samples is not read)
+      if (const char* as = std::getenv("OVR_HIP_AO_SAMPLES")) {
+        int k = 0;
+        float dist = 0.f;
+        const char* ad = std::getenv("OVR_HIP_AO_DISTANCE");
+        if (ovrhip_plugin::parse_ao(as, ad, &k, &dist) != 0)
+          throw std::runtime_error("[hip] OVR_HIP_AO_SAMPLES expects an integer in 0 ... 16, OVR_HIP_AO_DISTANCE a distance > 0 or inf");
+        check(ovr_hip_set_ambient_occlusion(h, k, dist));
+        if (!quiet) std::fprintf(stderr, "[hip] ambient occlusion: %d samples within %g\n", k, (double)dist);
+      }
     }
     commit();
   }

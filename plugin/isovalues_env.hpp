@@ -2,6 +2,7 @@
 // table on a machine without a GPU.
 #pragma once
 
+#include <cmath>
 #include <cstdio>
 
 namespace ovrhip_plugin {
@@ -31,6 +32,28 @@ inline int parse_iso_opacities(const char* text, float* a, int count)
   for (int k = 0; k < n; ++k)
     if (!(a[k] > 0.f && a[k] <= 1.f)) return -1;
   return n;
+}
+
+// OVR_HIP_AO_SAMPLES and OVR_HIP_AO_DISTANCE beside OVR_HIP_ISOVALUES (ovr_hip_set_ambient_occlusion): K, an integer in 0 ... 16 written in decimal digits, and the
+// radius in world units, a float > 0 or "inf" (unset: the whole box).  Each string is parsed whole.  Returns 0, or -1 for anything else: an empty string, a
+// sign, trailing text, K above 16, a radius that is NaN or <= 0
+inline int parse_ao(const char* samples, const char* distance, int* k, float* r)
+{
+  if (!samples || !*samples) return -1;
+  int n = 0, digits = 0;
+  for (const char* c = samples; *c; ++c, ++digits) {
+    if (*c < '0' || *c > '9' || digits >= 2) return -1;
+    n = 10 * n + (*c - '0');
+  }
+  if (n > 16) return -1;
+  float d = INFINITY;
+  if (distance) {
+    float one[2];
+    if (parse_isovalues(distance, one, 1) != 1 || !(one[0] > 0.f)) return -1;
+    d = one[0];
+  }
+  *k = n; *r = d;
+  return 0;
 }
 
 } // namespace ovrhip_plugin

@@ -521,6 +521,51 @@ int ovr_hip_get_ambient_occlusion(const ovr_hip_renderer* r, ovr_hip_ambient_occ
 /* the COMMITTED direction table as the host formed it: 16 x K x 3 floats, [m][j][x, y, z] (host memory).  EINVAL: a null pointer, a capacity below that */
 int ovr_hip_get_ambient_occlusion_directions(const ovr_hip_renderer* r, float* out, size_t capacity_floats);
 
+/* Slices (added within ABI v11: new entry points and structs only): the resident volume on up to OVR_HIP_MAX_SLICES cut planes or thick
+ * slabs, drawn in the march's place; open-volume-renderer_amd/slices.py is the arithmetic in numpy, the normative text.
+ *   caller     per slice a world point, a world normal of any length, a thickness in world units along the normal (0: a plane; > 0: a slab centred on the
+ *              plane; +inf: the whole box) and a mode, OVR_HIP_PROJECT_MAXIMUM / MINIMUM / MEAN, read only while thickness > 0.  The order given is kept.
+ *   host       n = the normal normalised in float64, each component rounded to float32; c = dot(n, point) formed in float64 from the rounded n and rounded
+ *              once; half = 0.5f * thickness.  ovr_hip_get_slices hands back exactly these.
+ *   ray        the projection's for the pixel sample (camera kind, jitter, samples per pixel) and its box test (t0, t1, hit) - the clipped one while a clip
+ *              box is committed, the orthographic rule for ignored slabs included; t is shared between world and object space.
+ *   slice k    dn = fma(n.x, d.x, fma(n.y, d.y, n.z * d.z)), e = fma(n.x, o.x, fma(n.y, o.y, n.z * o.z)) - c with the world origin o and direction d.
+ *              plane: ts = (-e) / dn, met iff hit, dn != 0 and t0 <= ts <= t1 (a NaN meets nothing), key ts.  slab: dn != 0: a = (-half - e) / dn,
+ *              b = (half - e) / dn, swapped if a > b, ta = fmaxf(t0, a), tb = fminf(t1, b); dn == 0: (ta, tb) = (t0, t1) if |e| <= half, else not met; met iff
+ *              hit and tb > ta, key ta.  thickness +inf gives (ta, tb) = (t0, t1) bit for bit: that slab's frame is the projection's of its mode.
+ *   winner     the met slice with the smallest key, of equal keys the lowest index.  Only the winner is sampled: a plane by one trilinear tap at
+ *              to_object(fma(ts, d, o)); a slab by the projection's steps on (ta, tb) at the committed sampling rate and its reduction of the slice's mode.  A
+ *              winning slab without a step counts as not met; the next nearest slice is not tried.
+ *   pixel      nothing met: rgba = 0, layer = 0.  Otherwise rgb = the projection's colour at v, clamped, a = 1 - a slice is opaque, the alpha table is not read -
+ *              and the buffer mapped as `grad` carries (v, t_k, k + 1).  Samples per pixel and accumulated frames combine as the projection's; convergence,
+ *              sparse sampling, reconstruction, rgba8 / rgba16f, tiles, shards and device groups work unchanged.
+ *   skipping   while ovr_hip_set_empty_space_skipping(1) is committed a MAXIMUM or MINIMUM slab drops fetches by the projection's rule; the frame, the layer and
+ *              samples + skipped_samples are bit for bit the non-skipping kernel's.  Planes and MEAN slabs fetch everything.
+ *   counters   samples = taps fetched (a plane that is met: 1), skipped_samples = steps whose fetch was dropped, shaded / shadow counters 0, layout 0,
+ *              pipeline 1, tuning 0: the tuner and the adaptive-skipping probe are neither asked nor fed.
+ * While n > 0 slices are committed, frames are slice frames: committed isovalues and a committed projection mode are kept but not drawn and resume at n = 0.  Slice
+ * frames ignore shading mode, light, material, shadow cache, AO, pipeline, LDS staging and layout choice; they honour camera kind, clip box, sampling rate,
+ * transfer function (colours and range) and grid convention.  Queued, applied at commit; every call resets the accumulation and voids nothing else; until it is
+ * called with n > 0 every frame, counter and kernel is what it was.  n = 0 or slices = NULL: off.  EINVAL (the state stays): n < 0 or n > 4, a null pointer with
+ * n > 0, a non-finite point, a normal that is zero, non-finite or not normalisable, a NaN or negative thickness, with thickness > 0 a mode outside 1 ... 3.  A
+ * device group forwards the call; ovr_hip_get_slices reports member 0's state.  Not done: translucent slices, volume context around a slice, lighting.
+ * Kernels: a plane kernel (every slice a plane: one lane per ray, one tap) and a walk kernel (a slab among them: four lanes per ray, the projection's rounds),
+ * each with the clipped / orthographic twins.  Measured (tools/slice_bench.py, profiles/r21_slices.md; MI355X, 1024^3 f32, 1920 x 1080, kernel_ms): one axial plane
+ * 0.046, three orthogonal planes 0.050, one oblique plane 0.045, a 32-voxel oblique MAXIMUM slab 0.164 (0.162 with range skipping,
+ * 33 % of the fetches dropped), the MEAN slab 0.164, the +inf MAXIMUM slab 1.669 beside the MAXIMUM projection frame's 1.864 and the unshaded
+ * march's 1.343 on the same camera. */
+#define OVR_HIP_MAX_SLICES 4
+typedef struct ovr_hip_slice { float point[3], normal[3], thickness; int32_t mode; } ovr_hip_slice;
+int ovr_hip_set_slices(ovr_hip_renderer* r, const ovr_hip_slice* slices, int32_t n);
+typedef struct ovr_hip_slices {
+  int32_t n;                                   /* the COMMITTED slices, in the order given */
+  struct { float normal[3], c, thickness; int32_t mode; } slice[OVR_HIP_MAX_SLICES];
+  int32_t walks;                               /* 1: a slab is among them - the frame takes the walk kernel */
+  int32_t range_skipping;                      /* 1: the last slice frame ran the range-skipping kernel */
+} ovr_hip_slices;
+/* the COMMITTED state, not the queued one */
+int ovr_hip_get_slices(const ovr_hip_renderer* r, ovr_hip_slices* out);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -688,6 +733,11 @@ int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org_devic
  * ESTATE without a volume, isovalues or committed AO samples; EINVAL: a null pointer, n < 0, a bad max_events or rotation. */
 int ovr_hip_isosurface_ao_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t max_events, int32_t rotation,
                                  int32_t range_skipping);
+/* a slice ray as the kernels evaluate it (added with the slices): n world-space rays as for ovr_hip_project_floats - the direction used as given - through the
+ * device function the slice frame's kernel calls, with the COMMITTED slices, volume transform, sampling rate and clip box.  Per ray 4 floats: (the winning
+ * slice's index + 1 or 0, v, t_k, steps walked - 1 for a plane); zeros for a ray that meets nothing.  ESTATE without a volume or without committed slices;
+ * EINVAL: a null pointer, n < 0. */
+int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t range_skipping);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -155,6 +155,36 @@ class IsosurfaceLayers(C.Structure):
     ]
 
 
+MAX_SLICES = 4
+
+
+class Slice(C.Structure):
+    _fields_ = [
+        ("point", C.c_float * 3),
+        ("normal", C.c_float * 3),
+        ("thickness", C.c_float),
+        ("mode", C.c_int32),
+    ]
+
+
+class CommittedSlice(C.Structure):
+    _fields_ = [
+        ("normal", C.c_float * 3),
+        ("c", C.c_float),
+        ("thickness", C.c_float),
+        ("mode", C.c_int32),
+    ]
+
+
+class Slices(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("slice", CommittedSlice * MAX_SLICES),
+        ("walks", C.c_int32),
+        ("range_skipping", C.c_int32),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -267,6 +297,9 @@ SYMBOLS = {
     "ovr_hip_set_projection": (C.c_int, [_H, C.c_int32]),
     "ovr_hip_get_projection": (C.c_int, [_H, C.POINTER(Projection)]),
     "ovr_hip_project_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "ovr_hip_set_slices": (C.c_int, [_H, C.POINTER(Slice), C.c_int32]),
+    "ovr_hip_get_slices": (C.c_int, [_H, C.POINTER(Slices)]),
+    "ovr_hip_slice_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

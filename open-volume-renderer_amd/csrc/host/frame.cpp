@@ -302,8 +302,20 @@ void fill_isosurface_params(const ovr_hip_renderer* r, RayMarchParams& q)
   q.ao_distance = ao.distance;
   q.ao_dirs = r->d_ao_dirs;
 }
-// a frame drawn by one kernel in the march's place, from the general layout: a projection or the isosurfaces
-static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0; }
+void fill_slice_params(const ovr_hip_renderer* r, RayMarchParams& q)
+{
+  const SliceP& p = r->slices.current;
+  q.slice_n = p.n;
+  for (int k = 0; k < OVR_HIP_MAX_SLICES; ++k) {
+    const bool on = k < p.n;
+    for (int a = 0; a < 3; ++a) q.slice_plane[k][a] = on ? p.normal[k][a] : 0.f;
+    q.slice_plane[k][3] = on ? p.c[k] : 0.f;
+    q.slice_half[k] = on ? 0.5f * p.thickness[k] : 0.f;
+    q.slice_mode[k] = on && p.thickness[k] > 0.f ? p.mode[k] : 0; // 0: a plane
+  }
+}
+// a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces or the slices
+static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0 || P.slice_n > 0; }
 
 // step 2, continued: tables, shard, jitter, counters
 static int fill_table_params(ovr_hip_renderer* r)
@@ -331,6 +343,7 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.projection = r->projection.current;
   P.mc_ranges = nullptr;
   fill_isosurface_params(r, P);
+  fill_slice_params(r, P);
   return 0;
 }
 
@@ -638,7 +651,7 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  if (r->projection.current != OVR_HIP_PROJECT_OFF || r->isosurfaces.current.n > 0) bind_general_layout(r);
+  if (r->projection.current != OVR_HIP_PROJECT_OFF || r->isosurfaces.current.n > 0 || r->slices.current.n > 0) bind_general_layout(r);
   else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
@@ -817,6 +830,10 @@ static int read_frame_stats(ovr_hip_renderer* r)
     r->isosurface_skipped = r->plan.isosurface.skip;
     r->stats.skipping_kernels = r->plan.isosurface.skip ? 1 : 0;
   }
+  if (r->plan.slices.on) { // a slice frame, likewise
+    r->slices_skipped = r->plan.slices.skip;
+    r->stats.skipping_kernels = r->plan.slices.skip ? 1 : 0;
+  }
   r->stats.replicas_building = poll_replica_builds(r);
   (void)hipGetLastError(); // hipErrorNotReady of the query is not an error
   return 0;
@@ -905,7 +922,7 @@ int finish_frame_one(ovr_hip_renderer* r)
   r->stats.stale_tiles = 0;
   if (int e = resolve_pool(r)) return e;
   if (int e = read_frame_stats(r)) return e;
-  if (r->plan.project.mode != 0 || r->plan.isosurface.on) r->stats.tuning = 0; // a projection or isosurface frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
+  if (r->plan.project.mode != 0 || r->plan.isosurface.on || r->plan.slices.on) r->stats.tuning = 0; // a projection, isosurface or slice frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
   else {
     const policy::FrameWork w = frame_work(r);
     tune_after_frame(r, w);

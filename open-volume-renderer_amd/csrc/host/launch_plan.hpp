@@ -92,6 +92,18 @@ constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clip
   return shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
 }
 
+// slice_plane_kernel<VT, am, clipped> and slice_walk_kernel<VT, am, skip, clipped> (open-volume-renderer_amd/slices.py is the arithmetic): cut
+// planes and thick slabs of the general layouts, up to kMaxSlices of them.  walks: a slab is among the committed slices - the projection's walk on the slab's
+// interval, the winning slice's mode a run-time value; without one the plane kernel, one lane per ray, which has nothing to skip.  The orthographic twins exist
+// on the clipped kernels alone, under the rule the projection's follow
+constexpr int kMaxSlices = 4; // include/ovr_hip.h OVR_HIP_MAX_SLICES
+constexpr bool slice_variant_exists(bool walks, int am, bool skip, bool clipped, bool orthographic = false)
+{
+  if (orthographic && !clipped) return false;
+  if (skip && !walks) return false; // one tap per ray: no fetch to drop
+  return am >= 0 && am <= 4;
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -144,6 +156,9 @@ struct LaunchFacts {
   int isosurfaces = 0;                // the number of committed isovalues; > 0: an isosurface frame - `projection` is kept but not drawn, pool, majorants and LDS staging are not read
   bool translucent = false;           // one of the committed isovalues' opacities is below 1 (ovr_hip_set_isosurface_layers): an isosurface frame takes the translucent twins
   bool ambient_occlusion = false;     // ambient-occlusion samples are committed (ovr_hip_set_ambient_occlusion, K > 0): a shaded isosurface frame takes the AO twins
+  int slices = 0;                     // the number of committed slices; > 0: a slice frame - `isosurfaces` and `projection` are kept but not drawn, shading, pool, majorants and LDS staging are not read
+  bool slice_walks = false;           // one of the committed slices is a slab (thickness > 0): the frame takes the walk kernel
+  bool slice_extremum = false;        // one of the committed slabs is a MAXIMUM or MINIMUM slab: the only ones range skipping drops fetches of
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -167,6 +182,8 @@ struct LaunchPlan {
   int shade_grid_blocks = 0;
   bool error = false;                 // the frame cannot be launched (hipErrorInvalidValue)
   bool ambient_occlusion = false;     // an isosurface frame's kernel is the AO twin of the translucent one (isosurface.translucent and isosurface.clipped are set)
+  // a slice frame (LaunchFacts::slices > 0): slice_plane_kernel or slice_walk_kernel in the march's place, nothing else of the plan but `am` is read
+  struct Slices { bool on = false, walks = false, skip = false, clipped = false; size_t lds_bytes = 0; } slices;
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -237,8 +254,25 @@ inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o
   return pl;
 }
 
+// a slice frame: the plane kernel while every slice is a plane, the walk kernel otherwise - its skipping twin where the ranges are bound and a slab is an
+// extremum's (planes and MEAN slabs fetch everything: a frame of those alone keeps the plain kernel)
+inline LaunchPlan plan_slices(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  const Addressing a = plan_addressing(f, o);
+  if (a.error || f.slices < 1 || f.slices > kMaxSlices || f.quad) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am);
+  pl.slices.on = true;
+  pl.slices.walks = f.slice_walks;
+  pl.slices.skip = f.slice_walks && f.slice_extremum && f.ranges;
+  pl.slices.clipped = w.clipped;
+  pl.slices.lds_bytes = w.lds_bytes;
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
+  if (f.slices != 0) return plan_slices(f, o); // committed isovalues and a committed projection mode are kept but not drawn
   if (f.isosurfaces != 0) return plan_isosurface(f, o); // a committed projection mode is kept but not drawn
   if (f.projection != 0) return plan_projection(f, o);
   LaunchPlan pl;
@@ -288,6 +322,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
+  if (pl.slices.on) return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic);
   if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion);
   if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
@@ -308,5 +343,8 @@ static_assert(isosurface_variant_exists(2, 0, true, true, false, true) && isosur
 static_assert(isosurface_variant_exists(1, 0, false, true, false, true, true) && isosurface_variant_exists(2, 4, true, true, true, true, true) && !isosurface_variant_exists(0, 0, false, true, false, true, true)
                 && !isosurface_variant_exists(2, 0, false, true, false, false, true) && !isosurface_variant_exists(2, 0, false, false, false, true, true),
               "the ambient-occlusion isosurface kernels: twins of the translucent ones, under a shading mode with an ambient term");
+static_assert(slice_variant_exists(false, 0, false, true, true) && slice_variant_exists(true, 4, true, true, true) && !slice_variant_exists(true, 0, true, false, true)
+                && !slice_variant_exists(false, 0, false, false, true) && !slice_variant_exists(false, 0, true, true),
+              "the slice kernels: orthographic on the clipped variants alone; the plane kernel has no skipping twin");
 
 } // namespace ovrhip

@@ -10,6 +10,7 @@
 #pragma GCC visibility push(hidden)
 #include "commit_plan.hpp"
 #include "policy.hpp"
+#include "slices_host.hpp"
 #pragma GCC visibility pop
 
 #include <hip/hip_runtime.h>
@@ -74,6 +75,15 @@ struct IsoP {
   float v[OVR_HIP_MAX_ISOVALUES] = { 0.f, 0.f, 0.f, 0.f };
   float a[OVR_HIP_MAX_ISOVALUES] = { 1.f, 1.f, 1.f, 1.f };
   bool translucent() const { for (int k = 0; k < n; ++k) if (a[k] < 1.f) return true; return false; }
+};
+// ovr_hip_set_slices, as the host derives them (slice_values in slices_host.hpp): the unit normal, c = dot(n, point), the thickness as given and the mode (kept
+// as given; read only while thickness > 0); the entries behind n are zeros
+struct SliceP {
+  int n = 0;
+  float normal[OVR_HIP_MAX_SLICES][3] = {};
+  float c[OVR_HIP_MAX_SLICES] = {}, thickness[OVR_HIP_MAX_SLICES] = {};
+  int mode[OVR_HIP_MAX_SLICES] = {};
+  bool walks() const { for (int k = 0; k < n; ++k) if (thickness[k] > 0.f) return true; return false; }
 };
 // ovr_hip_set_ambient_occlusion: K and the radius (+inf while K == 0: the radius is not read then)
 struct AoP { int samples = 0; float distance = INFINITY; };
@@ -218,6 +228,8 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::IsoP> isosurfaces; // ovr_hip_set_isosurfaces: sorted ascending; recorded under kShading like the projection mode.  n > 0: isosurface frames
   bool isosurface_skipped = false; // the last isosurface frame ran the range-skipping kernel (ovr_hip_get_isosurfaces)
   Queued<ovrhip::host::AoP> ambient_occlusion; // ovr_hip_set_ambient_occlusion; recorded under kShading like the isovalues
+  Queued<ovrhip::host::SliceP> slices; // ovr_hip_set_slices; recorded under kShading like the projection mode.  n > 0: slice frames, whatever isovalues and projection mode are committed
+  bool slices_skipped = false;     // the last slice frame ran the range-skipping kernel (ovr_hip_get_slices)
   std::vector<float> ao_table;     // the direction table of the committed K, [16][K][3], as uploaded to d_ao_dirs (both follow K at commit)
   float* d_ao_dirs = nullptr;
   Queued<float> rate;
@@ -408,6 +420,8 @@ void fill_shadow_params(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 const float* projection_ranges(const ovr_hip_renderer* r);
 // the committed isovalues into a frame's parameters (iso_n = 0: no isosurface frame)
 void fill_isosurface_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
+// the committed slices into a frame's parameters (slice_n = 0: no slice frame)
+void fill_slice_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -346,6 +346,45 @@ int ovr_hip_get_isosurfaces(const ovr_hip_renderer* r, ovr_hip_isosurfaces* out)
   return 0;
 }
 
+int ovr_hip_set_slices(ovr_hip_renderer* r, const ovr_hip_slice* slices, int32_t n)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (n < 0 || n > OVR_HIP_MAX_SLICES) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_slices: between 0 and 4 slices");
+  if (!slices && n > 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_slices: a null pointer with n > 0");
+  SliceP p;
+  p.n = n;
+  for (int k = 0; k < n; ++k) {
+    SliceValues v;
+    if (const char* why = slice_values(slices[k].point, slices[k].normal, slices[k].thickness, slices[k].mode, &v))
+      return fail(OVR_HIP_EINVAL, std::string("[hip] ovr_hip_set_slices: ") + why);
+    for (int a = 0; a < 3; ++a) p.normal[k][a] = v.normal[a];
+    p.c[k] = v.c;
+    p.thickness[k] = slices[k].thickness;
+    p.mode[k] = slices[k].mode;
+  }
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->slices.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_slices(m, slices, n));
+  return 0;
+}
+
+int ovr_hip_get_slices(const ovr_hip_renderer* r, ovr_hip_slices* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_slices: null argument");
+  const SliceP& p = r->slices.current;
+  std::memset(out, 0, sizeof(*out));
+  out->n = p.n;
+  for (int k = 0; k < p.n; ++k) {
+    for (int a = 0; a < 3; ++a) out->slice[k].normal[a] = p.normal[k][a];
+    out->slice[k].c = p.c[k];
+    out->slice[k].thickness = p.thickness[k];
+    out->slice[k].mode = p.mode[k];
+  }
+  out->walks = p.walks() ? 1 : 0;
+  out->range_skipping = r->slices_skipped ? 1 : 0;
+  return 0;
+}
+
 int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -694,6 +733,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (a->shading.current != b->shading.current || a->projection.current != b->projection.current) return false;
   if (!same_bytes(a->isosurfaces.current, b->isosurfaces.current)) return false;
   if (!same_bytes(a->ambient_occlusion.current, b->ambient_occlusion.current)) return false;
+  if (!same_bytes(a->slices.current, b->slices.current)) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -788,14 +828,15 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
   consume(ch, kSparse, r->sparse);         // :180-183
   consume(ch, kAccumulation, r->accumulate); // :185-188
   consume(ch, kSamplingRate, r->rate);     // :190-196
-  { // the projection mode, the isovalues and the AO state are recorded with the shading mode: set if any of the setters was called, differs if any value differs
+  { // the projection mode, the isovalues, the AO state and the slices are recorded with the shading mode: set if any of the setters was called, differs if any value differs
     const int shading = r->shading.current, projection = r->projection.current;
     const IsoP iso = r->isosurfaces.current;
     const AoP ao = r->ambient_occlusion.current;
-    const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update(), set_a = r->ambient_occlusion.update();
-    ch.note(kShading, set_s || set_p || set_i || set_a,
+    const SliceP sl = r->slices.current;
+    const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update(), set_a = r->ambient_occlusion.update(), set_l = r->slices.update();
+    ch.note(kShading, set_s || set_p || set_i || set_a || set_l,
             shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0 ||
-              std::memcmp(&ao, &r->ambient_occlusion.current, sizeof(AoP)) != 0);
+              std::memcmp(&ao, &r->ambient_occlusion.current, sizeof(AoP)) != 0 || std::memcmp(&sl, &r->slices.current, sizeof(SliceP)) != 0);
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
   }
@@ -1357,6 +1398,23 @@ int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org, const float* d
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_project_floats(q, org, dir, out, n, mode, range_skipping != 0 && mode != OVR_HIP_PROJECT_MEAN, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)
+{
+  if (!r || !org || !dir || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_slice_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: no volume was set");
+  if (r->slices.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: no slice is committed (ovr_hip_set_slices)");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
+  fill_slice_params(r, q);
+  q.mc_ranges = projection_ranges(r);
+  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: the resident volume has no macrocell ranges");
+  HIP_TRY(launch_slice_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

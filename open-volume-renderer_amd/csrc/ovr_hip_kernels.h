@@ -278,6 +278,13 @@ struct RayMarchParams {
   int ao_samples;
   float ao_distance;
   const float* ao_dirs;
+  // slices (ovr_hip_set_slices; open-volume-renderer_amd/slices.py is the arithmetic): slice_n > 0 = the frame is the slice kernels'.  Per slice the unit normal
+  // and c = dot(n, point) (slice_plane), half the thickness (slice_half) and slice_mode: 0 a plane, 1 ... 3 a slab of that projection mode; the entries behind
+  // slice_n unread.  Behind everything else, like the AO fields: no other kernel reads them
+  int slice_n;
+  float slice_plane[4][4];
+  float slice_half[4];
+  int slice_mode[4];
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -342,6 +349,10 @@ hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float*
 // after the event, O) per event, the rest zeros - with p.ao_samples / p.ao_distance / p.ao_dirs and every ray at the table's rotation `rotation` (0 ... 15)
 hipError_t launch_isosurface_ao_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int rotation, int range_skipping,
                                        hipStream_t stream);
+// known-answer entry of the slices (slice_ray in ovr_hip_slices.h, the function the walk frame's kernel calls; its stage and its one tap are the plane kernel's):
+// n world-space rays -> 4 floats each: the winning slice's index + 1 (0: nothing met), v, t_k, steps walked (a plane: 1), four lanes per ray.  p.slice_*: the
+// slices; p.mc_ranges: the ranges if range_skipping (hipErrorInvalidValue without them, without slices or for a replica's type)
+hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

@@ -16,6 +16,7 @@
 // function (colour float4 table + alpha table, 20 KiB at the shipped resolution of 1024), the per-axis brick-offset tables,
 #include "ovr_hip_device.h"
 #include "ovr_hip_isosurface_ao.h"
+#include "ovr_hip_slices.h"
 #include "ovr_hip_update.h"
 
 namespace ovrhip {
@@ -1019,6 +1020,11 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.translucent = p.iso_n > 0 && p.iso_translucent != 0;
   f.ambient_occlusion = p.iso_n > 0 && p.ao_samples > 0;
   f.orthographic = p.cam_orthographic != 0;
+  f.slices = p.slice_n;
+  for (int k = 0; k < p.slice_n && k < kMaxSlices; ++k) {
+    f.slice_walks = f.slice_walks || p.slice_mode[k] != 0;
+    f.slice_extremum = f.slice_extremum || p.slice_mode[k] == kProjectMaximum || p.slice_mode[k] == kProjectMinimum;
+  }
   return plan_launch(f, o);
 }
 
@@ -1074,10 +1080,13 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template IsosurfaceKernels isosurface_kernels_of<E, false>(const LaunchPlan&);       \
   extern template IsosurfaceLayersKernels isosurface_kernels_of<E, true>(const LaunchPlan&);
 #define OVR_X_AO(E, NAME, BASE, LAYOUT) extern template IsosurfaceAoKernels isosurface_ao_kernels_of<E>(const LaunchPlan&);
+#define OVR_X_SLICES(E, NAME, BASE, LAYOUT) extern template SliceKernels slice_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
+OVR_VOXEL_TYPES(OVR_X_SLICES)
 #undef OVR_X
 #undef OVR_X_AO
+#undef OVR_X_SLICES
 
 // a plan's kernels for the volume's voxel type: the frame's two - a projection's or an isosurface's kernel in the in-place march's place (such a plan is neither
 // pooled nor LDS-staged, march_lds_bytes is that kernel's) - and the known-answer entry's of such a plan.  All nullptr: the plan is an error, or no such variant
@@ -1087,12 +1096,15 @@ struct PlanKernels {
   IsosurfaceFloatsKernel isosurface_floats = nullptr;
   IsosurfaceLayersFloatsKernel isosurface_layers_floats = nullptr;
   IsosurfaceAoFloatsKernel isosurface_ao_floats = nullptr;
+  SliceFloatsKernel slice_floats = nullptr;
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   PlanKernels k;
   if (plan.error) return k;
-  if (plan.isosurface.on && plan.ambient_occlusion) {
+  if (plan.slices.on)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_floats = v.floats; });
+  else if (plan.isosurface.on && plan.ambient_occlusion) {
     if (p.ao_dirs && p.ao_samples > 0 && p.ao_samples <= kAoMaxSamples) // (the AO kernels read the direction table: no table, no kernel)
       dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_ao_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_ao_floats = v.floats; });
   }
@@ -2057,6 +2069,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
 {
   RayMarchParams q = p;
   q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
 }
@@ -2120,6 +2133,20 @@ hipError_t launch_project_floats(const RayMarchParams& p, const float* org, cons
   q.projection = mode; q.iso_n = 0; q.ao_samples = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
   const LaunchPlan pl = plan_raymarch(q);
   const ProjectFloatsKernel kern = plan_kernels(q, pl).project_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
+}
+
+// known-answer entry of the slices: the kernel of the general layout's type at the addressing mode a slice frame takes for it
+hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if ((range_skipping && !p.mc_ranges) || p.slice_n < 1 || p.slice_n > kMaxSlices) return hipErrorInvalidValue;
+  RayMarchParams q = query_params(p, range_skipping != 0);
+  q.slice_n = p.slice_n;
+  const LaunchPlan pl = plan_raymarch(q);
+  const SliceFloatsKernel kern = plan_kernels(q, pl).slice_floats;
   const unsigned int blocks = quad_ray_blocks(n);
   if (!kern || !blocks) return hipErrorInvalidValue;
   return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);

@@ -53,6 +53,7 @@ class Scene:
     volume_sampling_rate: float = 1.0
     spp: int = 1
     clipping_box: object = None                # (lower, upper) in world units or None (vidi3d.read_scene: the file's clippingBox)
+    slices: Sequence = ()                      # the file's visible cut planes (vidi3d.read_scene) - NOT applied by init: pass them to set_slices
 
 
 class _DevicePtr:
@@ -378,6 +379,51 @@ class DeviceHIP:
         L.check(self._lib.ovr_hip_project_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(mode), int(bool(range_skipping))))
         o = out.cpu().numpy()
         return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].astype(np.int64), o[:, 3].astype(np.int64)
+
+    # slices (include/ovr_hip.h ovr_hip_set_slices; slices.py is the arithmetic): up to four cut planes or thick slabs through the volume in the march's place -
+    # nearest slice wins; the buffer mapframe hands out as `grad` carries the layer (v, t_k, k + 1).  Queued, applied at commit; every call resets the accumulation.
+    def set_slices(self, slices=None):
+        """slices: dicts (point, normal, thickness = 0, mode = PROJECT_MAXIMUM) or (point, normal[, thickness[, mode]]) tuples, at most four, kept in the order
+        given; thickness 0 a plane, > 0 a slab of that many world units along the normal (inf: the whole box), mode read only for a slab.  None or (): off"""
+        items = [] if slices is None else list(slices)
+        arr = (L.Slice * max(len(items), 1))()
+        for k, s in enumerate(items):
+            if isinstance(s, dict):
+                point, normal, thickness, mode = s["point"], s["normal"], s.get("thickness", 0.0), s.get("mode", L.PROJECT_MAXIMUM)
+            else:
+                s = tuple(s)
+                point, normal, thickness, mode = s[0], s[1], (s[2] if len(s) > 2 else 0.0), (s[3] if len(s) > 3 else L.PROJECT_MAXIMUM)
+            point, normal = np.asarray(point, np.float32).ravel(), np.asarray(normal, np.float32).ravel()
+            if point.size != 3 or normal.size != 3:
+                raise RuntimeError("set_slices: a point and a normal hold three floats each")
+            arr[k].point[:] = [float(x) for x in point]
+            arr[k].normal[:] = [float(x) for x in normal]
+            arr[k].thickness = float(thickness)
+            arr[k].mode = int(mode)
+        L.check(self._lib.ovr_hip_set_slices(self._h, arr if items else None, len(items)))
+
+    def slices(self):
+        """ovr_hip_slices, the COMMITTED state: n, slice[k].normal / c / thickness / mode, walks (1: a slab is among them), range_skipping (1: the last slice
+        frame ran the range-skipping kernel)"""
+        c = L.Slices()
+        L.check(self._lib.ovr_hip_get_slices(self._h, C.byref(c)))
+        return c
+
+    def slice_rays(self, org, direction, range_skipping=False):
+        """slice rays as the kernels evaluate them (ovr_hip_slice_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
+        k (n,) int64 - the winning slice's index + 1, 0: nothing met -, v (n,), t_k (n,) float32, steps walked (n,) int64 (a plane: 1), with the committed slices,
+        volume, sampling rate and clip box"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("slice_rays: org and direction hold three floats per ray")
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_slice_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(bool(range_skipping))))
+        o = out.cpu().numpy()
+        return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64)
 
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.

@@ -14,12 +14,14 @@ _TYPE_NAME = {np.dtype(np.uint8): "UNSIGNED_BYTE", np.dtype(np.int8): "BYTE", np
 
 
 def write_scene(directory, name, volume, color_controls, alpha_table, scalar_range_normalized, camera, fovy=45.0,
-                sample_distance=1.0, clipping_box=None, projection_mode="PERSPECTIVE"):
+                sample_distance=1.0, clipping_box=None, projection_mode="PERSPECTIVE", slices=None):
     """volume: (nz, ny, nx) array; color_controls: [(position, r, g, b)]; alpha_table: float32 opacities (its length is the
     TF resolution); scalar_range_normalized: (lo, hi) as a fraction of the type's maximum for integer data, raw for floats
     (scalarMappingRange, serializer_vidi3d.cpp:236-272); camera: (eye, center, up); clipping_box: (lower, upper) in world units
     (spacing 1: voxels) or None - written as `clippingBox` in the units of `boundingBox`, which spans (0, 0, 0) .. dims - 1 as in
-    the reference's shipped scenes (`read_scene` maps it back); projection_mode: "PERSPECTIVE" or "ORTHOGRAPHIC", the camera's `projectionMode`."""
+    the reference's shipped scenes (`read_scene` maps it back); projection_mode: "PERSPECTIVE" or "ORTHOGRAPHIC", the camera's `projectionMode`;
+    slices: {"x" | "y" | "z": (position, visible)} - the cut planes of `view.volume.slice`, position in world units along that axis, written in the units of
+    `boundingBox` like the clipping box (`read_scene` maps it back) - or None: no `slice` block."""
     if projection_mode not in ("PERSPECTIVE", "ORTHOGRAPHIC"):
         raise ValueError("projection_mode is PERSPECTIVE or ORTHOGRAPHIC")
     os.makedirs(directory, exist_ok=True)
@@ -58,6 +60,11 @@ def write_scene(directory, name, volume, color_controls, alpha_table, scalar_ran
         doc["view"]["volume"]["boundingBox"] = {"minimum": xyz((0, 0, 0)), "maximum": xyz((nx - 1, ny - 1, nz - 1))}
         doc["view"]["volume"]["clippingBox"] = {"minimum": xyz([to_file(w, n) for w, n in zip(clipping_box[0], (nx, ny, nz))]),
                                                 "maximum": xyz([to_file(w, n) for w, n in zip(clipping_box[1], (nx, ny, nz))])}
+    if slices is not None:
+        to_file = lambda w, n: float(w) / n * (n - 1)
+        doc["view"]["volume"].setdefault("boundingBox", {"minimum": xyz((0, 0, 0)), "maximum": xyz((nx - 1, ny - 1, nz - 1))})
+        doc["view"]["volume"]["slice"] = {axis: {"position": to_file(slices[axis][0], n), "visible": bool(slices[axis][1])}
+                                          for axis, n in zip("xyz", (nx, ny, nz)) if axis in slices}
     path = os.path.join(directory, name + ".json")
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
@@ -174,10 +181,14 @@ _INT_MAX = {np.dtype(np.uint8): 255.0, np.dtype(np.int8): 127.0, np.dtype(np.uin
 
 def read_scene(path, load_volume=True):
     """VIDI3D scene file -> dict(volume, dtype, dims, grid_origin, grid_spacing, tfn_color (N x 4), tfn_opacity (N), value_range,
-    camera (eye, at, up, fovy), lights [(direction, color)], volume_sampling_rate, clipping_box).  `scene_from_file` wraps it into a Scene.
+    camera (eye, at, up, fovy), lights [(direction, color)], volume_sampling_rate, clipping_box, slices).  `scene_from_file` wraps it into a Scene.
     clipping_box: the file's `view.volume.clippingBox` - which the reference's loader drops - mapped linearly from `boundingBox` onto the volume's
     world box (grid_origin .. grid_origin + grid_spacing * dims) as (lower, upper), or None when the two boxes are equal (all of the reference's
-    shipped scenes) or the file has none."""
+    shipped scenes) or the file has none.
+    slices: the file's visible `view.volume.slice.{x, y, z}` entries - which the reference's loader drops too - as planes for DeviceHIP.set_slices: dicts
+    (point, normal = the axis, thickness 0.0, mode 1), the position mapped from `boundingBox` onto the world box exactly as the clipping box is, the other two
+    coordinates at the world box's centre; in the order x, y, z.  An empty list when none is visible (all of the reference's shipped scenes) or there is no
+    `boundingBox` to map from.  DeviceHIP.init does NOT apply them: the caller passes them to set_slices."""
     with open(path) as f:
         root = json.loads(_strip_json_comments(f.read()))
     workdir = os.path.dirname(os.path.abspath(path)) or "."
@@ -246,7 +257,18 @@ def read_scene(path, load_volume=True):
             world = [(0.0, spacing[k] * n) for k, n in enumerate((nx, ny, nz))]
             to_world = lambda c, k: world[k][0] + (c - bb[0][k]) / (bb[1][k] - bb[0][k]) * (world[k][1] - world[k][0])
             clipping_box = (tuple(to_world(cb[0][k], k) for k in range(3)), tuple(to_world(cb[1][k], k) for k in range(3)))
-    return dict(volume=volume, dtype=dtype, dims=(nx, ny, nz), grid_origin=(0.0, 0.0, 0.0), grid_spacing=spacing,
+    slices = []
+    if "slice" in jv and "boundingBox" in jv:
+        bb = [[float(jv["boundingBox"][m][k]) for k in "xyz"] for m in ("minimum", "maximum")]
+        world = [(0.0, spacing[k] * n) for k, n in enumerate((nx, ny, nz))]
+        for k, axis in enumerate("xyz"):
+            e = jv["slice"].get(axis)
+            if not e or not e.get("visible", False) or "position" not in e or bb[1][k] == bb[0][k]:
+                continue
+            point = [0.5 * (world[a][0] + world[a][1]) for a in range(3)]
+            point[k] = world[k][0] + (float(e["position"]) - bb[0][k]) / (bb[1][k] - bb[0][k]) * (world[k][1] - world[k][0])
+            slices.append(dict(point=tuple(point), normal=tuple(1.0 if a == k else 0.0 for a in range(3)), thickness=0.0, mode=1))
+    return dict(volume=volume, dtype=dtype, dims=(nx, ny, nz), grid_origin=(0.0, 0.0, 0.0), grid_spacing=spacing, slices=slices,
                 tfn_color=color, tfn_opacity=opacity, value_range=(float(vr[0]), float(vr[1])),
                 camera=(xyz(cam["eye"]), xyz(cam["center"]), xyz(cam["up"]), float(cam["fovy"])), lights=lights,
                 volume_sampling_rate=float(rate), clipping_box=clipping_box, projection_mode=str(cam.get("projectionMode", "PERSPECTIVE")).upper())
@@ -263,5 +285,5 @@ def scene_from_file(path):
         cam.orthographic_height = camera.auto_height(eye, at, fovy)
     scene = Scene(volume=d["volume"], grid_origin=d["grid_origin"], grid_spacing=d["grid_spacing"],
                   transfer_function=TransferFunction(color=d["tfn_color"], opacity=d["tfn_opacity"], value_range=d["value_range"]),
-                  camera=cam, volume_sampling_rate=d["volume_sampling_rate"], clipping_box=d["clipping_box"])
+                  camera=cam, volume_sampling_rate=d["volume_sampling_rate"], clipping_box=d["clipping_box"], slices=tuple(d["slices"]))
     return scene, cam

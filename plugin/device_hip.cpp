@@ -12,6 +12,7 @@
 #include "../include/ovr_hip.h"
 #include "isovalues_env.hpp"
 #include "orthographic_env.hpp"
+#include "slices_env.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -221,6 +222,26 @@ public:
           throw std::runtime_error("[hip] OVR_HIP_AO_SAMPLES expects an integer in 0 ... 16, OVR_HIP_AO_DISTANCE a distance > 0 or inf");
         check(ovr_hip_set_ambient_occlusion(h, k, dist));
         if (!quiet) std::fprintf(stderr, "[hip] ambient occlusion: %d samples within %g\n", k, (double)dist);
+      }
+      // Slices (ovr_hip_set_slices): OVR_HIP_SLICES="px,py,pz,nx,ny,nz[,thickness[,max|min|mean]];..." draws up to four cut planes (thickness 0, the default)
+      // or thick slabs (world units along the normal; inf: the whole box) in the march's place, coloured by the scene's transfer function.  Unset: nothing is called
+      if (const char* sv = std::getenv("OVR_HIP_SLICES")) {
+        ovrhip_plugin::SliceEnv e[OVR_HIP_MAX_SLICES];
+        const int n = ovrhip_plugin::parse_slices(sv, e, OVR_HIP_MAX_SLICES); // (the whole string: trailing text is an error, not a shorter list)
+        if (n < 1) throw std::runtime_error("[hip] OVR_HIP_SLICES expects one to four slices px,py,pz,nx,ny,nz[,thickness[,max|min|mean]] separated by semicolons");
+        ovr_hip_slice sl[OVR_HIP_MAX_SLICES];
+        for (int k = 0; k < n; ++k) {
+          for (int a = 0; a < 3; ++a) { sl[k].point[a] = e[k].point[a]; sl[k].normal[a] = e[k].normal[a]; }
+          sl[k].thickness = e[k].thickness;
+          sl[k].mode = e[k].mode;
+        }
+        check(ovr_hip_set_slices(h, sl, n));
+        if (!quiet)
+          for (int k = 0; k < n; ++k)
+            std::fprintf(stderr, "[hip] slice %d: through (%g, %g, %g), normal (%g, %g, %g), %s%s\n", k, (double)e[k].point[0], (double)e[k].point[1], (double)e[k].point[2],
+                         (double)e[k].normal[0], (double)e[k].normal[1], (double)e[k].normal[2],
+                         e[k].thickness > 0.f ? (e[k].mode == 1 ? "a maximum slab" : e[k].mode == 2 ? "a minimum slab" : "a mean slab") : "a plane",
+                         e[k].thickness > 0.f ? (std::string(" of thickness ") + std::to_string(e[k].thickness)).c_str() : "");
       }
     }
     commit();

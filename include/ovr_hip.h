@@ -548,7 +548,7 @@ int ovr_hip_get_ambient_occlusion_directions(const ovr_hip_renderer* r, float* o
  * transfer function (colours and range) and grid convention.  Queued, applied at commit; every call resets the accumulation and voids nothing else; until it is
  * called with n > 0 every frame, counter and kernel is what it was.  n = 0 or slices = NULL: off.  EINVAL (the state stays): n < 0 or n > 4, a null pointer with
  * n > 0, a non-finite point, a normal that is zero, non-finite or not normalisable, a NaN or negative thickness, with thickness > 0 a mode outside 1 ... 3.  A
- * device group forwards the call; ovr_hip_get_slices reports member 0's state.  Not done: translucent slices, volume context around a slice, lighting.
+ * device group forwards the call; ovr_hip_get_slices reports member 0's state.  Not done: translucent slices, lighting (the volume context around a slice: ovr_hip_set_slice_context).
  * Kernels: a plane kernel (every slice a plane: one lane per ray, one tap) and a walk kernel (a slab among them: four lanes per ray, the projection's rounds),
  * each with the clipped / orthographic twins.  Measured (tools/slice_bench.py, profiles/r21_slices.md; MI355X, 1024^3 f32, 1920 x 1080, kernel_ms): one axial plane
  * 0.046, three orthogonal planes 0.050, one oblique plane 0.045, a 32-voxel oblique MAXIMUM slab 0.164 (0.162 with range skipping,
@@ -565,6 +565,46 @@ typedef struct ovr_hip_slices {
 } ovr_hip_slices;
 /* the COMMITTED state, not the queued one */
 int ovr_hip_get_slices(const ovr_hip_renderer* r, ovr_hip_slices* out);
+
+/* Slice context (added within ABI v11: new entry points and one new struct only): the volume marched IN FRONT of the cut planes.  A context
+ * frame is a slice frame in which the unshaded emission-absorption march runs from the ray's entry into the box up to the winning slice; the opaque slice is
+ * composited behind it.  open-volume-renderer_amd/slice_context.py is the arithmetic in numpy, the normative text.  Per pixel sample:
+ *   ray, stage the slice frame's: (t0, t1, hit) and the winner (k, key, ta, tb), met under its rule (a winning slab without a step counts as not met); a ray that is
+ *              not hit gives zeros.
+ *   cut        tc = key if a slice is met, else t1.
+ *   context    the march's primary loop under OVR_HIP_SHADE_NONE with tc in t1's place, operation for operation: alpha = 0, C = 0, tx = t0,
+ *              ty = fminf(tc, t0 + step); while ty > tx and alpha < 0.9999f: tm = 0.5f * (tx + ty), the tap at to_object(fma(tm, d, o)), the march's classification
+ *              (rgb, a_tf), a = opacity_correction(a_tf, base, ty - tx), a' = a * opacity_scale, tr = 1 - alpha, C_ch = fma(tr * clamp01(rgb_ch), a', C_ch),
+ *              alpha = fma(tr, a', alpha), tx = ty, ty = fminf(tx + step, tc).
+ *   slice      composited iff one is met and alpha < 0.9999f (the loop's own condition: a saturated ray neither taps a plane nor walks a slab): v the slice
+ *              frame's, c = its clamped colour at v, tr = 1 - alpha, C_ch = fma(tr * c_ch, 1, C_ch), alpha = fma(tr, 1, alpha); the layer (the buffer mapped as
+ *              `grad`) is (v, t_k, k + 1) when the slice was composited, else zeros.
+ *   sample     a = alpha, rgb = C / a per channel if a > 0, else 0: the march's un-premultiplied pixel.  Samples per pixel and accumulated frames as the slice frame's.
+ *   counters   samples = context steps fetched + the composited winner's fetched taps; shaded_samples = context steps with a' > 0 (what the march counts under
+ *              SHADE_NONE); skipped_samples 0, shadow counters 0, layout 0, pipeline 1, tuning 0.
+ * Consequences, each exact: with no slice met on a ray and scale 1 the sample is the SHADE_NONE march's bit for bit (a frame whose slices no ray meets IS the
+ * march frame, counters included); with an all-zero alpha table or scale 0 frame and layer are the slice frame's bit for bit; mode OFF is the slice frame, kernel
+ * included.  A context frame honours what a slice frame honours - camera kind, clip box, sampling rate, grid convention, the transfer function's colours and
+ * range, samples per pixel, jitter, everything behind the pixel - and the transfer function's alpha table.  THE CONTEXT IS ALWAYS UNSHADED: the shading mode is
+ * ignored, as are light, material, shadow cache, ambient occlusion, pipeline, LDS staging and layout choice; it reads the general layout; the tuner and the
+ * adaptive-skipping probe are neither asked nor fed.  While empty-space skipping is committed a context frame still fetches every step, a slab inside it is not
+ * range-skipped and ovr_hip_get_slices().range_skipping reads 0.
+ * Queued, applied at commit, recorded with the other frame kinds: every call resets the accumulation and voids nothing else; until it is called with a mode other
+ * than OFF every frame, counter and kernel is what it was.  The mode is kept while no slice is committed and takes effect when n > 0.  opacity_scale is ignored,
+ * and stored as 1, in mode OFF.  EINVAL (the state stays): an unknown mode; in mode FRONT an opacity_scale that is NaN, negative or above 1.  A device group
+ * forwards the call; ovr_hip_get_slice_context reports member 0's state.
+ * Not done: a shaded context, majorant (empty-space) skipping of the context march, range skipping of a slab under context, translucent slices.
+ * Kernel: slice_context_kernel, one per general voxel type, addressing mode and camera, on the clipped box test alone (the unit box without a clip box) - four
+ * lanes per ray, rounds of 16 steps, the transfer function in LDS.  Measured: tools/slice_context_bench.py, profiles/r22_slice_context.md. */
+#define OVR_HIP_SLICE_CONTEXT_OFF 0
+#define OVR_HIP_SLICE_CONTEXT_FRONT 1
+int ovr_hip_set_slice_context(ovr_hip_renderer* r, int32_t mode, float opacity_scale);
+typedef struct ovr_hip_slice_context {
+  int32_t mode;          /* COMMITTED */
+  float opacity_scale;
+  int32_t active;        /* 1: the next frame is a context frame - mode FRONT and n > 0 slices committed */
+} ovr_hip_slice_context;
+int ovr_hip_get_slice_context(const ovr_hip_renderer* r, ovr_hip_slice_context* out);
 
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
@@ -738,6 +778,11 @@ int ovr_hip_isosurface_ao_floats(ovr_hip_renderer* r, const float* org_device, c
  * slice's index + 1 or 0, v, t_k, steps walked - 1 for a plane); zeros for a ray that meets nothing.  ESTATE without a volume or without committed slices;
  * EINVAL: a null pointer, n < 0. */
 int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t range_skipping);
+/* a context ray as the kernel evaluates it (added with the slice context): n world-space rays as for ovr_hip_slice_floats through the device function the context
+ * frame's kernel calls, with the COMMITTED slices, opacity scale, transfer function, volume transform, sampling rate and clip box.  Per ray 8 floats: (the
+ * composited slice's index + 1 or 0, v, t_k, context steps taken, r, g, b, a of the pixel sample).  ESTATE without a volume, without committed slices or while the
+ * committed context mode is OFF; EINVAL: a null pointer, n < 0. */
+int ovr_hip_slice_context_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

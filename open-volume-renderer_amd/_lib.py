@@ -185,6 +185,17 @@ class Slices(C.Structure):
     ]
 
 
+SLICE_CONTEXT_OFF, SLICE_CONTEXT_FRONT = 0, 1
+
+
+class SliceContext(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("opacity_scale", C.c_float),
+        ("active", C.c_int32),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -300,6 +311,9 @@ SYMBOLS = {
     "ovr_hip_set_slices": (C.c_int, [_H, C.POINTER(Slice), C.c_int32]),
     "ovr_hip_get_slices": (C.c_int, [_H, C.POINTER(Slices)]),
     "ovr_hip_slice_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_slice_context": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "ovr_hip_get_slice_context": (C.c_int, [_H, C.POINTER(SliceContext)]),
+    "ovr_hip_slice_context_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

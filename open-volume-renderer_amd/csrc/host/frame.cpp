@@ -313,6 +313,10 @@ void fill_slice_params(const ovr_hip_renderer* r, RayMarchParams& q)
     q.slice_half[k] = on ? 0.5f * p.thickness[k] : 0.f;
     q.slice_mode[k] = on && p.thickness[k] > 0.f ? p.mode[k] : 0; // 0: a plane
   }
+  // the context is kept while no slice is committed and takes effect when n > 0
+  const SliceContextP& c = r->slice_context.current;
+  q.slice_context = (p.n > 0 && c.mode == OVR_HIP_SLICE_CONTEXT_FRONT) ? 1 : 0;
+  q.slice_context_scale = c.scale;
 }
 // a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces or the slices
 static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0 || P.slice_n > 0; }

@@ -97,8 +97,12 @@ constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clip
 // interval, the winning slice's mode a run-time value; without one the plane kernel, one lane per ray, which has nothing to skip.  The orthographic twins exist
 // on the clipped kernels alone, under the rule the projection's follow
 constexpr int kMaxSlices = 4; // include/ovr_hip.h OVR_HIP_MAX_SLICES
-constexpr bool slice_variant_exists(bool walks, int am, bool skip, bool clipped, bool orthographic = false)
+// context (open-volume-renderer_amd/slice_context.py): slice_context_kernel<VT, am, orthographic>, the unshaded march in front of the winning
+// slice - ONE kernel for plane-only and slab sets alike (`walks` is not read), like the translucent isosurface twins ON THE CLIPPED VARIANTS ALONE (a frame
+// without a clip box runs it with the unit box), for both cameras; it fetches every step: no skipping twin
+constexpr bool slice_variant_exists(bool walks, int am, bool skip, bool clipped, bool orthographic = false, bool context = false)
 {
+  if (context) return clipped && !skip && am >= 0 && am <= 4;
   if (orthographic && !clipped) return false;
   if (skip && !walks) return false; // one tap per ray: no fetch to drop
   return am >= 0 && am <= 4;
@@ -159,6 +163,7 @@ struct LaunchFacts {
   int slices = 0;                     // the number of committed slices; > 0: a slice frame - `isosurfaces` and `projection` are kept but not drawn, shading, pool, majorants and LDS staging are not read
   bool slice_walks = false;           // one of the committed slices is a slab (thickness > 0): the frame takes the walk kernel
   bool slice_extremum = false;        // one of the committed slabs is a MAXIMUM or MINIMUM slab: the only ones range skipping drops fetches of
+  bool slice_context = false;         // the slice context is committed in mode FRONT (ovr_hip_set_slice_context): a slice frame takes the context kernel - read only while slices > 0
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -183,7 +188,8 @@ struct LaunchPlan {
   bool error = false;                 // the frame cannot be launched (hipErrorInvalidValue)
   bool ambient_occlusion = false;     // an isosurface frame's kernel is the AO twin of the translucent one (isosurface.translucent and isosurface.clipped are set)
   // a slice frame (LaunchFacts::slices > 0): slice_plane_kernel or slice_walk_kernel in the march's place, nothing else of the plan but `am` is read
-  struct Slices { bool on = false, walks = false, skip = false, clipped = false; size_t lds_bytes = 0; } slices;
+  // (context: slice_context_kernel - the unshaded march in front of the slices, with the transfer function in LDS behind the axis tables)
+  struct Slices { bool on = false, walks = false, skip = false, clipped = false; size_t lds_bytes = 0; bool context = false; } slices;
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -261,10 +267,16 @@ inline LaunchPlan plan_slices(const LaunchFacts& f, const LaunchOverrides& o)
   LaunchPlan pl;
   const Addressing a = plan_addressing(f, o);
   if (a.error || f.slices < 1 || f.slices > kMaxSlices || f.quad) { pl.error = true; return pl; }
-  const WalkFrame w = plan_walk_frame(pl, f, a.am);
+  WalkFrame w = plan_walk_frame(pl, f, a.am, f.slice_context);
+  if (f.slice_context) { // the march's classification per step: the transfer function in LDS behind the tables, as the march has it (0: it does not fit)
+    const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+    if (tf == 0) { pl = LaunchPlan(); pl.error = true; return pl; }
+    w.lds_bytes = pl.march_lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, a.am)) + tf, (size_t)kWaves * kCounterWords * 4);
+  }
   pl.slices.on = true;
   pl.slices.walks = f.slice_walks;
-  pl.slices.skip = f.slice_walks && f.slice_extremum && f.ranges;
+  pl.slices.context = f.slice_context;
+  pl.slices.skip = !f.slice_context && f.slice_walks && f.slice_extremum && f.ranges; // a context frame fetches every step, a slab's included
   pl.slices.clipped = w.clipped;
   pl.slices.lds_bytes = w.lds_bytes;
   return pl;
@@ -322,7 +334,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
-  if (pl.slices.on) return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic);
+  if (pl.slices.on) return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic, pl.slices.context);
   if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion);
   if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
@@ -346,5 +358,8 @@ static_assert(isosurface_variant_exists(1, 0, false, true, false, true, true) &&
 static_assert(slice_variant_exists(false, 0, false, true, true) && slice_variant_exists(true, 4, true, true, true) && !slice_variant_exists(true, 0, true, false, true)
                 && !slice_variant_exists(false, 0, false, false, true) && !slice_variant_exists(false, 0, true, true),
               "the slice kernels: orthographic on the clipped variants alone; the plane kernel has no skipping twin");
+static_assert(slice_variant_exists(false, 0, false, true, false, true) && slice_variant_exists(true, 4, false, true, true, true) && !slice_variant_exists(true, 0, false, false, false, true)
+                && !slice_variant_exists(true, 0, true, true, false, true),
+              "the slice context kernel: on the clipped variants alone, for both cameras, without a skipping twin");
 
 } // namespace ovrhip

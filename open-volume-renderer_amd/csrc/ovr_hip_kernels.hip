@@ -17,6 +17,7 @@
 #include "ovr_hip_device.h"
 #include "ovr_hip_isosurface_ao.h"
 #include "ovr_hip_slices.h"
+#include "ovr_hip_slice_context.h"
 #include "ovr_hip_update.h"
 
 namespace ovrhip {
@@ -1025,6 +1026,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
     f.slice_walks = f.slice_walks || p.slice_mode[k] != 0;
     f.slice_extremum = f.slice_extremum || p.slice_mode[k] == kProjectMaximum || p.slice_mode[k] == kProjectMinimum;
   }
+  f.slice_context = p.slice_n > 0 && p.slice_context != 0;
   return plan_launch(f, o);
 }
 
@@ -1080,7 +1082,9 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template IsosurfaceKernels isosurface_kernels_of<E, false>(const LaunchPlan&);       \
   extern template IsosurfaceLayersKernels isosurface_kernels_of<E, true>(const LaunchPlan&);
 #define OVR_X_AO(E, NAME, BASE, LAYOUT) extern template IsosurfaceAoKernels isosurface_ao_kernels_of<E>(const LaunchPlan&);
-#define OVR_X_SLICES(E, NAME, BASE, LAYOUT) extern template SliceKernels slice_kernels_of<E>(const LaunchPlan&);
+#define OVR_X_SLICES(E, NAME, BASE, LAYOUT)                                          \
+  extern template SliceKernels slice_kernels_of<E>(const LaunchPlan&);               \
+  extern template SliceContextKernels slice_context_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
 OVR_VOXEL_TYPES(OVR_X_SLICES)
@@ -1097,12 +1101,15 @@ struct PlanKernels {
   IsosurfaceLayersFloatsKernel isosurface_layers_floats = nullptr;
   IsosurfaceAoFloatsKernel isosurface_ao_floats = nullptr;
   SliceFloatsKernel slice_floats = nullptr;
+  SliceContextFloatsKernel slice_context_floats = nullptr;
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   PlanKernels k;
   if (plan.error) return k;
-  if (plan.slices.on)
+  if (plan.slices.on && plan.slices.context)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_context_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_context_floats = v.floats; });
+  else if (plan.slices.on)
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_floats = v.floats; });
   else if (plan.isosurface.on && plan.ambient_occlusion) {
     if (p.ao_dirs && p.ao_samples > 0 && p.ao_samples <= kAoMaxSamples) // (the AO kernels read the direction table: no table, no kernel)
@@ -2069,6 +2076,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
 {
   RayMarchParams q = p;
   q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
+  q.slice_context = 0;
   q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
@@ -2147,6 +2155,21 @@ hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const 
   q.slice_n = p.slice_n;
   const LaunchPlan pl = plan_raymarch(q);
   const SliceFloatsKernel kern = plan_kernels(q, pl).slice_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
+}
+
+// known-answer entry of the slice context: the context kernel's twin of the general layout's type at the addressing mode a context frame takes for it
+hipError_t launch_slice_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if (p.slice_n < 1 || p.slice_n > kMaxSlices || !p.tf_color || !p.tf_alpha) return hipErrorInvalidValue;
+  RayMarchParams q = query_params(p, false);
+  q.slice_n = p.slice_n;
+  q.slice_context = 1;
+  const LaunchPlan pl = plan_raymarch(q);
+  const SliceContextFloatsKernel kern = plan_kernels(q, pl).slice_context_floats;
   const unsigned int blocks = quad_ray_blocks(n);
   if (!kern || !blocks) return hipErrorInvalidValue;
   return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);

@@ -425,6 +425,38 @@ class DeviceHIP:
         o = out.cpu().numpy()
         return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64)
 
+    # the slice context (include/ovr_hip.h ovr_hip_set_slice_context; slice_context.py is the arithmetic): the unshaded march from the ray's entry up to the winning
+    # slice, the opaque slice composited behind it.  Queued, applied at commit; every call resets the accumulation; kept while no slice is committed.
+    def set_slice_context(self, mode, opacity_scale=1.0):
+        """mode: SLICE_CONTEXT_OFF (0) or SLICE_CONTEXT_FRONT (1); opacity_scale in [0, 1] multiplies every corrected opacity of the context (ignored, and
+        stored as 1, in mode OFF).  ValueError where the ABI says EINVAL"""
+        code = self._lib.ovr_hip_set_slice_context(self._h, int(mode), float(opacity_scale))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def slice_context(self):
+        """ovr_hip_slice_context, the COMMITTED state: mode, opacity_scale, active (1: the next frame is a context frame)"""
+        c = L.SliceContext()
+        L.check(self._lib.ovr_hip_get_slice_context(self._h, C.byref(c)))
+        return c
+
+    def slice_context_rays(self, org, direction):
+        """context rays as the kernel evaluates them (ovr_hip_slice_context_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given -
+        -> k (n,) int64 - the composited slice's index + 1, 0: none -, v (n,), t_k (n,) float32, context steps taken (n,) int64, rgba (n, 4) float32 of the pixel
+        sample, with the committed slices, context, transfer function, volume, sampling rate and clip box"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("slice_context_rays: org and direction hold three floats per ray")
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_slice_context_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n))
+        o = out.cpu().numpy()
+        return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
+
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
     def set_isosurfaces(self, values=(), opacities=None):

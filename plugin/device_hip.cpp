@@ -13,6 +13,7 @@
 #include "isovalues_env.hpp"
 #include "orthographic_env.hpp"
 #include "slices_env.hpp"
+#include "slice_context_env.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -242,6 +243,14 @@ public:
                          (double)e[k].normal[0], (double)e[k].normal[1], (double)e[k].normal[2],
                          e[k].thickness > 0.f ? (e[k].mode == 1 ? "a maximum slab" : e[k].mode == 2 ? "a minimum slab" : "a mean slab") : "a plane",
                          e[k].thickness > 0.f ? (std::string(" of thickness ") + std::to_string(e[k].thickness)).c_str() : "");
+      }
+      // Slice context (ovr_hip_set_slice_context): OVR_HIP_SLICE_CONTEXT=<scale in [0, 1]> beside OVR_HIP_SLICES marches the unshaded volume in front of the
+      // slices, every corrected opacity multiplied by the scale.  Unset: OFF, nothing is called
+      if (const char* cv = std::getenv("OVR_HIP_SLICE_CONTEXT")) {
+        float scale = 1.f;
+        if (!ovrhip_plugin::parse_slice_context(cv, &scale)) throw std::runtime_error("[hip] OVR_HIP_SLICE_CONTEXT expects one opacity scale in [0, 1]");
+        check(ovr_hip_set_slice_context(h, OVR_HIP_SLICE_CONTEXT_FRONT, scale));
+        if (!quiet) std::fprintf(stderr, "[hip] slice context: the volume in front of the slices, opacity scale %g\n", (double)scale);
       }
     }
     commit();

@@ -606,6 +606,50 @@ typedef struct ovr_hip_slice_context {
 } ovr_hip_slice_context;
 int ovr_hip_get_slice_context(const ovr_hip_renderer* r, ovr_hip_slice_context* out);
 
+/* Isosurface context (added within ABI v11: new entry points and one new struct only): the volume marched AROUND the level sets.  In a
+ * context frame ONE walk both composites the unshaded emission-absorption march and finds, shades and composites every crossing of the committed isovalues, each in
+ * its place along the ray: a bone surface inside translucent soft tissue.  open-volume-renderer_amd/isosurface_context.py is the arithmetic in numpy, the normative
+ * text.  Per pixel sample, float32 throughout:
+ *   ray, steps the isosurface frame's: (t0, t1, hit) of the (clipped) box test, tx_0 = t0, ty_0 = fminf(t1, t0 + step), tm_i = 0.5f * (tx_i + ty_i), tx_{i+1} = ty_i,
+ *              ty_{i+1} = fminf(tx_{i+1} + step, t1); s_i the tap at to_object(fma(tm_i, d, o)).
+ *   state      A = 0, C = 0, layer unset; step i exists while ty_i > tx_i and A < 0.9999f - the march's loop condition, tested before every step.
+ *   step i     1. events, if i >= 1 and side(s_{i-1}) != side(s_i): the translucent frame's events of the step in its order (ovr_hip_set_isosurface_layers), each with
+ *              its t*_k, pos*, normal, shade factor and colour c_k, composited by its expressions with the isovalue's own opacity alpha_k (the scale does not touch
+ *              it): tr = 1 - A, C_ch = fma(tr * c_ch, alpha_k, C_ch), A = fma(tr, alpha_k, A).  The ray's first event sets the layer (iso_k, t*_k, 1).
+ *              A >= 0.9999f behind an event ends the ray there: later events of the step and the step's own volume sample are not taken.
+ *              2. the volume sample, the march's under OVR_HIP_SHADE_NONE, operation for operation: (rgb, a_tf) the march's classification of s_i,
+ *              a = opacity_correction(a_tf, base, ty_i - tx_i), a' = a * opacity_scale, tr = 1 - A, C_ch = fma(tr * clamp01(rgb_ch), a', C_ch), A = fma(tr, a', A).
+ *              (The surface of step i lies between tm_{i-1} and tm_i, in front of sample i: hence this order.)
+ *   sample     a = A, rgb = C / A per channel if A > 0, else 0.  Samples per pixel and accumulated frames as the isosurface frame's; everything behind the pixel
+ *              works unchanged.
+ *   shading    the events honour the committed shading mode, light and material exactly as an isosurface frame's do; under OVR_HIP_SHADE_FULL the shadow ray is the
+ *              translucent frame's, cast by the level sets alone with their opacities.
+ *   counters   samples = steps walked (every step fetches: a context frame never range-skips, on the primary walk or on a shadow walk); skipped_samples =
+ *              skipped_shadow_samples = 0; shaded_samples = events composited + volume samples composited with a' > 0; shadow_samples = the steps of all shadow
+ *              walks; layout 0, pipeline 1, tuning 0 (the tuner and the adaptive-skipping probe are neither asked nor fed).
+ * Consequences, each exact (x * 1.0f, fma(tr, 0, A) and fma(p, 0, C) with finite p are exact): with no crossing on any ray and scale 1 frame and counters are the
+ * SHADE_NONE march's bit for bit; with an all-zero alpha table or scale 0 on a volume of finite voxels frame, layer, shaded_samples and the shadow steps are the
+ * translucent isosurface frame's (by its own identity the opaque frame's too) bit for bit, and samples equals that frame's samples + skipped_samples; mode OFF is
+ * the isosurface frame, kernel included.
+ * Queued, applied at commit, recorded with the other frame kinds: every call resets the accumulation and voids nothing else; until it is called with a mode other
+ * than OFF every frame, counter and kernel is what it was.  The mode is kept while no isovalue is committed; `active` = mode VOLUME, n > 0 isovalues committed and no
+ * slices committed (slices keep their precedence).  opacity_scale is ignored, and stored as 1, in mode OFF.  EINVAL (the state stays): an unknown mode; in mode
+ * VOLUME an opacity_scale that is NaN, negative or above 1.  A device group forwards the call; ovr_hip_get_isosurface_context reports member 0's committed state.
+ * Not done: a shaded context (THE CONTEXT IS ALWAYS UNSHADED); volume shadows on the surfaces (the volume casts no shadow on a surface); ambient occlusion (a
+ * committed ovr_hip_set_ambient_occlusion is kept and not used); range and majorant skipping.
+ * Kernel: isosurface_context_kernel, one per general voxel type, addressing mode, shading mode and camera, on the clipped box test alone (the unit box without a
+ * clip box) - four lanes per ray, rounds of 16 steps that end at their first crossing step, the transfer function in LDS.  Measured:
+ * tools/isosurface_context_bench.py, profiles/r23_isosurface_context.md. */
+#define OVR_HIP_ISO_CONTEXT_OFF 0
+#define OVR_HIP_ISO_CONTEXT_VOLUME 1
+int ovr_hip_set_isosurface_context(ovr_hip_renderer* r, int32_t mode, float opacity_scale);
+typedef struct ovr_hip_isosurface_context {
+  int32_t mode;          /* COMMITTED */
+  float opacity_scale;
+  int32_t active;        /* 1: the next frame is a context frame - mode VOLUME, n > 0 isovalues and no slices committed */
+} ovr_hip_isosurface_context;
+int ovr_hip_get_isosurface_context(const ovr_hip_renderer* r, ovr_hip_isosurface_context* out);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -783,6 +827,13 @@ int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org_device, const flo
  * composited slice's index + 1 or 0, v, t_k, context steps taken, r, g, b, a of the pixel sample).  ESTATE without a volume, without committed slices or while the
  * committed context mode is OFF; EINVAL: a null pointer, n < 0. */
 int ovr_hip_slice_context_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n);
+/* an isosurface context ray as the kernel evaluates it (added with the isosurface context): n world-space rays as for ovr_hip_isosurface_layers_floats, four
+ * lanes each, through the device function the context frame's kernel calls, under full shading, with the COMMITTED isovalues, opacities, opacity scale, transfer
+ * function, light, material, volume transform, sampling rate and clip box.  Per ray 8 + 8 * max_events floats (max_events in 1 ... 16): (events composited, A, steps
+ * walked, shadow steps, r, g, b of the pixel sample, volume samples with a' > 0), then ovr_hip_isosurface_layers_floats' record per event (k, t*, the world normal,
+ * the shadow term, A after the event, 0).  ESTATE without a volume, a transfer function or isovalues, or while the committed context mode is OFF; EINVAL: a null
+ * pointer, n < 0, max_events outside 1 ... 16. */
+int ovr_hip_isosurface_context_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t max_events);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -196,6 +196,17 @@ class SliceContext(C.Structure):
     ]
 
 
+ISO_CONTEXT_OFF, ISO_CONTEXT_VOLUME = 0, 1
+
+
+class IsosurfaceContext(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("opacity_scale", C.c_float),
+        ("active", C.c_int32),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -314,6 +325,9 @@ SYMBOLS = {
     "ovr_hip_set_slice_context": (C.c_int, [_H, C.c_int32, C.c_float]),
     "ovr_hip_get_slice_context": (C.c_int, [_H, C.POINTER(SliceContext)]),
     "ovr_hip_slice_context_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "ovr_hip_set_isosurface_context": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "ovr_hip_get_isosurface_context": (C.c_int, [_H, C.POINTER(IsosurfaceContext)]),
+    "ovr_hip_isosurface_context_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -301,6 +301,10 @@ void fill_isosurface_params(const ovr_hip_renderer* r, RayMarchParams& q)
   q.ao_samples = r->d_ao_dirs ? ao.samples : 0;
   q.ao_distance = ao.distance;
   q.ao_dirs = r->d_ao_dirs;
+  // the context is kept while no isovalue is committed and takes effect when n > 0 (slices keep their precedence: plan_launch never reads it under them)
+  const IsoContextP& c = r->isosurface_context.current;
+  q.iso_context = (p.n > 0 && c.mode == OVR_HIP_ISO_CONTEXT_VOLUME) ? 1 : 0;
+  q.iso_context_scale = c.scale;
 }
 void fill_slice_params(const ovr_hip_renderer* r, RayMarchParams& q)
 {

@@ -84,8 +84,12 @@ constexpr int kMaxIsovalues = 4; // include/ovr_hip.h OVR_HIP_MAX_ISOVALUES
 // without a clip box runs them with the unit box, whose bounds give the unclipped test's bits), for both cameras
 // ao (ambient occlusion): K hemisphere walks per event scale the ambient term - twins of the TRANSLUCENT kernels alone (an opaque frame runs
 // them with its all-ones opacities, section 19's identity), under a shading mode that has an ambient term
-constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false, bool translucent = false, bool ao = false)
+// context (open-volume-renderer_amd/isosurface_context.py): isosurface_context_kernel<VT, am, shade, orthographic>, the unshaded march
+// composited around the translucent walk's events - on the clipped variants alone like the translucent twins, for both cameras and the three shading modes; it
+// fetches every step (no skipping twin) and casts no ambient occlusion (no AO twin)
+constexpr bool isosurface_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false, bool translucent = false, bool ao = false, bool context = false)
 {
+  if (context) return clipped && !skip && !ao && translucent && shade >= 0 && shade <= 2 && am >= 0 && am <= 4;
   (void)skip; // both walks and both box tests exist for every variant, the orthographic camera on the clipped test
   if ((orthographic || translucent) && !clipped) return false;
   if (ao && !(translucent && shade >= 1)) return false;
@@ -164,6 +168,7 @@ struct LaunchFacts {
   bool slice_walks = false;           // one of the committed slices is a slab (thickness > 0): the frame takes the walk kernel
   bool slice_extremum = false;        // one of the committed slabs is a MAXIMUM or MINIMUM slab: the only ones range skipping drops fetches of
   bool slice_context = false;         // the slice context is committed in mode FRONT (ovr_hip_set_slice_context): a slice frame takes the context kernel - read only while slices > 0
+  bool isosurface_context = false;    // the isosurface context is committed in mode VOLUME (ovr_hip_set_isosurface_context): an isosurface frame takes the context kernel - read only while isosurfaces > 0 (and slices == 0)
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -181,7 +186,9 @@ struct LaunchPlan {
   // (lds_bytes, here and below: march_lds_bytes on such a frame and 0 on any other - the launches read march_lds_bytes, the plan tests pin both)
   struct Project { int mode = 0; bool skip = false, clipped = false; size_t lds_bytes = 0; } project;
   // an isosurface frame (LaunchFacts::isosurfaces > 0): isosurface_kernel in the march's place, nothing else of the plan but `am` and `shading` is read
-  struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; bool translucent = false; } isosurface;
+  // (context: isosurface_context_kernel - the unshaded march around the level sets, with the transfer function in LDS behind the axis tables; translucent and
+  // clipped are set, skip and ambient_occlusion never)
+  struct Isosurface { bool on = false, skip = false, clipped = false; size_t lds_bytes = 0; bool translucent = false; bool context = false; } isosurface;
   size_t march_lds_bytes = 0, shade_lds_bytes = 0;
   unsigned int lds_brick_offset = 0;  // LDS-staged bricks: where they start, behind the tables and the TF
   int shade_grid_blocks = 0;
@@ -248,12 +255,19 @@ inline LaunchPlan plan_isosurface(const LaunchFacts& f, const LaunchOverrides& o
   const Addressing a = plan_addressing(f, o);
   if (a.error || f.isosurfaces < 1 || f.isosurfaces > kMaxIsovalues || f.quad) { pl.error = true; return pl; }
   const int shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
-  const bool ao = f.ambient_occlusion && shading >= 1; // without an ambient term on the surface the committed samples are kept and not used
-  const WalkFrame w = plan_walk_frame(pl, f, a.am, f.translucent || ao);
+  const bool ctx = f.isosurface_context;
+  const bool ao = !ctx && f.ambient_occlusion && shading >= 1; // without an ambient term on the surface (or under the context) the committed samples are kept and not used
+  WalkFrame w = plan_walk_frame(pl, f, a.am, f.translucent || ao || ctx);
+  if (ctx) { // the march's classification per step: the transfer function in LDS behind the tables, as plan_slices has it under its context (0: it does not fit)
+    const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+    if (tf == 0) { pl = LaunchPlan(); pl.error = true; return pl; }
+    w.lds_bytes = pl.march_lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, a.am)) + tf, (size_t)kWaves * kCounterWords * 4);
+  }
   pl.shading = shading;
   pl.isosurface.on = true;
-  pl.isosurface.skip = f.ranges;
-  pl.isosurface.translucent = f.translucent || ao; // the AO twins are the translucent path's: an opaque frame runs it with its all-ones opacities
+  pl.isosurface.context = ctx;
+  pl.isosurface.skip = !ctx && f.ranges; // a context frame fetches every step, on the primary walk and on a shadow walk
+  pl.isosurface.translucent = f.translucent || ao || ctx; // the AO twins and the context are the translucent path's: an opaque frame runs it with its all-ones opacities
   pl.ambient_occlusion = ao;
   pl.isosurface.clipped = w.clipped;
   pl.isosurface.lds_bytes = w.lds_bytes;
@@ -335,7 +349,8 @@ inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
   if (pl.slices.on) return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic, pl.slices.context);
-  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion);
+  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion,
+                                                             pl.isosurface.context);
   if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
                               pl.cached && !pl.pooled, pl.orthographic) &&
@@ -361,5 +376,9 @@ static_assert(slice_variant_exists(false, 0, false, true, true) && slice_variant
 static_assert(slice_variant_exists(false, 0, false, true, false, true) && slice_variant_exists(true, 4, false, true, true, true) && !slice_variant_exists(true, 0, false, false, false, true)
                 && !slice_variant_exists(true, 0, true, true, false, true),
               "the slice context kernel: on the clipped variants alone, for both cameras, without a skipping twin");
+static_assert(isosurface_variant_exists(0, 0, false, true, false, true, false, true) && isosurface_variant_exists(2, 4, false, true, true, true, false, true)
+                && !isosurface_variant_exists(2, 0, false, false, false, true, false, true) && !isosurface_variant_exists(2, 0, true, true, false, true, false, true)
+                && !isosurface_variant_exists(2, 0, false, true, false, true, true, true) && !isosurface_variant_exists(1, 0, false, true, false, false, false, true),
+              "the isosurface context kernel: a translucent kernel on the clipped variants alone, for both cameras, without a skipping or an AO twin");
 
 } // namespace ovrhip

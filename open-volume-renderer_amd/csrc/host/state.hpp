@@ -87,6 +87,8 @@ struct SliceP {
 };
 // ovr_hip_set_slice_context: the mode (OVR_HIP_SLICE_CONTEXT_*) and the opacity scale in [0, 1], stored as 1 in mode OFF
 struct SliceContextP { int mode = 0; float scale = 1.f; };
+// ovr_hip_set_isosurface_context: the mode (OVR_HIP_ISO_CONTEXT_*) and the opacity scale in [0, 1], stored as 1 in mode OFF
+struct IsoContextP { int mode = 0; float scale = 1.f; };
 // ovr_hip_set_ambient_occlusion: K and the radius (+inf while K == 0: the radius is not read then)
 struct AoP { int samples = 0; float distance = INFINITY; };
 // ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
@@ -233,6 +235,7 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::SliceP> slices; // ovr_hip_set_slices; recorded under kShading like the projection mode.  n > 0: slice frames, whatever isovalues and projection mode are committed
   bool slices_skipped = false;     // the last slice frame ran the range-skipping kernel (ovr_hip_get_slices)
   Queued<ovrhip::host::SliceContextP> slice_context; // ovr_hip_set_slice_context; recorded under kShading like the slices.  Kept while no slice is committed: it takes effect when n > 0
+  Queued<ovrhip::host::IsoContextP> isosurface_context; // ovr_hip_set_isosurface_context; recorded under kShading like the isovalues.  Kept while no isovalue is committed: it takes effect when n > 0 and no slice is committed
   std::vector<float> ao_table;     // the direction table of the committed K, [16][K][3], as uploaded to d_ao_dirs (both follow K at commit)
   float* d_ao_dirs = nullptr;
   Queued<float> rate;

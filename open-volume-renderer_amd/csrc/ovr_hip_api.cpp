@@ -412,6 +412,33 @@ int ovr_hip_get_slice_context(const ovr_hip_renderer* r, ovr_hip_slice_context* 
   return 0;
 }
 
+int ovr_hip_set_isosurface_context(ovr_hip_renderer* r, int32_t mode, float opacity_scale)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (mode != OVR_HIP_ISO_CONTEXT_OFF && mode != OVR_HIP_ISO_CONTEXT_VOLUME) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurface_context: the mode is OFF or VOLUME");
+  IsoContextP p;
+  p.mode = mode;
+  if (mode != OVR_HIP_ISO_CONTEXT_OFF) { // (ignored, and stored as 1, in mode OFF)
+    if (!(opacity_scale >= 0.f && opacity_scale <= 1.f)) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_isosurface_context: the opacity scale lies in [0, 1]");
+    p.scale = opacity_scale;
+  }
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->isosurface_context.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_isosurface_context(m, mode, opacity_scale));
+  return 0;
+}
+
+int ovr_hip_get_isosurface_context(const ovr_hip_renderer* r, ovr_hip_isosurface_context* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_isosurface_context: null argument");
+  const IsoContextP& p = r->isosurface_context.current;
+  std::memset(out, 0, sizeof(*out));
+  out->mode = p.mode;
+  out->opacity_scale = p.scale;
+  out->active = (p.mode == OVR_HIP_ISO_CONTEXT_VOLUME && r->isosurfaces.current.n > 0 && r->slices.current.n == 0) ? 1 : 0; // slices keep their precedence
+  return 0;
+}
+
 int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -762,6 +789,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (!same_bytes(a->ambient_occlusion.current, b->ambient_occlusion.current)) return false;
   if (!same_bytes(a->slices.current, b->slices.current)) return false;
   if (!same_bytes(a->slice_context.current, b->slice_context.current)) return false;
+  if (!same_bytes(a->isosurface_context.current, b->isosurface_context.current)) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -863,11 +891,13 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
     const SliceP sl = r->slices.current;
     const SliceContextP sc = r->slice_context.current;
     const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update(), set_a = r->ambient_occlusion.update(), set_l = r->slices.update();
-    const bool set_c = r->slice_context.update();
-    ch.note(kShading, set_s || set_p || set_i || set_a || set_l || set_c,
+    const IsoContextP ic = r->isosurface_context.current;
+    const bool set_c = r->slice_context.update(), set_ic = r->isosurface_context.update();
+    ch.note(kShading, set_s || set_p || set_i || set_a || set_l || set_c || set_ic,
             shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0 ||
               std::memcmp(&ao, &r->ambient_occlusion.current, sizeof(AoP)) != 0 || std::memcmp(&sl, &r->slices.current, sizeof(SliceP)) != 0 ||
-              sc.mode != r->slice_context.current.mode || !(sc.scale == r->slice_context.current.scale));
+              sc.mode != r->slice_context.current.mode || !(sc.scale == r->slice_context.current.scale) ||
+              ic.mode != r->isosurface_context.current.mode || !(ic.scale == r->isosurface_context.current.scale));
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
   }
@@ -1500,6 +1530,26 @@ int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org, cons
   q.mc_ranges = projection_ranges(r);
   if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: the resident volume has no macrocell ranges");
   HIP_TRY(launch_isosurface_layers_floats(q, org, dir, out, n, max_events, range_skipping != 0, r->stream()));
+  HIP_TRY(hipStreamSynchronize(r->stream()));
+  return 0;
+}
+
+int ovr_hip_isosurface_context_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events)
+{
+  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_context_floats: bad arguments");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no volume was set");
+  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no isovalue is committed (ovr_hip_set_isosurfaces)");
+  if (r->isosurface_context.current.mode != OVR_HIP_ISO_CONTEXT_VOLUME)
+    return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no isosurface context is committed (ovr_hip_set_isosurface_context)");
+  if (!r->d_tf_color || !r->d_tf_alpha) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no transfer function was committed");
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them
+  q.tf_color = r->d_tf_color; q.tf_alpha = r->d_tf_alpha; // the committed tables, as a frame binds them
+  q.n_color = r->n_color; q.n_alpha = r->n_alpha;
+  fill_isosurface_params(r, q);
+  HIP_TRY(launch_isosurface_context_floats(q, org, dir, out, n, max_events, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
 }

@@ -290,6 +290,11 @@ struct RayMarchParams {
   // everything else, like the slice fields: no other kernel reads them
   int slice_context;
   float slice_context_scale;
+  // the isosurface context (ovr_hip_set_isosurface_context; open-volume-renderer_amd/isosurface_context.py is the arithmetic): iso_context != 0 with iso_n > 0 and
+  // slice_n == 0 = the frame is isosurface_context_kernel's - the unshaded march composited around the level sets' events, every corrected opacity multiplied
+  // by iso_context_scale.  Behind everything else: no other kernel reads them
+  int iso_context;
+  float iso_context_scale;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -362,6 +367,11 @@ hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const 
 // 8 floats each: the composited slice's index + 1 (0: none), v, t_k, context steps taken, then r, g, b, a of the pixel sample; four lanes per ray.  p.slice_*:
 // the slices and p.slice_context_scale; the transfer function as a frame binds it (hipErrorInvalidValue without slices, tables or for a replica's type)
 hipError_t launch_slice_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, hipStream_t stream);
+// known-answer entry of the isosurface context (isosurface_context_ray in ovr_hip_isosurface_context.h, the function the context frame's kernel calls, under full
+// shading): n world-space rays -> 8 + 8 max_events floats each: (events composited, A, steps walked, shadow steps, r, g, b of the pixel sample, volume samples
+// with a' > 0), then launch_isosurface_layers_floats' record per event; four lanes per ray.  out is zeroed first.  p.iso_*: the level sets and
+// p.iso_context_scale; the transfer function as a frame binds it (hipErrorInvalidValue without isovalues, tables or for a replica's type)
+hipError_t launch_isosurface_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

@@ -18,6 +18,7 @@
 #include "ovr_hip_isosurface_ao.h"
 #include "ovr_hip_slices.h"
 #include "ovr_hip_slice_context.h"
+#include "ovr_hip_isosurface_context.h"
 #include "ovr_hip_update.h"
 
 namespace ovrhip {
@@ -1027,6 +1028,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
     f.slice_extremum = f.slice_extremum || p.slice_mode[k] == kProjectMaximum || p.slice_mode[k] == kProjectMinimum;
   }
   f.slice_context = p.slice_n > 0 && p.slice_context != 0;
+  f.isosurface_context = p.iso_n > 0 && p.iso_context != 0;
   return plan_launch(f, o);
 }
 
@@ -1084,7 +1086,8 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
 #define OVR_X_AO(E, NAME, BASE, LAYOUT) extern template IsosurfaceAoKernels isosurface_ao_kernels_of<E>(const LaunchPlan&);
 #define OVR_X_SLICES(E, NAME, BASE, LAYOUT)                                          \
   extern template SliceKernels slice_kernels_of<E>(const LaunchPlan&);               \
-  extern template SliceContextKernels slice_context_kernels_of<E>(const LaunchPlan&);
+  extern template SliceContextKernels slice_context_kernels_of<E>(const LaunchPlan&); \
+  extern template IsosurfaceContextKernels isosurface_context_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
 OVR_VOXEL_TYPES(OVR_X_SLICES)
@@ -1102,6 +1105,7 @@ struct PlanKernels {
   IsosurfaceAoFloatsKernel isosurface_ao_floats = nullptr;
   SliceFloatsKernel slice_floats = nullptr;
   SliceContextFloatsKernel slice_context_floats = nullptr;
+  IsosurfaceContextFloatsKernel isosurface_context_floats = nullptr;
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
@@ -1111,6 +1115,8 @@ static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_context_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_context_floats = v.floats; });
   else if (plan.slices.on)
     dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_floats = v.floats; });
+  else if (plan.isosurface.on && plan.isosurface.context)
+    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_context_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_context_floats = v.floats; });
   else if (plan.isosurface.on && plan.ambient_occlusion) {
     if (p.ao_dirs && p.ao_samples > 0 && p.ao_samples <= kAoMaxSamples) // (the AO kernels read the direction table: no table, no kernel)
       dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_ao_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_ao_floats = v.floats; });
@@ -2077,6 +2083,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
   RayMarchParams q = p;
   q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0; q.lds_staging = 0;
   q.slice_context = 0;
+  q.iso_context = 0; // (the context's own query puts it back)
   q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
@@ -2203,6 +2210,22 @@ hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float*
   const unsigned int blocks = quad_ray_blocks(n);
   if (!kern || !blocks) return hipErrorInvalidValue;
   if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(4 + 8 * max_events) * sizeof(float), stream)) return e;
+  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
+}
+
+// known-answer entry of the isosurface context: the context kernel's twin of the general layout's type at the addressing mode a context frame takes for it,
+// under full shading.  out is zeroed first
+hipError_t launch_isosurface_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if (p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16 || !p.tf_color || !p.tf_alpha) return hipErrorInvalidValue;
+  RayMarchParams q = query_params(p, false);
+  q.iso_context = 1; q.shading = 2; q.ao_samples = 0;
+  const LaunchPlan pl = plan_raymarch(q);
+  const IsosurfaceContextFloatsKernel kern = plan_kernels(q, pl).isosurface_context_floats;
+  const unsigned int blocks = quad_ray_blocks(n);
+  if (!kern || !blocks) return hipErrorInvalidValue;
+  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(8 + 8 * max_events) * sizeof(float), stream)) return e;
   return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
 }
 

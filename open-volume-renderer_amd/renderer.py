@@ -497,6 +497,43 @@ class DeviceHIP:
         return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), k=e[:, :, 0].astype(np.int64),
                     t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy())
 
+    # the isosurface context (include/ovr_hip.h ovr_hip_set_isosurface_context; isosurface_context.py is the arithmetic): the unshaded march composited around
+    # the level sets' events, one walk for both.  Queued, applied at commit; every call resets the accumulation; kept while no isovalue is committed.
+    def set_isosurface_context(self, mode, opacity_scale=1.0):
+        """mode: ISO_CONTEXT_OFF (0) or ISO_CONTEXT_VOLUME (1); opacity_scale in [0, 1] multiplies every corrected opacity of the volume (ignored, and stored as
+        1, in mode OFF; the isovalues' own opacities are not touched).  ValueError where the ABI says EINVAL"""
+        code = self._lib.ovr_hip_set_isosurface_context(self._h, int(mode), float(opacity_scale))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def get_isosurface_context(self):
+        """ovr_hip_isosurface_context, the COMMITTED state: mode, opacity_scale, active (1: the next frame is a context frame)"""
+        c = L.IsosurfaceContext()
+        L.check(self._lib.ovr_hip_get_isosurface_context(self._h, C.byref(c)))
+        return c
+
+    def isosurface_context_rays(self, org, direction, max_events=8):
+        """context rays as the kernel evaluates them (ovr_hip_isosurface_context_floats; known-answer tests), under full shading: world rays (n, 3), (n, 3) ->
+        dict(events (n,) int64 - composited -, A (n,) float32, steps, shadow_steps, lit (n,) int64 - volume samples with a' > 0 -, rgb (n, 3) float32 of the pixel
+        sample, and per event slot e < max_events k (n, e) int64, t, shadow, A_after (n, e) float32, normal (n, e, 3); zeros behind a ray's events) with the
+        committed isovalues, opacities, context, transfer function, volume, sampling rate, light, material and clip box"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
+            raise RuntimeError("isosurface_context_rays: org and direction hold three floats per ray")
+        m = int(max_events)
+        out = torch.empty((n, 8 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        L.check(self._lib.ovr_hip_isosurface_context_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m))
+        o = out.cpu().numpy()
+        e = o[:, 8:].reshape(n, m, 8)
+        return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), rgb=o[:, 4:7].copy(),
+                    lit=o[:, 7].astype(np.int64), k=e[:, :, 0].astype(np.int64), t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(),
+                    A_after=e[:, :, 6].copy())
+
     # ambient occlusion of the isosurface frames (include/ovr_hip.h ovr_hip_set_ambient_occlusion; isosurface.py is the arithmetic).  Queued, applied at commit;
     # every call resets the accumulation.
     def set_ambient_occlusion(self, samples, distance=float("inf")):

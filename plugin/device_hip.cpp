@@ -14,6 +14,7 @@
 #include "orthographic_env.hpp"
 #include "slices_env.hpp"
 #include "slice_context_env.hpp"
+#include "iso_context_env.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -212,6 +213,14 @@ public:
           }
           std::fprintf(stderr, "\n");
         }
+      }
+      // Isosurface context (ovr_hip_set_isosurface_context): OVR_HIP_ISO_CONTEXT=<scale in [0, 1]> beside OVR_HIP_ISOVALUES marches the unshaded volume around
+      // the level sets in the same walk, every corrected opacity of the volume multiplied by the scale.  Unset: OFF, nothing is called
+      if (const char* cv = std::getenv("OVR_HIP_ISO_CONTEXT")) {
+        float scale = 1.f;
+        if (!ovrhip_plugin::parse_iso_context(cv, &scale)) throw std::runtime_error("[hip] OVR_HIP_ISO_CONTEXT expects one opacity scale in [0, 1]");
+        check(ovr_hip_set_isosurface_context(h, OVR_HIP_ISO_CONTEXT_VOLUME, scale));
+        if (!quiet) std::fprintf(stderr, "[hip] isosurface context: the volume around the level sets, opacity scale %g\n", (double)scale);
       }
       // Ambient occlusion of the isosurface frames (ovr_hip_set_ambient_occlusion): OVR_HIP_AO_SAMPLES=8 casts that many occlusion walks per event,
       // OVR_HIP_AO_DISTANCE=12 cuts them at that many world units (unset: the whole box).  Unset: nothing is called (the scene's own ao_samples is not read)

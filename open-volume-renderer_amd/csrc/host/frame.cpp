@@ -297,11 +297,11 @@ void fill_isosurface_params(const ovr_hip_renderer* r, RayMarchParams& q)
   for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) q.iso_values[k] = k < p.n ? p.v[k] : 0.f;
   for (int k = 0; k < OVR_HIP_MAX_ISOVALUES; ++k) q.iso_opacities[k] = k < p.n ? p.a[k] : 1.f;
   q.iso_translucent = p.translucent() ? 1 : 0;
-  const AoP& ao = r->ambient_occlusion.current; // (the known-answer entries and the lattice's build clear K: launch_*_floats, launch_shadow_cache)
+  const AoP& ao = r->ambient_occlusion.current; // (the known-answer entries and the lattice's build clear K: launch_ray_query, launch_shadow_cache)
   q.ao_samples = r->d_ao_dirs ? ao.samples : 0;
   q.ao_distance = ao.distance;
   q.ao_dirs = r->d_ao_dirs;
-  // the context is kept while no isovalue is committed and takes effect when n > 0 (slices keep their precedence: plan_launch never reads it under them)
+  // the context is kept while no isovalue is committed and takes effect when n > 0 (under committed slices it is bound and not read: committed_frame, launch_plan.hpp)
   const IsoContextP& c = r->isosurface_context.current;
   q.iso_context = (p.n > 0 && c.mode == OVR_HIP_ISO_CONTEXT_VOLUME) ? 1 : 0;
   q.iso_context_scale = c.scale;
@@ -323,7 +323,7 @@ void fill_slice_params(const ovr_hip_renderer* r, RayMarchParams& q)
   q.slice_context_scale = c.scale;
 }
 // a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces or the slices
-static bool in_place_frame(const RayMarchParams& P) { return P.projection != OVR_HIP_PROJECT_OFF || P.iso_n > 0 || P.slice_n > 0; }
+static bool in_place_frame(const RayMarchParams& P) { return ovrhip::committed_frame(P.slice_n, P.iso_n, P.projection) != CommittedFrame::March; }
 
 // step 2, continued: tables, shard, jitter, counters
 static int fill_table_params(ovr_hip_renderer* r)
@@ -659,7 +659,7 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  if (r->projection.current != OVR_HIP_PROJECT_OFF || r->isosurfaces.current.n > 0 || r->slices.current.n > 0) bind_general_layout(r);
+  if (committed_frame(r) != CommittedFrame::March) bind_general_layout(r);
   else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
@@ -830,17 +830,14 @@ static int read_frame_stats(ovr_hip_renderer* r)
   r->stats.frame_index = r->frame_index;
   r->sparse_prev_pixels = r->P.sparse_xy ? r->stats.active_pixels : 0;
   r->stats.skipping_kernels = r->skip.frame_used ? 1 : 0;
-  if (r->plan.project.mode != 0) { // a projection frame: which kernel ran; the adaptive-skipping probe had no say
-    r->projection_skipped = r->plan.project.skip;
-    r->stats.skipping_kernels = r->plan.project.skip ? 1 : 0;
-  }
-  if (r->plan.isosurface.on) { // an isosurface frame, likewise
-    r->isosurface_skipped = r->plan.isosurface.skip;
-    r->stats.skipping_kernels = r->plan.isosurface.skip ? 1 : 0;
-  }
-  if (r->plan.slices.on) { // a slice frame, likewise
-    r->slices_skipped = r->plan.slices.skip;
-    r->stats.skipping_kernels = r->plan.slices.skip ? 1 : 0;
+  // a frame of one kernel in the march's place: which twin ran (the adaptive-skipping probe had no say), kept for the kind's getter
+  switch (frame_kind(r->plan)) {
+  case FrameKind::March: break;
+  case FrameKind::Projection: r->stats.skipping_kernels = r->projection_skipped = r->plan.project.skip; break;
+  case FrameKind::Isosurface: case FrameKind::IsosurfaceLayers: case FrameKind::IsosurfaceAo: case FrameKind::IsosurfaceContext:
+    r->stats.skipping_kernels = r->isosurface_skipped = r->plan.isosurface.skip;
+    break;
+  case FrameKind::SlicePlane: case FrameKind::SliceWalk: case FrameKind::SliceContext: r->stats.skipping_kernels = r->slices_skipped = r->plan.slices.skip; break;
   }
   r->stats.replicas_building = poll_replica_builds(r);
   (void)hipGetLastError(); // hipErrorNotReady of the query is not an error
@@ -930,7 +927,7 @@ int finish_frame_one(ovr_hip_renderer* r)
   r->stats.stale_tiles = 0;
   if (int e = resolve_pool(r)) return e;
   if (int e = read_frame_stats(r)) return e;
-  if (r->plan.project.mode != 0 || r->plan.isosurface.on || r->plan.slices.on) r->stats.tuning = 0; // a projection, isosurface or slice frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
+  if (frame_kind(r->plan) != FrameKind::March) r->stats.tuning = 0; // a projection, isosurface or slice frame feeds neither the tuner nor the automatic pipeline nor the skipping probe
   else {
     const policy::FrameWork w = frame_work(r);
     tune_after_frame(r, w);

@@ -1,8 +1,10 @@
 // launch_plan.hpp - which march and shade kernel a frame takes and what each launch needs, as a pure function of a few facts about the frame:
 // the ONLY statement of the variant rules.  Nothing here calls HIP or knows RayMarchParams: plan_raymarch (ovr_hip_kernels.hip) fills the facts
-// and reads the environment switches, frame_kernels<VT> (ovr_hip_device.h) turns a plan into the two kernels, launch_raymarch launches them, the
-// kernels' static_asserts ask march_variant_exists / shade_variant_exists - and tests/test_launch_plan.py drives the same code on a machine without
-// a GPU.  Every variant renders the same frame bit for bit, so a wrong choice here shows as speed alone: hence the tables of that test.
+// and reads the environment switches, plan_kernels (ovr_hip_kernels.hip) turns a plan into its kernels - a switch over frame_kind to the lookup of the kind's
+// device header, frame_kernels<VT> (ovr_hip_device.h) for the march -, launch_raymarch launches them, launch_ray_query the known-answer twin of a kind's kernel
+// (ray_query.hpp), the kernels' static_asserts ask march_variant_exists / shade_variant_exists - and tests/test_launch_plan.py drives the same code on a
+// machine without a GPU.  Every variant of the march renders the same frame bit for bit, so a wrong choice here shows as speed alone: hence the tables of that test.
+// committed_frame is the ONLY statement of which committed state is drawn, frame_kind the only reading of a plan's kind (tests/test_ray_query_table.py).
 #pragma once
 
 #include <algorithm>
@@ -139,6 +141,21 @@ constexpr int addressing_mode(unsigned long long stored_bytes, int elem_bytes, i
   const size_t fixed = tf_lds_bytes(n_color, n_alpha) + (size_t)kWaves * request_queue_entries(1, false) * kShadeReqBytes + 1024; // TF + the largest request queues + slack
   return ((am == 2 && tables > 64 * 1024) || tables + 16 + fixed > 160 * 1024) ? 3 : am;
 }
+
+// ---- the kind of a frame
+// What is committed decides what is drawn, and THIS is the precedence: slices over isovalues over a projection mode over the march.  Committed state of a lower
+// rank is kept and not drawn - and not read: the isosurface context, the ambient occlusion and the opacities mean nothing under slices.  plan_launch, the
+// `active` fields of the getters (ovr_hip_api.cpp) and the frame's layout and skipping steps (host/frame.cpp) all ask here
+enum class CommittedFrame { March, Projection, Isovalues, Slices };
+constexpr CommittedFrame committed_frame(int slices, int isovalues, int projection)
+{
+  return slices != 0 ? CommittedFrame::Slices : isovalues != 0 ? CommittedFrame::Isovalues : projection != 0 ? CommittedFrame::Projection : CommittedFrame::March;
+}
+static_assert(committed_frame(1, 1, 1) == CommittedFrame::Slices && committed_frame(0, 1, 1) == CommittedFrame::Isovalues && committed_frame(0, 0, 1) == CommittedFrame::Projection
+                && committed_frame(0, 0, 0) == CommittedFrame::March,
+              "slices over isovalues over projection over march");
+// one value per kernel family that can stand in the march's place (frame_kind below reads it off a plan)
+enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext };
 
 // ---- facts -> plan
 struct LaunchFacts {
@@ -298,9 +315,12 @@ inline LaunchPlan plan_slices(const LaunchFacts& f, const LaunchOverrides& o)
 
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
-  if (f.slices != 0) return plan_slices(f, o); // committed isovalues and a committed projection mode are kept but not drawn
-  if (f.isosurfaces != 0) return plan_isosurface(f, o); // a committed projection mode is kept but not drawn
-  if (f.projection != 0) return plan_projection(f, o);
+  switch (committed_frame(f.slices, f.isosurfaces, f.projection)) {
+  case CommittedFrame::Slices: return plan_slices(f, o);
+  case CommittedFrame::Isovalues: return plan_isosurface(f, o);
+  case CommittedFrame::Projection: return plan_projection(f, o);
+  case CommittedFrame::March: break;
+  }
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.orthographic = f.orthographic;
@@ -344,14 +364,30 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   return pl;
 }
 
-// the plan's variants exist - what frame_kernels / project_kernels_of / isosurface_kernels_of (ovr_hip_device.h: tables these predicates fill) then look up (f32_general decides the LDS-staged march alone)
+// the kind of frame a plan draws - the kernel family in the march's place - derived from the plan's own members: nothing is stored, nothing can disagree.  THE
+// one reading of those members: plan_variants_exist, plan_kernels and the launchers of the known-answer queries (ovr_hip_kernels.hip) and what host/frame.cpp does
+// behind a frame all switch over it.  (An error plan reads as the march: plan_variants_exist and plan_kernels ask `error` first)
+inline FrameKind frame_kind(const LaunchPlan& pl)
+{
+  if (pl.slices.on) return pl.slices.context ? FrameKind::SliceContext : pl.slices.walks ? FrameKind::SliceWalk : FrameKind::SlicePlane;
+  if (pl.isosurface.on)
+    return pl.isosurface.context ? FrameKind::IsosurfaceContext : pl.ambient_occlusion ? FrameKind::IsosurfaceAo
+           : pl.isosurface.translucent ? FrameKind::IsosurfaceLayers : FrameKind::Isosurface;
+  return pl.project.mode != 0 ? FrameKind::Projection : FrameKind::March;
+}
+
+// the plan's variants exist - what frame_kernels / project_kernels_of / isosurface_kernels_of ... (the device headers: tables these predicates fill) then look up (f32_general decides the LDS-staged march alone)
 inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
 {
   if (pl.error) return false;
-  if (pl.slices.on) return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic, pl.slices.context);
-  if (pl.isosurface.on) return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion,
-                                                             pl.isosurface.context);
-  if (pl.project.mode != 0) return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
+  switch (frame_kind(pl)) {
+  case FrameKind::SlicePlane: case FrameKind::SliceWalk: case FrameKind::SliceContext:
+    return slice_variant_exists(pl.slices.walks, pl.am, pl.slices.skip, pl.slices.clipped, pl.orthographic, pl.slices.context);
+  case FrameKind::Isosurface: case FrameKind::IsosurfaceLayers: case FrameKind::IsosurfaceAo: case FrameKind::IsosurfaceContext:
+    return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion, pl.isosurface.context);
+  case FrameKind::Projection: return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
+  case FrameKind::March: break;
+  }
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
                               pl.cached && !pl.pooled, pl.orthographic) &&
          (!pl.pooled || shade_variant_exists(pl.shading, pl.am, pl.skip, pl.shade.material, pl.shade.clipped, pl.cached, pl.orthographic));

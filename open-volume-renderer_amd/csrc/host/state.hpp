@@ -379,6 +379,11 @@ namespace ovrhip {
 namespace host __attribute__((visibility("hidden"))) {
 
 inline int set_device(ovr_hip_renderer* r) { HIP_TRY(hipSetDevice(r->device)); return 0; }
+// what the committed state makes the next frame (launch_plan.hpp: slices over isovalues over a projection mode over the march)
+inline ovrhip::CommittedFrame committed_frame(const ovr_hip_renderer* r)
+{
+  return ovrhip::committed_frame(r->slices.current.n, r->isosurfaces.current.n, r->projection.current);
+}
 
 // (see GroupState::mtx; followers are only ever called with their leader's lock held)
 struct GroupLock {

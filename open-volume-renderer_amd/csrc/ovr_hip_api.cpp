@@ -1,13 +1,14 @@
 // ovr_hip_api.cpp - C ABI (include/ovr_hip.h) of the MI355X ray-marching backend: the extern "C" layer of the host-side state machine -
 // create / destroy, the queued setters, commit diffing, render / sync, mapframe, swap and the getters.  The state machine itself lives in
 // host/: state.hpp (the renderer's state), policy.hpp (the automatic decisions, free of HIP), commit_plan.hpp (what a changed parameter invalidates, free of
-// HIP), buffers.cpp, volume.cpp, frame.cpp, group.cpp.
+// HIP), ray_query.hpp (the known-answer ray queries as a table, free of HIP), buffers.cpp, volume.cpp, frame.cpp, group.cpp.
 //
 // Mirrors the host half of the reference's GPU device (citations relative to the reference tree):
 //   queued setters + commit diffing ... ovr/renderer.h:135-285, ovr/devices/optix7/device_impl.cpp:113-197
 //   render / frame_index / reset ...... device_impl.cpp:199-269
 //   double-buffered framebuffer ....... ovr/devices/optix7/optix7_common.h:328-414, device_impl.cpp:102-111,271-281
 // No CPU fallback exists: every entry point needs a HIP device and fails with OVR_HIP_EDEVICE otherwise.
+#include "host/ray_query.hpp"
 #include "host/state.hpp"
 
 #include <chrono>
@@ -408,7 +409,7 @@ int ovr_hip_get_slice_context(const ovr_hip_renderer* r, ovr_hip_slice_context* 
   std::memset(out, 0, sizeof(*out));
   out->mode = p.mode;
   out->opacity_scale = p.scale;
-  out->active = (p.mode == OVR_HIP_SLICE_CONTEXT_FRONT && r->slices.current.n > 0) ? 1 : 0;
+  out->active = (p.mode == OVR_HIP_SLICE_CONTEXT_FRONT && committed_frame(r) == CommittedFrame::Slices) ? 1 : 0;
   return 0;
 }
 
@@ -435,7 +436,7 @@ int ovr_hip_get_isosurface_context(const ovr_hip_renderer* r, ovr_hip_isosurface
   std::memset(out, 0, sizeof(*out));
   out->mode = p.mode;
   out->opacity_scale = p.scale;
-  out->active = (p.mode == OVR_HIP_ISO_CONTEXT_VOLUME && r->isosurfaces.current.n > 0 && r->slices.current.n == 0) ? 1 : 0; // slices keep their precedence
+  out->active = (p.mode == OVR_HIP_ISO_CONTEXT_VOLUME && committed_frame(r) == CommittedFrame::Isovalues) ? 1 : 0;
   return 0;
 }
 
@@ -460,6 +461,7 @@ int ovr_hip_get_ambient_occlusion(const ovr_hip_renderer* r, ovr_hip_ambient_occ
   out->samples = p.samples;
   out->distance = p.distance;
   out->rotations = OVR_HIP_AO_ROTATIONS;
+  // as include/ovr_hip.h defines it - of the next ISOSURFACE frame: committed slices and the isosurface context, under which no frame casts it, are not read
   out->active = p.samples > 0 && r->isosurfaces.current.n > 0 && r->shading.current != OVR_HIP_SHADE_NONE ? 1 : 0;
   return 0;
 }
@@ -1448,129 +1450,79 @@ int ovr_hip_shadow_floats(ovr_hip_renderer* r, const float* pos, float* out, int
   return 0;
 }
 
-int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t mode, int32_t range_skipping)
+// the seven known-answer ray queries: one path, walked by the entry's row of host/ray_query.hpp - what must be committed, which parameters it binds, its record
+namespace {
+static_assert(kQueryEinval == OVR_HIP_EINVAL && kQueryEstate == OVR_HIP_ESTATE && kQueryRotations == OVR_HIP_AO_ROTATIONS && kProjectMaximum == OVR_HIP_PROJECT_MAXIMUM
+                && kProjectMean == OVR_HIP_PROJECT_MEAN,
+              "host/ray_query.hpp restates include/ovr_hip.h");
+int ray_query(ovr_hip_renderer* r, RayQueryId id, const float* org, const float* dir, float* out, int64_t n, int32_t mode = 0, int32_t max_events = 0, int32_t rotation = 0,
+              int32_t range_skipping = 0) // (0: what the entry does not take)
 {
-  if (!r || !org || !dir || !out || n < 0 || mode < OVR_HIP_PROJECT_MAXIMUM || mode > OVR_HIP_PROJECT_MEAN) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_project_floats: bad arguments");
+  const RayQuery& d = kRayQueries[id];
+  RayQueryCall c;
+  c.org = org; c.dir = dir; c.out = out; c.n = n;
+  c.mode = mode; c.max_events = max_events; c.rotation = rotation; c.range_skipping = range_skipping;
+  if (const QueryStatus s = ray_query_arguments(d, r != nullptr, c); s.code) return fail(s.code, s.message);
   if (int e = set_device(r)) return e;
   if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: no volume was set");
+  QueryFacts f;
+  f.volume = r->have_volume;
+  f.slices = r->slices.current.n;
+  f.isovalues = r->isosurfaces.current.n;
+  f.slice_context = r->slice_context.current.mode == OVR_HIP_SLICE_CONTEXT_FRONT;
+  f.isosurface_context = r->isosurface_context.current.mode == OVR_HIP_ISO_CONTEXT_VOLUME;
+  f.ao_samples = r->ambient_occlusion.current.samples;
+  f.transfer_function = r->d_tf_color && r->d_tf_alpha;
+  f.ranges = projection_ranges(r) != nullptr;
+  if (const QueryStatus s = ray_query_preconditions(d, f, c.range_skipping != 0); s.code) return fail(s.code, s.message);
   RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
-  q.mc_ranges = projection_ranges(r);
-  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_project_floats: the resident volume has no macrocell ranges");
-  HIP_TRY(launch_project_floats(q, org, dir, out, n, mode, range_skipping != 0 && mode != OVR_HIP_PROJECT_MEAN, r->stream()));
+  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are read by the context kernels alone)
+  if (d.needs_tf) { // the committed tables, as a frame binds them
+    q.tf_color = r->d_tf_color; q.tf_alpha = r->d_tf_alpha;
+    q.n_color = r->n_color; q.n_alpha = r->n_alpha;
+  }
+  if (d.needs == QueryNeeds::Slices) fill_slice_params(r, q);
+  if (d.needs == QueryNeeds::Isovalues) fill_isosurface_params(r, q);
+  if (d.takes_range_skipping) q.mc_ranges = projection_ranges(r);
+  HIP_TRY(launch_ray_query(id, q, c, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
+}
+} // namespace
+
+int ovr_hip_project_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t mode, int32_t range_skipping)
+{
+  return ray_query(r, kQueryProject, org, dir, out, n, mode, 0, 0, range_skipping);
 }
 
 int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)
 {
-  if (!r || !org || !dir || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_slice_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: no volume was set");
-  if (r->slices.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: no slice is committed (ovr_hip_set_slices)");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
-  fill_slice_params(r, q);
-  q.mc_ranges = projection_ranges(r);
-  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_floats: the resident volume has no macrocell ranges");
-  HIP_TRY(launch_slice_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQuerySlice, org, dir, out, n, 0, 0, 0, range_skipping);
 }
 
 int ovr_hip_slice_context_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n)
 {
-  if (!r || !org || !dir || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_slice_context_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_context_floats: no volume was set");
-  if (r->slices.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_context_floats: no slice is committed (ovr_hip_set_slices)");
-  if (r->slice_context.current.mode != OVR_HIP_SLICE_CONTEXT_FRONT)
-    return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_context_floats: no slice context is committed (ovr_hip_set_slice_context)");
-  if (!r->d_tf_color || !r->d_tf_alpha) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_slice_context_floats: no transfer function was committed");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them
-  q.tf_color = r->d_tf_color; q.tf_alpha = r->d_tf_alpha; // the committed tables, as a frame binds them
-  q.n_color = r->n_color; q.n_alpha = r->n_alpha;
-  fill_slice_params(r, q);
-  HIP_TRY(launch_slice_context_floats(q, org, dir, out, n, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQuerySliceContext, org, dir, out, n);
 }
 
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)
 {
-  if (!r || !org || !dir || !out || n < 0) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: no volume was set");
-  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: no isovalue is committed (ovr_hip_set_isosurfaces)");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
-  fill_isosurface_params(r, q);
-  q.mc_ranges = projection_ranges(r);
-  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_floats: the resident volume has no macrocell ranges");
-  HIP_TRY(launch_isosurface_floats(q, org, dir, out, n, range_skipping != 0, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQueryIsosurface, org, dir, out, n, 0, 0, 0, range_skipping);
 }
 
 int ovr_hip_isosurface_layers_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events, int32_t range_skipping)
 {
-  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_layers_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: no volume was set");
-  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: no isovalue is committed (ovr_hip_set_isosurface_layers)");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
-  fill_isosurface_params(r, q);
-  q.mc_ranges = projection_ranges(r);
-  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_layers_floats: the resident volume has no macrocell ranges");
-  HIP_TRY(launch_isosurface_layers_floats(q, org, dir, out, n, max_events, range_skipping != 0, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQueryIsosurfaceLayers, org, dir, out, n, 0, max_events, 0, range_skipping);
 }
 
 int ovr_hip_isosurface_context_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events)
 {
-  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_context_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no volume was set");
-  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no isovalue is committed (ovr_hip_set_isosurfaces)");
-  if (r->isosurface_context.current.mode != OVR_HIP_ISO_CONTEXT_VOLUME)
-    return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no isosurface context is committed (ovr_hip_set_isosurface_context)");
-  if (!r->d_tf_color || !r->d_tf_alpha) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_context_floats: no transfer function was committed");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them
-  q.tf_color = r->d_tf_color; q.tf_alpha = r->d_tf_alpha; // the committed tables, as a frame binds them
-  q.n_color = r->n_color; q.n_alpha = r->n_alpha;
-  fill_isosurface_params(r, q);
-  HIP_TRY(launch_isosurface_context_floats(q, org, dir, out, n, max_events, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQueryIsosurfaceContext, org, dir, out, n, 0, max_events);
 }
 
 int ovr_hip_isosurface_ao_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t max_events, int32_t rotation, int32_t range_skipping)
 {
-  if (!r || !org || !dir || !out || n < 0 || max_events < 1 || max_events > 16 || rotation < 0 || rotation >= OVR_HIP_AO_ROTATIONS)
-    return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_isosurface_ao_floats: bad arguments");
-  if (int e = set_device(r)) return e;
-  if (int e = finish_frame(r)) return e;
-  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no volume was set");
-  if (r->isosurfaces.current.n < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no isovalue is committed (ovr_hip_set_isosurface_layers)");
-  if (r->ambient_occlusion.current.samples < 1) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: no ambient-occlusion sample is committed (ovr_hip_set_ambient_occlusion)");
-  RayMarchParams q = r->P;
-  fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are not read)
-  fill_isosurface_params(r, q);
-  q.mc_ranges = projection_ranges(r);
-  if (range_skipping && !q.mc_ranges) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_isosurface_ao_floats: the resident volume has no macrocell ranges");
-  HIP_TRY(launch_isosurface_ao_floats(q, org, dir, out, n, max_events, rotation, range_skipping != 0, r->stream()));
-  HIP_TRY(hipStreamSynchronize(r->stream()));
-  return 0;
+  return ray_query(r, kQueryIsosurfaceAo, org, dir, out, n, 0, max_events, rotation, range_skipping);
 }
 
 int ovr_hip_camera_rays(ovr_hip_renderer* r, int32_t frame_index, int32_t sample, float* org_dir, size_t capacity_floats)

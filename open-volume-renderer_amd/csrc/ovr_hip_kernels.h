@@ -341,37 +341,28 @@ hipError_t launch_schedule(const RayMarchParams& p, const unsigned int* src, uns
 // zero the pixels (RGBA, gradient layer, optionally the accumulation buffer) of `n` blocks that are not launched: what their rays' miss would write
 hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* blocks, unsigned int n, int clear_accum, hipStream_t stream);
 
-// known-answer entry of the projections (project_ray in ovr_hip_device.h, the function project_kernel calls): n world-space rays (origin, direction - used as given) ->
-// 4 floats each: v, tm*, steps, fetched steps (four zeros for a ray that is not marched), four lanes per ray.  p.vol: the general layout; p.mc_ranges: the ranges
-// if range_skipping (hipErrorInvalidValue without them, for a replica's type or a mode outside 1 ... 3)
-hipError_t launch_project_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int mode, int range_skipping, hipStream_t stream);
-
-// known-answer entry of the isosurfaces (isosurface_ray in ovr_hip_device.h, the function isosurface_kernel calls, with full shading): n world-space rays -> 8 floats
-// each: hit, isovalue, t*, steps walked, the world normal, the shadow term (zeros for a ray without a hit, but the steps walked), four lanes per ray.  p.iso_n /
-// p.iso_values: the isovalues; p.mc_ranges: the ranges if range_skipping (hipErrorInvalidValue without them, without isovalues or for a replica's type)
-hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream);
-// its translucent twin (isosurface_ray<TRANS>, the function the translucent frame's kernel calls): 4 + 8 max_events floats per ray - (events composited, A, steps
-// walked, shadow steps), then (k, t*, the world normal, shadow, A after the event, 0) per event, the rest zeros - with p.iso_opacities, whatever p.iso_translucent says
-hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int range_skipping,
-                                           hipStream_t stream);
-// the ambient-occlusion twin (isosurface_layers_ao in ovr_hip_isosurface_ao.h, the function the AO frame's kernel calls, with full shading): 8 + 8 max_events floats
-// per ray - (events composited, A, steps walked, shadow steps, the AO walks' steps, the AO walks' fetched steps, 0, 0), then (k, t*, the world normal, shadow, A
-// after the event, O) per event, the rest zeros - with p.ao_samples / p.ao_distance / p.ao_dirs and every ray at the table's rotation `rotation` (0 ... 15)
-hipError_t launch_isosurface_ao_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int rotation, int range_skipping,
-                                       hipStream_t stream);
-// known-answer entry of the slices (slice_ray in ovr_hip_slices.h, the function the walk frame's kernel calls; its stage and its one tap are the plane kernel's):
-// n world-space rays -> 4 floats each: the winning slice's index + 1 (0: nothing met), v, t_k, steps walked (a plane: 1), four lanes per ray.  p.slice_*: the
-// slices; p.mc_ranges: the ranges if range_skipping (hipErrorInvalidValue without them, without slices or for a replica's type)
-hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream);
-// known-answer entry of the slice context (slice_context_ray in ovr_hip_slice_context.h, the function the context frame's kernel calls): n world-space rays ->
-// 8 floats each: the composited slice's index + 1 (0: none), v, t_k, context steps taken, then r, g, b, a of the pixel sample; four lanes per ray.  p.slice_*:
-// the slices and p.slice_context_scale; the transfer function as a frame binds it (hipErrorInvalidValue without slices, tables or for a replica's type)
-hipError_t launch_slice_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, hipStream_t stream);
-// known-answer entry of the isosurface context (isosurface_context_ray in ovr_hip_isosurface_context.h, the function the context frame's kernel calls, under full
-// shading): n world-space rays -> 8 + 8 max_events floats each: (events composited, A, steps walked, shadow steps, r, g, b of the pixel sample, volume samples
-// with a' > 0), then launch_isosurface_layers_floats' record per event; four lanes per ray.  out is zeroed first.  p.iso_*: the level sets and
-// p.iso_context_scale; the transfer function as a frame binds it (hipErrorInvalidValue without isovalues, tables or for a replica's type)
-hipError_t launch_isosurface_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, hipStream_t stream);
+// The known-answer ray queries: n world-space rays (origin, direction - used as given) -> one record of floats each, four lanes per ray, computed by the device
+// function that the frame kernel of the query's kind calls.  host/ray_query.hpp (kRayQueries) holds per query what it needs, which of c's arguments it takes and its
+// record's size; p.vol: the general layout; p.mc_ranges: the ranges if c.range_skipping.  hipErrorInvalidValue: something the query needs is missing from p, a
+// replica's type, an argument out of range, or a plan of another frame kind than the query's.  The records (zeros for a ray that is not marched):
+//   kQueryProject (project_ray, ovr_hip_device.h; c.mode 1 ... 3)   v, tm*, steps, fetched steps
+//   kQuerySlice (slice_ray, ovr_hip_slices.h - the walk kernel's; its stage and its one tap are the plane kernel's; p.slice_*)
+//                                                                   the winning slice's index + 1 (0: nothing met), v, t_k, steps walked (a plane: 1)
+//   kQuerySliceContext (slice_context_ray, ovr_hip_slice_context.h; p.slice_*, p.slice_context_scale, the transfer function as a frame binds it)
+//                                                                   the composited slice's index + 1 (0: none), v, t_k, context steps taken, then r, g, b, a of the pixel sample
+//   kQueryIsosurface (isosurface_ray, ovr_hip_device.h, with full shading; p.iso_n / p.iso_values)
+//                                                                   hit, isovalue, t*, steps walked, the world normal, the shadow term (without a hit: the steps walked alone)
+//   kQueryIsosurfaceLayers (isosurface_ray<TRANS>; p.iso_opacities, whatever p.iso_translucent says; out is zeroed first)
+//                                                                   (events composited, A, steps walked, shadow steps), then per event up to c.max_events
+//                                                                   (k, t*, the world normal, shadow, A after the event, 0)
+//   kQueryIsosurfaceContext (isosurface_context_ray, ovr_hip_isosurface_context.h, under full shading; p.iso_*, p.iso_context_scale, the transfer function; zeroed first)
+//                                                                   (events composited, A, steps walked, shadow steps, r, g, b of the pixel sample, volume samples with a' > 0),
+//                                                                   then kQueryIsosurfaceLayers' record per event
+//   kQueryIsosurfaceAo (isosurface_layers_ao, ovr_hip_isosurface_ao.h, with full shading; p.ao_samples / p.ao_distance / p.ao_dirs, every ray at the table's rotation
+//   c.rotation, 0 ... 15; zeroed first)                             (events composited, A, steps walked, shadow steps, the AO walks' steps, the AO walks' fetched steps, 0, 0),
+//                                                                   then (k, t*, the world normal, shadow, A after the event, O) per event
+struct RayQueryCall; // host/ray_query.hpp
+hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream);
 
 // ---- convergence estimate and adaptive refinement (include/ovr_hip.h ovr_hip_set_convergence)
 // Per 8x8-pixel block b (one wave, lane = 8 * (y & 7) + (x & 7)) after an even frame n:

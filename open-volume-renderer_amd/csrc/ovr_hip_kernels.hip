@@ -20,6 +20,7 @@
 #include "ovr_hip_slice_context.h"
 #include "ovr_hip_isosurface_context.h"
 #include "ovr_hip_update.h"
+#include "host/ray_query.hpp"
 
 namespace ovrhip {
 static_assert(kPoolSubs <= 64 && (kPoolSubs & (kPoolSubs - 1)) == 0, "reduce_counters_kernel reduces the sub-pool counters with one wave");
@@ -1095,39 +1096,41 @@ OVR_VOXEL_TYPES(OVR_X_SLICES)
 #undef OVR_X_AO
 #undef OVR_X_SLICES
 
-// a plan's kernels for the volume's voxel type: the frame's two - a projection's or an isosurface's kernel in the in-place march's place (such a plan is neither
-// pooled nor LDS-staged, march_lds_bytes is that kernel's) - and the known-answer entry's of such a plan.  All nullptr: the plan is an error, or no such variant
+// a plan's kernels for the volume's voxel type: the frame's two - the kernel of another frame kind in the in-place march's place (such a plan is neither pooled nor
+// LDS-staged, march_lds_bytes is that kernel's) - and the known-answer twin of such a kernel, filed by its signature: launch_ray_query holds the plan's kind to
+// the query's before it calls one.  All nullptr: the plan is an error, or no such variant
+typedef void (*QueryKernel)(const RayMarchParams, const float*, const float*, float*, long long);
+typedef void (*QueryEventsKernel)(const RayMarchParams, const float*, const float*, float*, long long, int);        // + max_events
+typedef void (*QueryRotationKernel)(const RayMarchParams, const float*, const float*, float*, long long, int, int); // + max_events, rotation
 struct PlanKernels {
   FrameKernels frame;
-  ProjectFloatsKernel project_floats = nullptr;
-  IsosurfaceFloatsKernel isosurface_floats = nullptr;
-  IsosurfaceLayersFloatsKernel isosurface_layers_floats = nullptr;
-  IsosurfaceAoFloatsKernel isosurface_ao_floats = nullptr;
-  SliceFloatsKernel slice_floats = nullptr;
-  SliceContextFloatsKernel slice_context_floats = nullptr;
-  IsosurfaceContextFloatsKernel isosurface_context_floats = nullptr;
+  QueryKernel query = nullptr;
+  QueryEventsKernel query_events = nullptr;
+  QueryRotationKernel query_rotation = nullptr;
+  void set(QueryKernel k) { query = k; }
+  void set(QueryEventsKernel k) { query_events = k; }
+  void set(QueryRotationKernel k) { query_rotation = k; }
+  template <typename V> void take(const V& v) { frame.march = v.frame; set(v.floats); } // (the pair a *_kernels_of lookup returns)
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
 {
   PlanKernels k;
   if (plan.error) return k;
-  if (plan.slices.on && plan.slices.context)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_context_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_context_floats = v.floats; });
-  else if (plan.slices.on)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = slice_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.slice_floats = v.floats; });
-  else if (plan.isosurface.on && plan.isosurface.context)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_context_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_context_floats = v.floats; });
-  else if (plan.isosurface.on && plan.ambient_occlusion) {
+  const int t = p.vol.type;
+  switch (frame_kind(plan)) {
+  case FrameKind::SliceContext: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(slice_context_kernels_of<decltype(vt)::value>(plan)); }); break;
+  case FrameKind::SlicePlane:
+  case FrameKind::SliceWalk: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(slice_kernels_of<decltype(vt)::value>(plan)); }); break;
+  case FrameKind::IsosurfaceContext: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(isosurface_context_kernels_of<decltype(vt)::value>(plan)); }); break;
+  case FrameKind::IsosurfaceAo:
     if (p.ao_dirs && p.ao_samples > 0 && p.ao_samples <= kAoMaxSamples) // (the AO kernels read the direction table: no table, no kernel)
-      dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_ao_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.isosurface_ao_floats = v.floats; });
+      dispatch_voxel_type<true>(t, [&](auto vt) { k.take(isosurface_ao_kernels_of<decltype(vt)::value>(plan)); });
+    break;
+  case FrameKind::IsosurfaceLayers: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(isosurface_kernels_of<decltype(vt)::value, true>(plan)); }); break;
+  case FrameKind::Isosurface: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(isosurface_kernels_of<decltype(vt)::value, false>(plan)); }); break;
+  case FrameKind::Projection: dispatch_voxel_type(t, [&](auto vt) { k.take(project_kernels_of<decltype(vt)::value>(plan)); }); break;
+  case FrameKind::March: dispatch_voxel_type(t, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); }); break;
   }
-  else if (plan.isosurface.on && plan.isosurface.translucent)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, true>(plan); k.frame.march = v.frame; k.isosurface_layers_floats = v.floats; });
-  else if (plan.isosurface.on)
-    dispatch_voxel_type<true>(p.vol.type, [&](auto vt) { const auto v = isosurface_kernels_of<decltype(vt)::value, false>(plan); k.frame.march = v.frame; k.isosurface_floats = v.floats; });
-  else if (plan.project.mode != 0)
-    dispatch_voxel_type(p.vol.type, [&](auto vt) { const auto v = project_kernels_of<decltype(vt)::value>(plan); k.frame.march = v.frame; k.project_floats = v.floats; });
-  else dispatch_voxel_type(p.vol.type, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); });
   return k;
 }
 
@@ -2139,113 +2142,42 @@ hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float
   return hipGetLastError();
 }
 
-// known-answer entry of the projections: the kernel of the general layout's type at the addressing mode a projection frame takes for it
-hipError_t launch_project_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int mode, int range_skipping, hipStream_t stream)
+// the known-answer ray queries (host/ray_query.hpp): the twin of the frame kernel of the query's kind, of the general layout's type at the addressing mode such a
+// frame takes for it.  What the query does not ask about is scrubbed from the plan's facts, whatever is committed and whatever the last frame drew
+hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream)
 {
-  if (n <= 0) return hipSuccess;
-  if (range_skipping && !p.mc_ranges) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, range_skipping != 0);
-  q.projection = mode; q.iso_n = 0; q.ao_samples = 0; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
+  if (query < 0 || query >= kRayQueryCount) return hipErrorInvalidValue;
+  const RayQuery& d = kRayQueries[query];
+  if (c.n <= 0) return hipSuccess;
+  const bool skip = d.takes_range_skipping && c.range_skipping != 0 && !(d.takes_mode && c.mode == kProjectMean); // (a mean needs every sample: it has no skipping twin)
+  if (skip && !p.mc_ranges) return hipErrorInvalidValue;
+  if (d.needs == QueryNeeds::Slices && (p.slice_n < 1 || p.slice_n > kMaxSlices)) return hipErrorInvalidValue;
+  if (d.needs == QueryNeeds::Isovalues && (p.iso_n < 1 || p.iso_n > kMaxIsovalues)) return hipErrorInvalidValue;
+  if (d.takes_max_events && (c.max_events < 1 || c.max_events > kQueryMaxEvents)) return hipErrorInvalidValue;
+  if (d.takes_rotation && (c.rotation < 0 || c.rotation >= kAoRotations)) return hipErrorInvalidValue;
+  if (d.needs_ao && (p.ao_samples < 1 || p.ao_samples > kAoMaxSamples || !p.ao_dirs)) return hipErrorInvalidValue;
+  if (d.needs_tf && (!p.tf_color || !p.tf_alpha)) return hipErrorInvalidValue;
+  RayMarchParams q = query_params(p, skip);
+  switch (d.kind) {
+  case FrameKind::Projection: q.projection = c.mode; q.iso_n = 0; q.ao_samples = 0; break; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
+  case FrameKind::SliceWalk: q.slice_n = p.slice_n; break;
+  case FrameKind::SliceContext: q.slice_n = p.slice_n; q.slice_context = 1; break;
+  case FrameKind::Isosurface: q.iso_translucent = 0; q.ao_samples = 0; break;       // (the first crossing, opaque, whatever opacities and AO samples are committed)
+  case FrameKind::IsosurfaceLayers: q.iso_translucent = 1; q.ao_samples = 0; break; // (without ambient occlusion, whatever is committed)
+  case FrameKind::IsosurfaceContext: q.iso_context = 1; q.shading = 2; q.ao_samples = 0; break; // (under full shading)
+  case FrameKind::IsosurfaceAo: q.iso_translucent = 1; q.shading = 2; break;        // (with full shading, the committed samples)
+  default: return hipErrorInvalidValue;
+  }
   const LaunchPlan pl = plan_raymarch(q);
-  const ProjectFloatsKernel kern = plan_kernels(q, pl).project_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
-}
-
-// known-answer entry of the slices: the kernel of the general layout's type at the addressing mode a slice frame takes for it
-hipError_t launch_slice_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if ((range_skipping && !p.mc_ranges) || p.slice_n < 1 || p.slice_n > kMaxSlices) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, range_skipping != 0);
-  q.slice_n = p.slice_n;
-  const LaunchPlan pl = plan_raymarch(q);
-  const SliceFloatsKernel kern = plan_kernels(q, pl).slice_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
-}
-
-// known-answer entry of the slice context: the context kernel's twin of the general layout's type at the addressing mode a context frame takes for it
-hipError_t launch_slice_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if (p.slice_n < 1 || p.slice_n > kMaxSlices || !p.tf_color || !p.tf_alpha) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, false);
-  q.slice_n = p.slice_n;
-  q.slice_context = 1;
-  const LaunchPlan pl = plan_raymarch(q);
-  const SliceContextFloatsKernel kern = plan_kernels(q, pl).slice_context_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
-}
-
-// known-answer entry of the isosurfaces: the kernel of the general layout's type at the addressing mode an isosurface frame takes for it
-hipError_t launch_isosurface_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int range_skipping, hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, range_skipping != 0);
-  q.iso_translucent = 0; q.ao_samples = 0; // (the first crossing, opaque, whatever opacities and AO samples are committed)
-  const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceFloatsKernel kern = plan_kernels(q, pl).isosurface_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n);
-}
-
-// known-answer entry of the translucent isosurfaces: the twin of the kernel above, at the addressing mode a translucent frame takes.  out is zeroed first: the
-// kernel writes a ray's header and the events it composited
-hipError_t launch_isosurface_layers_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int range_skipping,
-                                           hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, range_skipping != 0);
-  q.iso_translucent = 1; q.ao_samples = 0; // (without ambient occlusion, whatever is committed)
-  const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceLayersFloatsKernel kern = plan_kernels(q, pl).isosurface_layers_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(4 + 8 * max_events) * sizeof(float), stream)) return e;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
-}
-
-// known-answer entry of the isosurface context: the context kernel's twin of the general layout's type at the addressing mode a context frame takes for it,
-// under full shading.  out is zeroed first
-hipError_t launch_isosurface_context_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if (p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16 || !p.tf_color || !p.tf_alpha) return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, false);
-  q.iso_context = 1; q.shading = 2; q.ao_samples = 0;
-  const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceContextFloatsKernel kern = plan_kernels(q, pl).isosurface_context_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(8 + 8 * max_events) * sizeof(float), stream)) return e;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events);
-}
-
-// known-answer entry of the ambient occlusion: the AO twin of the kernel above with full shading, every ray at the rotation `rotation` of the direction table.
-// out is zeroed first
-hipError_t launch_isosurface_ao_floats(const RayMarchParams& p, const float* org, const float* dir, float* out, int64_t n, int max_events, int rotation, int range_skipping,
-                                       hipStream_t stream)
-{
-  if (n <= 0) return hipSuccess;
-  if ((range_skipping && !p.mc_ranges) || p.iso_n < 1 || p.iso_n > kMaxIsovalues || max_events < 1 || max_events > 16 || rotation < 0 || rotation >= kAoRotations ||
-      p.ao_samples < 1 || p.ao_samples > kAoMaxSamples || !p.ao_dirs)
-    return hipErrorInvalidValue;
-  RayMarchParams q = query_params(p, range_skipping != 0);
-  q.iso_translucent = 1; q.shading = 2;
-  const LaunchPlan pl = plan_raymarch(q);
-  const IsosurfaceAoFloatsKernel kern = plan_kernels(q, pl).isosurface_ao_floats;
-  const unsigned int blocks = quad_ray_blocks(n);
-  if (!kern || !blocks) return hipErrorInvalidValue;
-  if (hipError_t e = hipMemsetAsync(out, 0, (size_t)n * (size_t)(8 + 8 * max_events) * sizeof(float), stream)) return e;
-  return launch_variant(kern, dim3(blocks), kBlock, pl.march_lds_bytes, stream, q, org, dir, out, n, max_events, rotation);
+  if (pl.error || !query_runs(d, frame_kind(pl))) return hipErrorInvalidValue; // (the kernels are filed by signature: a plan of another kind must not lend its own)
+  const PlanKernels k = plan_kernels(q, pl);
+  const dim3 grid(quad_ray_blocks(c.n));
+  if (!grid.x || !(d.takes_rotation ? k.query_rotation != nullptr : d.takes_max_events ? k.query_events != nullptr : k.query != nullptr)) return hipErrorInvalidValue;
+  if (d.zeroed)
+    if (hipError_t e = hipMemsetAsync(c.out, 0, (size_t)c.n * ray_query_record_floats(d, c.max_events) * sizeof(float), stream)) return e;
+  if (d.takes_rotation) return launch_variant(k.query_rotation, grid, kBlock, pl.march_lds_bytes, stream, q, c.org, c.dir, c.out, c.n, c.max_events, c.rotation);
+  if (d.takes_max_events) return launch_variant(k.query_events, grid, kBlock, pl.march_lds_bytes, stream, q, c.org, c.dir, c.out, c.n, c.max_events);
+  return launch_variant(k.query, grid, kBlock, pl.march_lds_bytes, stream, q, c.org, c.dir, c.out, c.n);
 }
 
 // known-answer entry of the box test: the object-space ray as the march forms it (to_object of the origin, the direction scaled by inv_scale, not

@@ -368,17 +368,22 @@ class DeviceHIP:
     def project_rays(self, org, direction, mode, range_skipping=False):
         """a projection as the kernels evaluate it (ovr_hip_project_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
         v (n,), tm* (n,) float32, steps (n,), fetched steps (n,) int64, with the committed volume, sampling rate and clip box; zeros for a ray that is not marched"""
+        o = self._ray_query("project_rays", "ovr_hip_project_floats", org, direction, 4, int(mode), int(bool(range_skipping)))
+        return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].astype(np.int64), o[:, 3].astype(np.int64)
+
+    def _ray_query(self, what, entry, org, direction, width, *args):
+        """the one path of the known-answer ray queries (project_rays ... isosurface_ao_rays): world rays (n, 3), (n, 3) onto the device, the library's `entry`
+        called with `args` behind (org, dir, out, n), its records back as (n, width) float32"""
         import torch
         dev = torch.device("cuda", self.device_id)
         t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
         n = int(t[0].numel()) // 3
         if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("project_rays: org and direction hold three floats per ray")
-        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            raise RuntimeError(f"{what}: org and direction hold three floats per ray")
+        out = torch.empty((n, width), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_project_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(mode), int(bool(range_skipping))))
-        o = out.cpu().numpy()
-        return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].astype(np.int64), o[:, 3].astype(np.int64)
+        L.check(getattr(self._lib, entry)(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, *args))
+        return out.cpu().numpy()
 
     # slices (include/ovr_hip.h ovr_hip_set_slices; slices.py is the arithmetic): up to four cut planes or thick slabs through the volume in the march's place -
     # nearest slice wins; the buffer mapframe hands out as `grad` carries the layer (v, t_k, k + 1).  Queued, applied at commit; every call resets the accumulation.
@@ -413,16 +418,7 @@ class DeviceHIP:
         """slice rays as the kernels evaluate them (ovr_hip_slice_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
         k (n,) int64 - the winning slice's index + 1, 0: nothing met -, v (n,), t_k (n,) float32, steps walked (n,) int64 (a plane: 1), with the committed slices,
         volume, sampling rate and clip box"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("slice_rays: org and direction hold three floats per ray")
-        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_slice_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(bool(range_skipping))))
-        o = out.cpu().numpy()
+        o = self._ray_query("slice_rays", "ovr_hip_slice_floats", org, direction, 4, int(bool(range_skipping)))
         return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64)
 
     # the slice context (include/ovr_hip.h ovr_hip_set_slice_context; slice_context.py is the arithmetic): the unshaded march from the ray's entry up to the winning
@@ -445,16 +441,7 @@ class DeviceHIP:
         """context rays as the kernel evaluates them (ovr_hip_slice_context_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given -
         -> k (n,) int64 - the composited slice's index + 1, 0: none -, v (n,), t_k (n,) float32, context steps taken (n,) int64, rgba (n, 4) float32 of the pixel
         sample, with the committed slices, context, transfer function, volume, sampling rate and clip box"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("slice_context_rays: org and direction hold three floats per ray")
-        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_slice_context_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n))
-        o = out.cpu().numpy()
+        o = self._ray_query("slice_context_rays", "ovr_hip_slice_context_floats", org, direction, 8)
         return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
 
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
@@ -482,18 +469,9 @@ class DeviceHIP:
         """translucent isosurface rays as the kernels evaluate them (ovr_hip_isosurface_layers_floats; known-answer tests): world rays (n, 3), (n, 3) ->
         dict(events (n,) int64 - composited -, A (n,) float32, steps, shadow_steps (n,) int64, and per event slot e < max_events k (n, e) int64, t, shadow,
         A_after (n, e) float32, normal (n, e, 3); zeros behind a ray's events) with the committed isovalues, opacities, volume, sampling rate, light and clip box"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("isosurface_layer_rays: org and direction hold three floats per ray")
         m = int(max_events)
-        out = torch.empty((n, 4 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_isosurface_layers_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m, int(bool(range_skipping))))
-        o = out.cpu().numpy()
-        e = o[:, 4:].reshape(n, m, 8)
+        o = self._ray_query("isosurface_layer_rays", "ovr_hip_isosurface_layers_floats", org, direction, 4 + 8 * max(m, 0), m, int(bool(range_skipping)))
+        e = o[:, 4:].reshape(len(o), m, 8)
         return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), k=e[:, :, 0].astype(np.int64),
                     t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy())
 
@@ -518,18 +496,9 @@ class DeviceHIP:
         dict(events (n,) int64 - composited -, A (n,) float32, steps, shadow_steps, lit (n,) int64 - volume samples with a' > 0 -, rgb (n, 3) float32 of the pixel
         sample, and per event slot e < max_events k (n, e) int64, t, shadow, A_after (n, e) float32, normal (n, e, 3); zeros behind a ray's events) with the
         committed isovalues, opacities, context, transfer function, volume, sampling rate, light, material and clip box"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("isosurface_context_rays: org and direction hold three floats per ray")
         m = int(max_events)
-        out = torch.empty((n, 8 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_isosurface_context_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m))
-        o = out.cpu().numpy()
-        e = o[:, 8:].reshape(n, m, 8)
+        o = self._ray_query("isosurface_context_rays", "ovr_hip_isosurface_context_floats", org, direction, 8 + 8 * max(m, 0), m)
+        e = o[:, 8:].reshape(len(o), m, 8)
         return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64), rgb=o[:, 4:7].copy(),
                     lit=o[:, 7].astype(np.int64), k=e[:, :, 0].astype(np.int64), t=e[:, :, 1].copy(), normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(),
                     A_after=e[:, :, 6].copy())
@@ -561,18 +530,9 @@ class DeviceHIP:
         """isosurface rays with ambient occlusion as the kernels evaluate them (ovr_hip_isosurface_ao_floats; known-answer tests): world rays (n, 3), (n, 3), every
         ray at the rotation `rotation` of the direction table -> isosurface_layer_rays' dict plus O (n, e) float32 per event slot and ao_steps, ao_fetched (n,)
         int64: the steps the AO walks of all events walked and fetched"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("isosurface_ao_rays: org and direction hold three floats per ray")
         m = int(max_events)
-        out = torch.empty((n, 8 + 8 * max(m, 0)), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_isosurface_ao_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, m, int(rotation), int(bool(range_skipping))))
-        o = out.cpu().numpy()
-        e = o[:, 8:].reshape(n, m, 8)
+        o = self._ray_query("isosurface_ao_rays", "ovr_hip_isosurface_ao_floats", org, direction, 8 + 8 * max(m, 0), m, int(rotation), int(bool(range_skipping)))
+        e = o[:, 8:].reshape(len(o), m, 8)
         return dict(events=o[:, 0].astype(np.int64), A=o[:, 1].copy(), steps=o[:, 2].astype(np.int64), shadow_steps=o[:, 3].astype(np.int64),
                     ao_steps=o[:, 4].astype(np.int64), ao_fetched=o[:, 5].astype(np.int64), k=e[:, :, 0].astype(np.int64), t=e[:, :, 1].copy(),
                     normal=e[:, :, 2:5].copy(), shadow=e[:, :, 5].copy(), A_after=e[:, :, 6].copy(), O=e[:, :, 7].copy())
@@ -586,16 +546,7 @@ class DeviceHIP:
     def isosurface_rays(self, org, direction, range_skipping=False):
         """isosurface rays as the kernels evaluate them (ovr_hip_isosurface_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as given - ->
         dict(hit (n,) bool, iso, t (n,) float32, steps (n,) int64, normal (n, 3), shadow (n,)) with the committed isovalues, volume, sampling rate, light and clip box"""
-        import torch
-        dev = torch.device("cuda", self.device_id)
-        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction)]
-        n = int(t[0].numel()) // 3
-        if t[0].numel() != 3 * n or t[1].numel() != 3 * n:
-            raise RuntimeError("isosurface_rays: org and direction hold three floats per ray")
-        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        torch.cuda.synchronize(dev)
-        L.check(self._lib.ovr_hip_isosurface_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), out.data_ptr(), n, int(bool(range_skipping))))
-        o = out.cpu().numpy()
+        o = self._ray_query("isosurface_rays", "ovr_hip_isosurface_floats", org, direction, 8, int(bool(range_skipping)))
         return dict(hit=o[:, 0] != 0, iso=o[:, 1].copy(), t=o[:, 2].copy(), steps=o[:, 3].astype(np.int64), normal=o[:, 4:7].copy(), shadow=o[:, 7].copy())
 
     # ---- extensions of this backend ----------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // Driver of tests/test_ambient_occlusion_plan.py: the ambient-occlusion part of csrc/host/launch_plan.hpp (LaunchFacts::ambient_occlusion,
 // LaunchPlan::ambient_occlusion, isosurface_variant_exists) on the CPU.  `driver <scenario>` exits 0 when every row of the scenario gave what it expects.
 #include "launch_plan.hpp"
+#include "plan_compare.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -26,16 +27,11 @@ static LaunchFacts small(int elem = 4)
 }
 static LaunchOverrides ov(int addressing, int deep = -1) { LaunchOverrides o; o.addressing = addressing; o.deep = deep; return o; }
 
-// every field of a plan but ambient_occlusion
-static bool same_but_ao(const LaunchPlan& a, const LaunchPlan& b)
+// every member of a plan but ambient_occlusion
+static bool same_but_ao(LaunchPlan a, const LaunchPlan& b)
 {
-  return a.shading == b.shading && a.am == b.am && a.pooled == b.pooled && a.skip == b.skip && a.march.lds_staged == b.march.lds_staged && a.march.deep == b.march.deep
-         && a.march.material == b.march.material && a.march.clipped == b.march.clipped && a.shade.material == b.shade.material && a.shade.clipped == b.shade.clipped
-         && a.shade_order == b.shade_order && a.cached == b.cached && a.march_lds_bytes == b.march_lds_bytes && a.shade_lds_bytes == b.shade_lds_bytes
-         && a.lds_brick_offset == b.lds_brick_offset && a.shade_grid_blocks == b.shade_grid_blocks && a.error == b.error && a.project.mode == b.project.mode
-         && a.project.skip == b.project.skip && a.project.clipped == b.project.clipped && a.project.lds_bytes == b.project.lds_bytes && a.isosurface.on == b.isosurface.on
-         && a.isosurface.skip == b.isosurface.skip && a.isosurface.clipped == b.isosurface.clipped && a.isosurface.lds_bytes == b.isosurface.lds_bytes
-         && a.isosurface.translucent == b.isosurface.translucent && a.orthographic == b.orthographic;
+  a.ambient_occlusion = b.ambient_occlusion;
+  return same_plan(a, b);
 }
 
 template <typename F> static int for_all_facts(F&& fn)

@@ -1,6 +1,7 @@
 // Driver of tests/test_projection_plan.py: the projection part of csrc/host/launch_plan.hpp on the CPU.  `driver <scenario>` exits 0 when every row of the
 // scenario's table gave what the row expects; the expectations are literals, worked out by hand per row.
 #include "launch_plan.hpp"
+#include "plan_compare.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -28,14 +29,6 @@ static LaunchFacts small(int elem = 4)
   return f;
 }
 static LaunchOverrides ov(int addressing) { LaunchOverrides o; o.addressing = addressing; return o; }
-
-static bool same_plan(const LaunchPlan& a, const LaunchPlan& b)
-{
-  return a.shading == b.shading && a.am == b.am && a.pooled == b.pooled && a.skip == b.skip && a.march.lds_staged == b.march.lds_staged && a.march.deep == b.march.deep
-         && a.march.material == b.march.material && a.march.clipped == b.march.clipped && a.shade.material == b.shade.material && a.shade.clipped == b.shade.clipped
-         && a.shade_order == b.shade_order && a.cached == b.cached && a.march_lds_bytes == b.march_lds_bytes && a.shade_lds_bytes == b.shade_lds_bytes
-         && a.lds_brick_offset == b.lds_brick_offset && a.shade_grid_blocks == b.shade_grid_blocks && a.error == b.error;
-}
 
 // projection == 0: the fields the projections added do not move a plan, and its projection part stays empty
 static void off_changes_nothing()

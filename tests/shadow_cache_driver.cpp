@@ -2,6 +2,7 @@
 // csrc/host/policy.hpp (the lattice's dimensions) - on the CPU.  `driver <scenario>` exits 0 when every row of the scenario gave what it expects.
 // The expectations are literals worked out from DESIGN.md section 14; none is computed by calling the headers.
 #include "launch_plan.hpp"
+#include "plan_compare.hpp"
 #include "policy.hpp"
 
 #include <cstdio>
@@ -61,14 +62,6 @@ static void cached_plans()
   LaunchFacts f = f32_24();
   f.shading = 2; f.shadow_cache = true; f.pool = true; f.world = 2;
   CHECK(plan_launch(f).march.deep && plan_launch(f).cached, "a cached shard: deep %d", (int)plan_launch(f).march.deep);
-}
-
-static bool same_plan(const LaunchPlan& a, const LaunchPlan& b)
-{
-  return a.shading == b.shading && a.am == b.am && a.pooled == b.pooled && a.skip == b.skip && a.march.lds_staged == b.march.lds_staged && a.march.deep == b.march.deep
-         && a.march.material == b.march.material && a.march.clipped == b.march.clipped && a.shade.material == b.shade.material && a.shade.clipped == b.shade.clipped
-         && a.shade_order == b.shade_order && a.march_lds_bytes == b.march_lds_bytes && a.shade_lds_bytes == b.shade_lds_bytes && a.lds_brick_offset == b.lds_brick_offset
-         && a.shade_grid_blocks == b.shade_grid_blocks && a.error == b.error;
 }
 
 // the launcher as it was before the fact existed, restated on the facts (tests/launch_plan_driver.cpp holds plan_launch to the same restatement)

@@ -2,6 +2,7 @@
 // exits 0 when every row of the scenario's table gave what the row expects; the expectations are literals, worked out by hand per row.
 #include "commit_plan.hpp"
 #include "launch_plan.hpp"
+#include "plan_compare.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -26,18 +27,6 @@ static LaunchFacts small(int elem = 4)
   return f;
 }
 static LaunchOverrides ov(int addressing) { LaunchOverrides o; o.addressing = addressing; return o; }
-
-static bool same_plan(const LaunchPlan& a, const LaunchPlan& b)
-{
-  return a.shading == b.shading && a.am == b.am && a.pooled == b.pooled && a.skip == b.skip && a.march.lds_staged == b.march.lds_staged && a.march.deep == b.march.deep
-         && a.march.material == b.march.material && a.march.clipped == b.march.clipped && a.shade.material == b.shade.material && a.shade.clipped == b.shade.clipped
-         && a.shade_order == b.shade_order && a.cached == b.cached && a.orthographic == b.orthographic && a.project.mode == b.project.mode && a.project.skip == b.project.skip
-         && a.project.clipped == b.project.clipped && a.project.lds_bytes == b.project.lds_bytes && a.isosurface.on == b.isosurface.on && a.isosurface.skip == b.isosurface.skip
-         && a.isosurface.clipped == b.isosurface.clipped && a.isosurface.translucent == b.isosurface.translucent && a.isosurface.lds_bytes == b.isosurface.lds_bytes
-         && a.ambient_occlusion == b.ambient_occlusion && a.march_lds_bytes == b.march_lds_bytes && a.shade_lds_bytes == b.shade_lds_bytes
-         && a.lds_brick_offset == b.lds_brick_offset && a.shade_grid_blocks == b.shade_grid_blocks && a.error == b.error && a.slices.on == b.slices.on
-         && a.slices.walks == b.slices.walks && a.slices.skip == b.slices.skip && a.slices.clipped == b.slices.clipped && a.slices.lds_bytes == b.slices.lds_bytes;
-}
 
 // plane versus walk kernel; the skipping twin only with bound ranges and an extremum slab; the clipped / orthographic twins by the projection's rule
 static void kernels()

@@ -207,6 +207,18 @@ class IsosurfaceContext(C.Structure):
     ]
 
 
+PREINTEGRATION_OFF, PREINTEGRATION_SEGMENTS = 0, 1
+
+
+class Preintegration(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("active", C.c_int32),
+        ("nodes", C.c_int32),
+        ("subdivision", C.c_int32),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -328,6 +340,10 @@ SYMBOLS = {
     "ovr_hip_set_isosurface_context": (C.c_int, [_H, C.c_int32, C.c_float]),
     "ovr_hip_get_isosurface_context": (C.c_int, [_H, C.POINTER(IsosurfaceContext)]),
     "ovr_hip_isosurface_context_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_preintegration": (C.c_int, [_H, C.c_int32]),
+    "ovr_hip_get_preintegration": (C.c_int, [_H, C.POINTER(Preintegration)]),
+    "ovr_hip_get_preintegration_tables": (C.c_int, [_H, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32)]),
+    "ovr_hip_preintegrated_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

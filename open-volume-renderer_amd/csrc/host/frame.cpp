@@ -322,8 +322,42 @@ void fill_slice_params(const ovr_hip_renderer* r, RayMarchParams& q)
   q.slice_context = (p.n > 0 && c.mode == OVR_HIP_SLICE_CONTEXT_FRONT) ? 1 : 0;
   q.slice_context_scale = c.scale;
 }
-// a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces or the slices
-static bool in_place_frame(const RayMarchParams& P) { return ovrhip::committed_frame(P.slice_n, P.iso_n, P.projection) != CommittedFrame::March; }
+bool preintegrated_frame(const ovr_hip_renderer* r)
+{
+  return committed_frame(r) == CommittedFrame::March && r->shading.current == OVR_HIP_SHADE_NONE && r->preintegration.current.mode == OVR_HIP_PREINTEGRATION_SEGMENTS;
+}
+int bind_preintegration(ovr_hip_renderer* r, RayMarchParams& q)
+{
+  q.preintegrated = 1;
+  q.preint_m1 = 0;
+  q.preint_nodes = nullptr;
+  const LaunchPlan pl = plan_raymarch(q);
+  if (pl.error || !pl.preintegrated.on || !r->h_tf) return 0;
+  const int s = pl.preintegrated.subdivision;
+  if (r->preint_generation != r->tf_generation || r->preint_subdivision != s || !r->d_preint_nodes) {
+    // (h_tf is rewritten by upload_tfn alone, which raises the generation: between commits it holds the committed tables)
+    const int m = build_preintegration_nodes(r->h_tf, r->n_color, r->h_tf + (size_t)r->n_color * 4, r->n_alpha, s, r->preint_table);
+    if (m != pl.preintegrated.nodes) return fail(OVR_HIP_EINVAL, "[hip] pre-integration: the node table could not be built");
+    if (r->preint_capacity < r->preint_table.size()) {
+      HIP_TRY(hipDeviceSynchronize()); // nothing may still read the old table
+      if (r->d_preint_nodes) HIP_TRY(hipFree(r->d_preint_nodes));
+      r->d_preint_nodes = nullptr; r->preint_capacity = 0;
+      HIP_TRY(hipMalloc((void**)&r->d_preint_nodes, r->preint_table.size() * sizeof(float)));
+      r->preint_capacity = r->preint_table.size();
+    }
+    // stream-ordered behind the frames that read the old table; the vector is pageable, so the call returns once it has been staged
+    HIP_TRY(hipMemcpyAsync(r->d_preint_nodes, r->preint_table.data(), r->preint_table.size() * sizeof(float), hipMemcpyHostToDevice, r->stream()));
+    HIP_TRY(hipStreamSynchronize(r->stream()));
+    r->preint_nodes = m;
+    r->preint_subdivision = s;
+    r->preint_generation = r->tf_generation;
+  }
+  q.preint_m1 = r->preint_nodes - 1;
+  q.preint_nodes = r->d_preint_nodes;
+  return 0;
+}
+// a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces, the slices or the pre-integrated march
+static bool in_place_frame(const RayMarchParams& P) { return ovrhip::committed_frame(P.slice_n, P.iso_n, P.projection) != CommittedFrame::March || P.preintegrated != 0; }
 
 // step 2, continued: tables, shard, jitter, counters
 static int fill_table_params(ovr_hip_renderer* r)
@@ -352,6 +386,9 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.mc_ranges = nullptr;
   fill_isosurface_params(r, P);
   fill_slice_params(r, P);
+  P.preintegrated = preintegrated_frame(r) ? 1 : 0;
+  P.preint_m1 = 0;
+  P.preint_nodes = nullptr;
   return 0;
 }
 
@@ -659,10 +696,12 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  if (committed_frame(r) != CommittedFrame::March) bind_general_layout(r);
+  if (committed_frame(r) != CommittedFrame::March || preintegrated_frame(r)) bind_general_layout(r);
   else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
+  if (r->P.preintegrated)
+    if (int e = bind_preintegration(r, r->P)) return e;
   // the shadow cache: a frame with full shading reads the lattice of a mode other than MARCHED (built here, in front of the frame, when it is stale)
   r->P.shadow_lattice = nullptr;
   if (!in_place_frame(r->P) && r->P.shading == OVR_HIP_SHADE_FULL && r->shadow.current.mode != OVR_HIP_SHADOWS_MARCHED)
@@ -833,6 +872,7 @@ static int read_frame_stats(ovr_hip_renderer* r)
   // a frame of one kernel in the march's place: which twin ran (the adaptive-skipping probe had no say), kept for the kind's getter
   switch (frame_kind(r->plan)) {
   case FrameKind::March: break;
+  case FrameKind::PreintegratedMarch: r->stats.skipping_kernels = 0; break; // (it fetches every step)
   case FrameKind::Projection: r->stats.skipping_kernels = r->projection_skipped = r->plan.project.skip; break;
   case FrameKind::Isosurface: case FrameKind::IsosurfaceLayers: case FrameKind::IsosurfaceAo: case FrameKind::IsosurfaceContext:
     r->stats.skipping_kernels = r->isosurface_skipped = r->plan.isosurface.skip;

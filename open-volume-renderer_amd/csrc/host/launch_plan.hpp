@@ -7,6 +7,8 @@
 // committed_frame is the ONLY statement of which committed state is drawn, frame_kind the only reading of a plan's kind (tests/test_ray_query_table.py).
 #pragma once
 
+#include "preintegration_host.hpp"
+
 #include <algorithm>
 #include <cstddef>
 
@@ -114,6 +116,15 @@ constexpr bool slice_variant_exists(bool walks, int am, bool skip, bool clipped,
   return am >= 0 && am <= 4;
 }
 
+// preintegrated_kernel<VT, am, orthographic> (open-volume-renderer_amd/preintegration.py is the arithmetic): the unshaded march with
+// every SEGMENT between two consecutive samples classified by the transfer function's integral over the values it spans - like the context kernels ON THE
+// CLIPPED VARIANTS ALONE (a frame without a clip box runs it with the unit box), for both cameras, of the general layouts; it fetches every step: no skipping twin
+constexpr bool preintegrated_variant_exists(int am, bool skip, bool clipped, bool orthographic = false)
+{
+  (void)orthographic; // both cameras
+  return clipped && !skip && am >= 0 && am <= 4;
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -129,6 +140,11 @@ constexpr size_t axis_table_bytes(int nx, int ny, int nz, int am)
   return am == 3 ? 0 : am == 2 ? ez * 8 + ab * 4 : (ab + ez) * 4;
 }
 constexpr size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+// the LDS budget of a pre-integrated frame's workgroup - axis tables + transfer function + the 16 * (M + 1) bytes of the node table: a third of a CU's 160 KiB
+// (a multiple of 16), so that three workgroups - one wave each per SIMD, the march's kMarchWavesPerEu = 3 - stay resident.  The kernel is gather-bound like the
+// march: a table that cost it the third wave would cost more than its finer nodes gain, so the subdivision S gives way first (4, 2, 1) and a transfer function
+// whose S = 1 table does not fit is refused, as one whose tables exceed tf_lds_bytes' bound is
+constexpr size_t kPreintegrationLdsBudget = ((size_t)160 * 1024 / 3) & ~(size_t)15;
 
 // Addressing mode of a volume layout: 0 = 32-bit byte offsets (<= 4 GiB), 1 = 32-bit element offsets (< 2^32 stored voxels), 2 = 64-bit z
 // table, 3 = computed 64-bit offsets, no tables.  Modes 0-2 keep the per-axis tables in LDS next to the transfer function and the request
@@ -155,7 +171,7 @@ static_assert(committed_frame(1, 1, 1) == CommittedFrame::Slices && committed_fr
                 && committed_frame(0, 0, 0) == CommittedFrame::March,
               "slices over isovalues over projection over march");
 // one value per kernel family that can stand in the march's place (frame_kind below reads it off a plan)
-enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext };
+enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext, PreintegratedMarch };
 
 // ---- facts -> plan
 struct LaunchFacts {
@@ -186,6 +202,7 @@ struct LaunchFacts {
   bool slice_extremum = false;        // one of the committed slabs is a MAXIMUM or MINIMUM slab: the only ones range skipping drops fetches of
   bool slice_context = false;         // the slice context is committed in mode FRONT (ovr_hip_set_slice_context): a slice frame takes the context kernel - read only while slices > 0
   bool isosurface_context = false;    // the isosurface context is committed in mode VOLUME (ovr_hip_set_isosurface_context): an isosurface frame takes the context kernel - read only while isosurfaces > 0 (and slices == 0)
+  bool preintegrated = false;         // pre-integration is committed in mode SEGMENTS (ovr_hip_set_preintegration): the unshaded march takes the pre-integrated kernel - read only while the committed frame is the march and shading == 0
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -214,6 +231,9 @@ struct LaunchPlan {
   // a slice frame (LaunchFacts::slices > 0): slice_plane_kernel or slice_walk_kernel in the march's place, nothing else of the plan but `am` is read
   // (context: slice_context_kernel - the unshaded march in front of the slices, with the transfer function in LDS behind the axis tables)
   struct Slices { bool on = false, walks = false, skip = false, clipped = false; size_t lds_bytes = 0; bool context = false; } slices;
+  // a pre-integrated march (LaunchFacts::preintegrated on the unshaded march): preintegrated_kernel in the march's place, nothing else of the plan but `am` is
+  // read.  LDS: [axis tables][transfer function][node table, 16-byte aligned]; subdivision / nodes: S and M of the node table the budget allows
+  struct Preintegrated { bool on = false, clipped = false; size_t lds_bytes = 0; int subdivision = 0, nodes = 0; } preintegrated;
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -313,6 +333,26 @@ inline LaunchPlan plan_slices(const LaunchFacts& f, const LaunchOverrides& o)
   return pl;
 }
 
+// a pre-integrated march: one kernel of the general layout on the clipped box test, the transfer function and the node table in LDS behind the axis tables.
+// error: the transfer function does not fit (tf_lds_bytes), or the node table of subdivision 1 does not fit the budget beside tables and transfer function
+inline LaunchPlan plan_preintegrated(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  const Addressing a = plan_addressing(f, o);
+  const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+  if (a.error || tf == 0 || f.quad) { pl.error = true; return pl; }
+  const size_t front = align16(align16(axis_table_bytes(f.nx, f.ny, f.nz, a.am)) + tf); // where the node table starts
+  const int s = front < kPreintegrationLdsBudget ? preintegration_subdivision(f.n_color, f.n_alpha, kPreintegrationLdsBudget - front) : 0;
+  if (s == 0) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am, true);
+  pl.preintegrated.on = true;
+  pl.preintegrated.clipped = w.clipped;
+  pl.preintegrated.subdivision = s;
+  pl.preintegrated.nodes = preintegration_nodes(f.n_color, f.n_alpha, s);
+  pl.preintegrated.lds_bytes = pl.march_lds_bytes = std::max<size_t>(front + preintegration_table_bytes(pl.preintegrated.nodes), (size_t)kWaves * kCounterWords * 4);
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
   switch (committed_frame(f.slices, f.isosurfaces, f.projection)) {
@@ -321,6 +361,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   case CommittedFrame::Projection: return plan_projection(f, o);
   case CommittedFrame::March: break;
   }
+  if (f.preintegrated && f.shading == 0) return plan_preintegrated(f, o); // under GRADIENT or FULL shading the mode is kept and not drawn
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.orthographic = f.orthographic;
@@ -369,6 +410,7 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
 // behind a frame all switch over it.  (An error plan reads as the march: plan_variants_exist and plan_kernels ask `error` first)
 inline FrameKind frame_kind(const LaunchPlan& pl)
 {
+  if (pl.preintegrated.on) return FrameKind::PreintegratedMarch;
   if (pl.slices.on) return pl.slices.context ? FrameKind::SliceContext : pl.slices.walks ? FrameKind::SliceWalk : FrameKind::SlicePlane;
   if (pl.isosurface.on)
     return pl.isosurface.context ? FrameKind::IsosurfaceContext : pl.ambient_occlusion ? FrameKind::IsosurfaceAo
@@ -386,6 +428,7 @@ inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
   case FrameKind::Isosurface: case FrameKind::IsosurfaceLayers: case FrameKind::IsosurfaceAo: case FrameKind::IsosurfaceContext:
     return isosurface_variant_exists(pl.shading, pl.am, pl.isosurface.skip, pl.isosurface.clipped, pl.orthographic, pl.isosurface.translucent, pl.ambient_occlusion, pl.isosurface.context);
   case FrameKind::Projection: return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
+  case FrameKind::PreintegratedMarch: return preintegrated_variant_exists(pl.am, pl.skip, pl.preintegrated.clipped, pl.orthographic);
   case FrameKind::March: break;
   }
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
@@ -416,5 +459,9 @@ static_assert(isosurface_variant_exists(0, 0, false, true, false, true, false, t
                 && !isosurface_variant_exists(2, 0, false, false, false, true, false, true) && !isosurface_variant_exists(2, 0, true, true, false, true, false, true)
                 && !isosurface_variant_exists(2, 0, false, true, false, true, true, true) && !isosurface_variant_exists(1, 0, false, true, false, false, false, true),
               "the isosurface context kernel: a translucent kernel on the clipped variants alone, for both cameras, without a skipping or an AO twin");
+static_assert(preintegrated_variant_exists(0, false, true) && preintegrated_variant_exists(4, false, true, true) && !preintegrated_variant_exists(0, false, false)
+                && !preintegrated_variant_exists(0, true, true) && !preintegrated_variant_exists(5, false, true),
+              "the pre-integrated kernel: on the clipped variants alone, for both cameras, without a skipping twin");
+static_assert(kPreintegrationLdsBudget % 16 == 0 && 3 * kPreintegrationLdsBudget <= 160 * 1024 && 4 * kPreintegrationLdsBudget > 160 * 1024, "three workgroups per CU");
 
 } // namespace ovrhip

@@ -25,6 +25,7 @@ struct RayQuery {
   bool takes_range_skipping, takes_max_events, takes_rotation, takes_mode; // its arguments beyond (r, org, dir, out, n)
   int header_floats, event_floats;  // a ray's record: the header and what follows per event
   bool zeroed;                      // out is zeroed first: the kernel writes a ray's header and the events it met
+  bool needs_preintegration = false; // pre-integration committed in mode SEGMENTS (trailing and defaulted: the seven rows below read as they did)
 };
 enum RayQueryId { kQueryProject, kQuerySlice, kQuerySliceContext, kQueryIsosurface, kQueryIsosurfaceLayers, kQueryIsosurfaceContext, kQueryIsosurfaceAo, kRayQueryCount };
 constexpr RayQuery kRayQueries[kRayQueryCount] = {
@@ -37,6 +38,13 @@ constexpr RayQuery kRayQueries[kRayQueryCount] = {
   { "ovr_hip_isosurface_context_floats", FrameKind::IsosurfaceContext, QueryNeeds::Isovalues, "ovr_hip_set_isosurfaces",       true,   false, true,  false, true,  false, false, 8, 8, true },
   { "ovr_hip_isosurface_ao_floats",      FrameKind::IsosurfaceAo,      QueryNeeds::Isovalues, "ovr_hip_set_isosurface_layers", false,  true,  false, true,  true,  true,  false, 8, 8, true },
 };
+// the eighth entry, ovr_hip_preintegrated_floats (added with pre-integrated classification), walks the same path by a row of its own, OUTSIDE kRayQueries: that
+// table stays the seven rows tests/test_ray_query_table.py holds it to.  Its id follows theirs; ray_query_row is the one lookup of a row by id
+constexpr int kQueryPreintegrated = kRayQueryCount, kRayQueryIds = kRayQueryCount + 1;
+constexpr RayQuery kPreintegrationQueries[1] = {
+  { "ovr_hip_preintegrated_floats",      FrameKind::PreintegratedMarch, QueryNeeds::Nothing,  nullptr,                         false,  false, true,  false, false, false, false, 8, 0, false, true },
+};
+constexpr const RayQuery& ray_query_row(int id) { return id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id]; }
 // the plan a query asked for is the plan of its kernel (slices: the committed set decides between the two slice kernels, as it does for a frame)
 constexpr bool query_runs(const RayQuery& d, FrameKind k) { return k == d.kind || (d.kind == FrameKind::SliceWalk && k == FrameKind::SlicePlane); }
 
@@ -59,6 +67,7 @@ struct QueryFacts {
   int ao_samples = 0;
   bool transfer_function = false;   // both tables are resident
   bool ranges = false;              // the resident volume has its macrocells' value ranges
+  bool preintegration = false;      // committed in mode SEGMENTS
 };
 struct QueryStatus { int code = 0; std::string message; };
 inline QueryStatus query_refusal(const RayQuery& d, int code, const std::string& what) { return { code, std::string("[hip] ") + d.name + ": " + what }; }
@@ -71,7 +80,7 @@ inline QueryStatus ray_query_arguments(const RayQuery& d, bool renderer, const R
   return bad ? query_refusal(d, kQueryEinval, "bad arguments") : QueryStatus();
 }
 
-// the preconditions, reported in this order: volume, slices or isovalues, context mode, AO samples, transfer function, macrocell ranges
+// the preconditions, reported in this order: volume, slices or isovalues, context mode, AO samples, pre-integration, transfer function, macrocell ranges
 inline QueryStatus ray_query_preconditions(const RayQuery& d, const QueryFacts& f, bool range_skipping)
 {
   const bool slices = d.needs == QueryNeeds::Slices;
@@ -81,6 +90,7 @@ inline QueryStatus ray_query_preconditions(const RayQuery& d, const QueryFacts& 
   if (d.needs_context && !(slices ? f.slice_context : f.isosurface_context))
     return query_refusal(d, kQueryEstate, slices ? "no slice context is committed (ovr_hip_set_slice_context)" : "no isosurface context is committed (ovr_hip_set_isosurface_context)");
   if (d.needs_ao && f.ao_samples < 1) return query_refusal(d, kQueryEstate, "no ambient-occlusion sample is committed (ovr_hip_set_ambient_occlusion)");
+  if (d.needs_preintegration && !f.preintegration) return query_refusal(d, kQueryEstate, "no pre-integration is committed (ovr_hip_set_preintegration)");
   if (d.needs_tf && !f.transfer_function) return query_refusal(d, kQueryEstate, "no transfer function was committed");
   if (d.takes_range_skipping && range_skipping && !f.ranges) return query_refusal(d, kQueryEstate, "the resident volume has no macrocell ranges");
   return QueryStatus();

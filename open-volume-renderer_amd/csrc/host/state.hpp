@@ -89,6 +89,8 @@ struct SliceP {
 struct SliceContextP { int mode = 0; float scale = 1.f; };
 // ovr_hip_set_isosurface_context: the mode (OVR_HIP_ISO_CONTEXT_*) and the opacity scale in [0, 1], stored as 1 in mode OFF
 struct IsoContextP { int mode = 0; float scale = 1.f; };
+// ovr_hip_set_preintegration: the mode (OVR_HIP_PREINTEGRATION_*)
+struct PreintP { int mode = 0; };
 // ovr_hip_set_ambient_occlusion: K and the radius (+inf while K == 0: the radius is not read then)
 struct AoP { int samples = 0; float distance = INFINITY; };
 // ovr_hip_set_light / ovr_hip_set_material.  The defaults are the reference's literals: its light vector (params.h:79), light_rgb = 2 = intensity 1
@@ -236,6 +238,14 @@ struct ovr_hip_renderer {
   bool slices_skipped = false;     // the last slice frame ran the range-skipping kernel (ovr_hip_get_slices)
   Queued<ovrhip::host::SliceContextP> slice_context; // ovr_hip_set_slice_context; recorded under kShading like the slices.  Kept while no slice is committed: it takes effect when n > 0
   Queued<ovrhip::host::IsoContextP> isosurface_context; // ovr_hip_set_isosurface_context; recorded under kShading like the isovalues.  Kept while no isovalue is committed: it takes effect when n > 0 and no slice is committed
+  Queued<ovrhip::host::PreintP> preintegration; // ovr_hip_set_preintegration; recorded under kShading like the other frame kinds.  Kept, and not drawn, while the committed frame is not the unshaded march
+  // the integral node table of the committed transfer function (host/preintegration_host.hpp): built by the first pre-integrated frame (or tables getter) after a
+  // transfer-function commit - it carries the generation of the tables it was built from and the subdivision the frame's LDS budget allowed
+  std::vector<float> preint_table; // 4 * (M + 1) floats, as uploaded to d_preint_nodes
+  float* d_preint_nodes = nullptr;
+  size_t preint_capacity = 0;      // floats d_preint_nodes holds
+  int preint_nodes = 0, preint_subdivision = 0; // M and S of the table; 0: none yet
+  unsigned long long preint_generation = 0;     // tf_generation of the tables it was built from
   std::vector<float> ao_table;     // the direction table of the committed K, [16][K][3], as uploaded to d_ao_dirs (both follow K at commit)
   float* d_ao_dirs = nullptr;
   Queued<float> rate;
@@ -303,6 +313,7 @@ struct ovr_hip_renderer {
   bool tf_copy_pending = false;  // a frame has not yet been ordered behind ev_tf
   int n_color = 0, n_alpha = 0;
   bool have_tfn = false;
+  unsigned long long tf_generation = 0; // + 1 with every upload of the tables (what is derived from them - the pre-integration's node table - carries it)
 
   // framebuffer sets
   float* d_rgba[2] = { nullptr, nullptr };
@@ -433,6 +444,11 @@ const float* projection_ranges(const ovr_hip_renderer* r);
 void fill_isosurface_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 // the committed slices into a frame's parameters (slice_n = 0: no slice frame)
 void fill_slice_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
+// the next frame is a pre-integrated march: the committed frame is the march, the committed shading mode NONE and the committed mode SEGMENTS
+bool preintegrated_frame(const ovr_hip_renderer* r);
+// q.preintegrated / preint_m1 / preint_nodes for the frame q describes so far (its layout, tables and clip box are bound): the node table is rebuilt when the
+// transfer function was committed since, or the plan's subdivision changed.  A plan that is an error binds no table: the launch then fails as any error plan does
+int bind_preintegration(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -216,6 +216,7 @@ int upload_tfn(ovr_hip_renderer* r)
   HIP_TRY(hipEventRecord(r->ev_tf, r->stream()));
   r->tf_copy_pending = true;
   r->have_tfn = true;
+  r->tf_generation++;
   return 0;
 }
 

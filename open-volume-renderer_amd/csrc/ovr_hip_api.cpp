@@ -111,6 +111,7 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_noise) (void)hipFree(r->d_noise);
   if (r->d_mc_minmax) (void)hipFree(r->d_mc_minmax);
   if (r->d_ao_dirs) (void)hipFree(r->d_ao_dirs);
+  if (r->d_preint_nodes) (void)hipFree(r->d_preint_nodes);
   if (r->d_mc_majorant) (void)hipFree(r->d_mc_majorant);
   if (r->d_mc_occupancy) (void)hipFree(r->d_mc_occupancy);
   if (r->d_mc_fine) (void)hipFree(r->d_mc_fine);
@@ -437,6 +438,53 @@ int ovr_hip_get_isosurface_context(const ovr_hip_renderer* r, ovr_hip_isosurface
   out->mode = p.mode;
   out->opacity_scale = p.scale;
   out->active = (p.mode == OVR_HIP_ISO_CONTEXT_VOLUME && committed_frame(r) == CommittedFrame::Isovalues) ? 1 : 0;
+  return 0;
+}
+
+int ovr_hip_set_preintegration(ovr_hip_renderer* r, int32_t mode)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (mode != OVR_HIP_PREINTEGRATION_OFF && mode != OVR_HIP_PREINTEGRATION_SEGMENTS) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_preintegration: the mode is OFF or SEGMENTS");
+  PreintP p;
+  p.mode = mode;
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->preintegration.set(p); }
+  GROUP_FORWARD(r, ovr_hip_set_preintegration(m, mode));
+  return 0;
+}
+
+int ovr_hip_get_preintegration(const ovr_hip_renderer* r, ovr_hip_preintegration* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_preintegration: null argument");
+  std::memset(out, 0, sizeof(*out));
+  out->mode = r->preintegration.current.mode;
+  out->active = preintegrated_frame(r) ? 1 : 0;
+  // (the table of the last pre-integrated frame or tables getter: 0 until one was built, and while a newer transfer function awaits its rebuild)
+  const bool fresh = r->preint_nodes > 0 && r->preint_generation == r->tf_generation;
+  out->nodes = fresh ? r->preint_nodes : 0;
+  out->subdivision = fresh ? r->preint_subdivision : 0;
+  return 0;
+}
+
+int ovr_hip_get_preintegration_tables(ovr_hip_renderer* r, float* nodes_host, size_t capacity_nodes, int32_t* n_nodes)
+{
+  if (!r || !n_nodes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_preintegration_tables: null argument");
+  if (int e = set_device(r)) return e;
+  if (int e = finish_frame(r)) return e;
+  if (!r->have_volume) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_preintegration_tables: no volume was set");
+  if (!r->d_tf_color || !r->d_tf_alpha || !r->h_tf) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_preintegration_tables: no transfer function was committed");
+  // the table a pre-integrated frame of the committed volume, transfer function and clip box would read, whatever mode and shading are committed
+  RayMarchParams q = r->P;
+  fill_shadow_params(r, q);
+  q.shading = 0; q.projection = 0; q.iso_n = 0; q.slice_n = 0; q.ao_samples = 0;
+  q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
+  if (int e = bind_preintegration(r, q)) return e;
+  if (!q.preint_nodes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_preintegration_tables: the node table does not fit the frame's LDS budget beside this transfer function");
+  *n_nodes = r->preint_nodes;
+  if (nodes_host) {
+    if (capacity_nodes < (size_t)r->preint_nodes) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_preintegration_tables: nodes_host holds fewer than n_nodes nodes");
+    std::memcpy(nodes_host, r->preint_table.data(), (size_t)r->preint_nodes * 4 * sizeof(float));
+  }
   return 0;
 }
 
@@ -792,6 +840,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (!same_bytes(a->slices.current, b->slices.current)) return false;
   if (!same_bytes(a->slice_context.current, b->slice_context.current)) return false;
   if (!same_bytes(a->isosurface_context.current, b->isosurface_context.current)) return false;
+  if (a->preintegration.current.mode != b->preintegration.current.mode) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -895,11 +944,14 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
     const bool set_s = r->shading.update(), set_p = r->projection.update(), set_i = r->isosurfaces.update(), set_a = r->ambient_occlusion.update(), set_l = r->slices.update();
     const IsoContextP ic = r->isosurface_context.current;
     const bool set_c = r->slice_context.update(), set_ic = r->isosurface_context.update();
+    const int pm = r->preintegration.current.mode;
+    const bool set_pi = r->preintegration.update();
     ch.note(kShading, set_s || set_p || set_i || set_a || set_l || set_c || set_ic,
             shading != r->shading.current || projection != r->projection.current || std::memcmp(&iso, &r->isosurfaces.current, sizeof(IsoP)) != 0 ||
               std::memcmp(&ao, &r->ambient_occlusion.current, sizeof(AoP)) != 0 || std::memcmp(&sl, &r->slices.current, sizeof(SliceP)) != 0 ||
               sc.mode != r->slice_context.current.mode || !(sc.scale == r->slice_context.current.scale) ||
               ic.mode != r->isosurface_context.current.mode || !(ic.scale == r->isosurface_context.current.scale));
+    if (set_pi) ch.note(kShading, true, ch.of[kShading].differs || pm != r->preintegration.current.mode); // ovr_hip_set_preintegration: the same row - a call sets it, a changed mode differs
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
   }
@@ -1450,15 +1502,15 @@ int ovr_hip_shadow_floats(ovr_hip_renderer* r, const float* pos, float* out, int
   return 0;
 }
 
-// the seven known-answer ray queries: one path, walked by the entry's row of host/ray_query.hpp - what must be committed, which parameters it binds, its record
+// the known-answer ray queries (the table's seven and the pre-integrated march's): one path, walked by the entry's row of host/ray_query.hpp - what must be committed, which parameters it binds, its record
 namespace {
 static_assert(kQueryEinval == OVR_HIP_EINVAL && kQueryEstate == OVR_HIP_ESTATE && kQueryRotations == OVR_HIP_AO_ROTATIONS && kProjectMaximum == OVR_HIP_PROJECT_MAXIMUM
                 && kProjectMean == OVR_HIP_PROJECT_MEAN,
               "host/ray_query.hpp restates include/ovr_hip.h");
-int ray_query(ovr_hip_renderer* r, RayQueryId id, const float* org, const float* dir, float* out, int64_t n, int32_t mode = 0, int32_t max_events = 0, int32_t rotation = 0,
+int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, float* out, int64_t n, int32_t mode = 0, int32_t max_events = 0, int32_t rotation = 0,
               int32_t range_skipping = 0) // (0: what the entry does not take)
 {
-  const RayQuery& d = kRayQueries[id];
+  const RayQuery& d = ray_query_row(id);
   RayQueryCall c;
   c.org = org; c.dir = dir; c.out = out; c.n = n;
   c.mode = mode; c.max_events = max_events; c.rotation = rotation; c.range_skipping = range_skipping;
@@ -1474,6 +1526,7 @@ int ray_query(ovr_hip_renderer* r, RayQueryId id, const float* org, const float*
   f.ao_samples = r->ambient_occlusion.current.samples;
   f.transfer_function = r->d_tf_color && r->d_tf_alpha;
   f.ranges = projection_ranges(r) != nullptr;
+  f.preintegration = r->preintegration.current.mode == OVR_HIP_PREINTEGRATION_SEGMENTS;
   if (const QueryStatus s = ray_query_preconditions(d, f, c.range_skipping != 0); s.code) return fail(s.code, s.message);
   RayMarchParams q = r->P;
   fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are read by the context kernels alone)
@@ -1484,6 +1537,11 @@ int ray_query(ovr_hip_renderer* r, RayQueryId id, const float* org, const float*
   if (d.needs == QueryNeeds::Slices) fill_slice_params(r, q);
   if (d.needs == QueryNeeds::Isovalues) fill_isosurface_params(r, q);
   if (d.takes_range_skipping) q.mc_ranges = projection_ranges(r);
+  if (d.needs_preintegration) { // the unshaded march's node table, whatever frame kind and shading mode are committed
+    q.shading = 0; q.projection = 0; q.iso_n = 0; q.slice_n = 0; q.ao_samples = 0;
+    q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
+    if (int e = bind_preintegration(r, q)) return e;
+  }
   HIP_TRY(launch_ray_query(id, q, c, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
@@ -1503,6 +1561,11 @@ int ovr_hip_slice_floats(ovr_hip_renderer* r, const float* org, const float* dir
 int ovr_hip_slice_context_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n)
 {
   return ray_query(r, kQuerySliceContext, org, dir, out, n);
+}
+
+int ovr_hip_preintegrated_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n)
+{
+  return ray_query(r, kQueryPreintegrated, org, dir, out, n);
 }
 
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)

@@ -295,6 +295,12 @@ struct RayMarchParams {
   // by iso_context_scale.  Behind everything else: no other kernel reads them
   int iso_context;
   float iso_context_scale;
+  // pre-integrated classification (ovr_hip_set_preintegration; open-volume-renderer_amd/preintegration.py is the arithmetic): preintegrated != 0 on the unshaded
+  // march = the frame is preintegrated_kernel's.  preint_m1 = M - 1 and preint_nodes = the M + 1 float4 nodes (T, Kr, Kg, Kb) of the committed transfer function
+  // (device memory, built by host/preintegration_host.hpp).  Behind everything else, the pointer last: no other kernel reads them
+  int preintegrated;
+  int preint_m1;
+  const float* preint_nodes;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -361,6 +367,8 @@ hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* bloc
 //   kQueryIsosurfaceAo (isosurface_layers_ao, ovr_hip_isosurface_ao.h, with full shading; p.ao_samples / p.ao_distance / p.ao_dirs, every ray at the table's rotation
 //   c.rotation, 0 ... 15; zeroed first)                             (events composited, A, steps walked, shadow steps, the AO walks' steps, the AO walks' fetched steps, 0, 0),
 //                                                                   then (k, t*, the world normal, shadow, A after the event, O) per event
+//   kQueryPreintegrated (preintegrated_ray, ovr_hip_preintegration.h; p.preint_nodes / p.preint_m1, the transfer function as a frame binds it)
+//                                                                   segments taken, of them integral-branch segments, tx at exit, 0, then r, g, b, a of the pixel sample
 struct RayQueryCall; // host/ray_query.hpp
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream);
 

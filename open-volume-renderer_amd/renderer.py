@@ -444,6 +444,36 @@ class DeviceHIP:
         o = self._ray_query("slice_context_rays", "ovr_hip_slice_context_floats", org, direction, 8)
         return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
 
+    # pre-integrated classification (include/ovr_hip.h ovr_hip_set_preintegration; preintegration.py is the arithmetic): the unshaded march with every segment
+    # between two samples classified by the transfer function's integral over the values it spans.  Queued, applied at commit; every call resets the accumulation;
+    # kept, and not drawn, under GRADIENT / FULL shading and while slices, isovalues or a projection are committed.
+    def set_preintegration(self, mode):
+        """mode: PREINTEGRATION_OFF (0) or PREINTEGRATION_SEGMENTS (1).  ValueError where the ABI says EINVAL"""
+        code = self._lib.ovr_hip_set_preintegration(self._h, int(mode))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def get_preintegration(self):
+        """ovr_hip_preintegration, the COMMITTED state: mode, active (1: the next frame is pre-integrated), nodes and subdivision of the node table built last"""
+        c = L.Preintegration()
+        L.check(self._lib.ovr_hip_get_preintegration(self._h, C.byref(c)))
+        return c
+
+    def preintegration_tables(self):
+        """the float32 node table the frames read (ovr_hip_get_preintegration_tables; built if stale): (M, 4) - T, Kr, Kg, Kb per node"""
+        n = C.c_int32(0)
+        L.check(self._lib.ovr_hip_get_preintegration_tables(self._h, None, 0, C.byref(n)))
+        nodes = np.zeros((int(n.value), 4), np.float32)
+        L.check(self._lib.ovr_hip_get_preintegration_tables(self._h, nodes.ctypes.data_as(C.POINTER(C.c_float)), int(n.value), C.byref(n)))
+        return nodes
+
+    def preintegrated_rays(self, org, direction):
+        """pre-integrated rays as the kernel evaluates them (ovr_hip_preintegrated_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as
+        given - -> segments taken (n,) int64, of them integral-branch segments (n,) int64, tx at exit (n,) float32, rgba (n, 4) float32 of the pixel sample"""
+        o = self._ray_query("preintegrated_rays", "ovr_hip_preintegrated_floats", org, direction, 8)
+        return o[:, 0].astype(np.int64), o[:, 1].astype(np.int64), o[:, 2].copy(), o[:, 4:8].copy()
+
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
     def set_isosurfaces(self, values=(), opacities=None):

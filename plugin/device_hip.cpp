@@ -15,6 +15,7 @@
 #include "slices_env.hpp"
 #include "slice_context_env.hpp"
 #include "iso_context_env.hpp"
+#include "../open-volume-renderer_amd/csrc/host/preintegration_host.hpp" // (HIP-free: parse_preintegration)
 
 #include <chrono>
 #include <cmath>
@@ -260,6 +261,14 @@ public:
         if (!ovrhip_plugin::parse_slice_context(cv, &scale)) throw std::runtime_error("[hip] OVR_HIP_SLICE_CONTEXT expects one opacity scale in [0, 1]");
         check(ovr_hip_set_slice_context(h, OVR_HIP_SLICE_CONTEXT_FRONT, scale));
         if (!quiet) std::fprintf(stderr, "[hip] slice context: the volume in front of the slices, opacity scale %g\n", (double)scale);
+      }
+      // Pre-integrated classification (ovr_hip_set_preintegration): OVR_HIP_PREINTEGRATION=1 classifies every segment of the unshaded march by the transfer
+      // function's integral over the values it spans; 0: OFF.  Unset: nothing is called
+      if (const char* pv = std::getenv("OVR_HIP_PREINTEGRATION")) {
+        int mode = 0;
+        if (!ovrhip::parse_preintegration(pv, &mode)) throw std::runtime_error("[hip] OVR_HIP_PREINTEGRATION expects 0 or 1");
+        check(ovr_hip_set_preintegration(h, mode));
+        if (!quiet && mode) std::fprintf(stderr, "[hip] pre-integrated classification: segments (drawn by unshaded march frames)\n");
       }
     }
     commit();

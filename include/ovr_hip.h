@@ -700,6 +700,54 @@ int ovr_hip_get_preintegration(const ovr_hip_renderer* r, ovr_hip_preintegration
  * does not fit the LDS budget */
 int ovr_hip_get_preintegration_tables(ovr_hip_renderer* r, float* nodes_host, size_t capacity_nodes, int32_t* n_nodes);
 
+/* Gradient opacity (added within ABI v11: new entry points and one new struct only): the march in which the transfer function's opacity
+ * of every sample is weighted by the magnitude of the local gradient (Levoy 1988; VTK's "gradient opacity"), so that the inside of a homogeneous material fades
+ * and its boundaries stay - what a 1-D table cannot tell apart.  The reference has no such control: like the clip box, the definition is this project's.
+ * open-volume-renderer_amd/gradient_opacity.py is the arithmetic in numpy, the normative text.
+ * State: (mode, lo, hi), lo < hi, both finite, lo may be negative; in mode OFF the thresholds are ignored and stored as (0, 1).  inv_ramp = 1.f / (hi - lo), once,
+ * in float32, on the host.
+ * Per pixel sample the loop is the unshaded march's - ray, box test, t0, t1, step = 1 / rate, base = 1, all float32, every fma explicit.  After the tap s at the
+ * object position po and a_tf, rgb from the march's classification:
+ *   if a_tf > 0:                                  - otherwise no gradient is fetched: a_tf * w is 0 whatever w
+ *     d_k = -g_k if po_k + g_k > 1 else g_k       - g_k = 1 / n_k (vertex-centred: 1 / (n_k - 1)): the shading's forward difference
+ *     G_k = (tap(po + d_k e_k) - s) / d_k         - the product multiplies with the stored reciprocal, DESIGN.md section 3's existing approximated place
+ *     W_k = G_k * inv_scale_k                     - the world gradient, sample units per world length
+ *     m   = sqrtf(fma(Wx, Wx, fma(Wy, Wy, Wz * Wz))) * tf_scale    - tf_scale: the transfer-function coordinate's scale, 0 for a degenerate range
+ *     w   = clamp01((m - lo) * inv_ramp);  a_tf = a_tf * w
+ *   a = opacity_correction(a_tf, base * (ty - tx))
+ * m is "fraction of the transfer function's range per world unit length" and does not depend on the voxel type; sqrtf is correctly rounded in both builds.
+ * Under shading NONE the composite is the march's and the gradient layer zero.  Under shading GRADIENT a step with a > 0 uses the same G for the light:
+ * n_o = -normalize(G), n_w = normalize(n_o * inv_scale), the camera normal as the shaded march forms it, shade = ka + light(n_w) with the committed material and
+ * light, C = fma(tr * clamp01(rgb * shade), a, C), and the gradient layer accumulates fma(tr * clamp01(n_c), a, .): operation for operation the GRADIENT-shaded
+ * march.  Counters: samples = steps taken, shaded_samples = steps with a > 0; shadow and skipped counters 0, layout 0, pipeline 1, tuning 0.
+ * Consequences: with (lo, hi) = (-1, 0) w == 1 for every m >= 0 and the frame is the same state's OFF frame bit for bit, under NONE and GRADIENT, counters and
+ * gradient layer included; over a constant volume with lo >= 0 the frame is zero with shaded_samples == 0 and the march's samples; on a linear ramp with hi at
+ * most the ramp's slope (in m's units) w == 1 and the frame is the OFF frame bit for bit; where every w is exactly 0.5 the frame is the OFF frame's under the
+ * alpha table times 0.5.
+ * A frame is a gradient-opacity frame iff the committed frame is the march (no slices, isovalues or projection), the mode is RAMP, the committed shading mode is
+ * OVR_HIP_SHADE_NONE or OVR_HIP_SHADE_GRADIENT, and the frame is not a pre-integrated one; under FULL shading, slices, isovalues, a projection or an active
+ * pre-integration the mode is kept and not drawn.  Such a frame honours camera kind, clip box, sampling rate, transfer function, grid convention, samples per
+ * pixel, jitter, accumulation, sparse sampling, image shards and device groups.  It fetches every step (no empty-space-skipping twin), reads the general layout,
+ * ignores LDS staging and neither asks nor feeds the tuner.
+ * Queued, applied at commit, recorded with the other frame kinds: every call resets the accumulation and voids nothing else; until it is called with mode RAMP
+ * every frame, counter and kernel is what it was.  EINVAL (the state stays): an unknown mode, a non-finite threshold, lo >= hi in mode RAMP.  A device group
+ * forwards the call; ovr_hip_get_gradient_opacity reports member 0's state.
+ * Not done: FULL shading and shadow rays whose opacity is gradient-weighted, a 2-D (value x gradient) table or a piecewise weight, gradient opacity inside the
+ * two contexts or the pre-integrated march, empty-space skipping of the new march, a scene-file field, the mode walk of tests/mode_walk.py over the new kind.
+ * Kernel: gradient_opacity_kernel, one per general voxel type, addressing mode, shading mode (NONE, GRADIENT) and camera, on the clipped box test alone - four
+ * lanes per ray, rounds of 16 steps, the three gradient taps of a step behind a wave-uniform ballot on a_tf > 0, transfer function in LDS.  Measured:
+ * tools/gradient_opacity_bench.py, DESIGN.md section 25. */
+#define OVR_HIP_GRADIENT_OPACITY_OFF 0
+#define OVR_HIP_GRADIENT_OPACITY_RAMP 1
+int ovr_hip_set_gradient_opacity(ovr_hip_renderer* r, int32_t mode, float lo, float hi);
+typedef struct ovr_hip_gradient_opacity {
+  int32_t mode;    /* COMMITTED */
+  int32_t active;  /* 1: the next frame is a gradient-opacity frame - mode RAMP, the march committed, shading NONE or GRADIENT, no active pre-integration */
+  float lo, hi;    /* (0, 1) in mode OFF */
+  float inv_ramp;  /* 1.f / (hi - lo) as the kernels multiply with it */
+} ovr_hip_gradient_opacity;
+int ovr_hip_get_gradient_opacity(const ovr_hip_renderer* r, ovr_hip_gradient_opacity* out);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -889,6 +937,12 @@ int ovr_hip_isosurface_context_floats(ovr_hip_renderer* r, const float* org_devi
  * shading mode are committed.  Per ray 8 floats: segments taken, of them integral-branch segments, tx at exit, 0, r, g, b, a of the pixel sample.  ESTATE without a
  * volume, while the committed mode is OFF or without a committed transfer function; EINVAL: a null pointer, n < 0. */
 int ovr_hip_preintegrated_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n);
+/* a gradient-opacity ray as the kernel evaluates it (added with gradient opacity): n world-space rays as for ovr_hip_slice_floats through the device function
+ * the gradient-opacity frame's kernel calls, with the COMMITTED thresholds, transfer function, volume transform, sampling rate, clip box, light and material -
+ * whatever frame kind and shading mode are committed - under shading `shade`: 0 (NONE) or 1 (GRADIENT; the view vector is the perspective camera's).  Per ray 8
+ * floats: steps taken, of them steps that fetched a gradient, tx at exit, steps with a > 0, r, g, b, a of the pixel sample.  ESTATE without a volume, while the
+ * committed mode is OFF or without a committed transfer function; EINVAL: a null pointer, n < 0, shade outside {0, 1}. */
+int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t shade);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -219,6 +219,19 @@ class Preintegration(C.Structure):
     ]
 
 
+GRADIENT_OPACITY_OFF, GRADIENT_OPACITY_RAMP = 0, 1
+
+
+class GradientOpacity(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("active", C.c_int32),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("inv_ramp", C.c_float),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -344,6 +357,9 @@ SYMBOLS = {
     "ovr_hip_get_preintegration": (C.c_int, [_H, C.POINTER(Preintegration)]),
     "ovr_hip_get_preintegration_tables": (C.c_int, [_H, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32)]),
     "ovr_hip_preintegrated_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "ovr_hip_set_gradient_opacity": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float]),
+    "ovr_hip_get_gradient_opacity": (C.c_int, [_H, C.POINTER(GradientOpacity)]),
+    "ovr_hip_gradient_opacity_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -26,6 +26,7 @@ struct RayQuery {
   int header_floats, event_floats;  // a ray's record: the header and what follows per event
   bool zeroed;                      // out is zeroed first: the kernel writes a ray's header and the events it met
   bool needs_preintegration = false; // pre-integration committed in mode SEGMENTS (trailing and defaulted: the seven rows below read as they did)
+  bool needs_gradient_opacity = false, takes_shade = false; // gradient opacity committed in mode RAMP; `mode` is a shading mode, NONE (0) or GRADIENT (1) (likewise)
 };
 enum RayQueryId { kQueryProject, kQuerySlice, kQuerySliceContext, kQueryIsosurface, kQueryIsosurfaceLayers, kQueryIsosurfaceContext, kQueryIsosurfaceAo, kRayQueryCount };
 constexpr RayQuery kRayQueries[kRayQueryCount] = {
@@ -44,7 +45,15 @@ constexpr int kQueryPreintegrated = kRayQueryCount, kRayQueryIds = kRayQueryCoun
 constexpr RayQuery kPreintegrationQueries[1] = {
   { "ovr_hip_preintegrated_floats",      FrameKind::PreintegratedMarch, QueryNeeds::Nothing,  nullptr,                         false,  false, true,  false, false, false, false, 8, 0, false, true },
 };
-constexpr const RayQuery& ray_query_row(int id) { return id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id]; }
+// the ninth, ovr_hip_gradient_opacity_floats (added with gradient opacity), likewise: a row of its own behind the pre-integration's, whose ids stay what they were
+constexpr int kQueryGradientOpacity = kRayQueryIds, kRayQueryRows = kRayQueryIds + 1;
+constexpr RayQuery kGradientOpacityQueries[1] = {
+  { "ovr_hip_gradient_opacity_floats",   FrameKind::GradientOpacityMarch, QueryNeeds::Nothing, nullptr,                        false,  false, true,  false, false, false, false, 8, 0, false, false, true, true },
+};
+constexpr const RayQuery& ray_query_row(int id)
+{
+  return id >= kRayQueryIds ? kGradientOpacityQueries[id - kRayQueryIds] : id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id];
+}
 // the plan a query asked for is the plan of its kernel (slices: the committed set decides between the two slice kernels, as it does for a frame)
 constexpr bool query_runs(const RayQuery& d, FrameKind k) { return k == d.kind || (d.kind == FrameKind::SliceWalk && k == FrameKind::SlicePlane); }
 
@@ -68,6 +77,7 @@ struct QueryFacts {
   bool transfer_function = false;   // both tables are resident
   bool ranges = false;              // the resident volume has its macrocells' value ranges
   bool preintegration = false;      // committed in mode SEGMENTS
+  bool gradient_opacity = false;    // committed in mode RAMP
 };
 struct QueryStatus { int code = 0; std::string message; };
 inline QueryStatus query_refusal(const RayQuery& d, int code, const std::string& what) { return { code, std::string("[hip] ") + d.name + ": " + what }; }
@@ -75,12 +85,12 @@ inline QueryStatus query_refusal(const RayQuery& d, int code, const std::string&
 // step one of an entry, in front of anything that touches the device
 inline QueryStatus ray_query_arguments(const RayQuery& d, bool renderer, const RayQueryCall& c)
 {
-  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean))
+  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean)) || (d.takes_shade && (c.mode < 0 || c.mode > 1))
                    || (d.takes_max_events && (c.max_events < 1 || c.max_events > kQueryMaxEvents)) || (d.takes_rotation && (c.rotation < 0 || c.rotation >= kQueryRotations));
   return bad ? query_refusal(d, kQueryEinval, "bad arguments") : QueryStatus();
 }
 
-// the preconditions, reported in this order: volume, slices or isovalues, context mode, AO samples, pre-integration, transfer function, macrocell ranges
+// the preconditions, reported in this order: volume, slices or isovalues, context mode, AO samples, pre-integration, gradient opacity, transfer function, macrocell ranges
 inline QueryStatus ray_query_preconditions(const RayQuery& d, const QueryFacts& f, bool range_skipping)
 {
   const bool slices = d.needs == QueryNeeds::Slices;
@@ -91,6 +101,7 @@ inline QueryStatus ray_query_preconditions(const RayQuery& d, const QueryFacts& 
     return query_refusal(d, kQueryEstate, slices ? "no slice context is committed (ovr_hip_set_slice_context)" : "no isosurface context is committed (ovr_hip_set_isosurface_context)");
   if (d.needs_ao && f.ao_samples < 1) return query_refusal(d, kQueryEstate, "no ambient-occlusion sample is committed (ovr_hip_set_ambient_occlusion)");
   if (d.needs_preintegration && !f.preintegration) return query_refusal(d, kQueryEstate, "no pre-integration is committed (ovr_hip_set_preintegration)");
+  if (d.needs_gradient_opacity && !f.gradient_opacity) return query_refusal(d, kQueryEstate, "no gradient opacity is committed (ovr_hip_set_gradient_opacity)");
   if (d.needs_tf && !f.transfer_function) return query_refusal(d, kQueryEstate, "no transfer function was committed");
   if (d.takes_range_skipping && range_skipping && !f.ranges) return query_refusal(d, kQueryEstate, "the resident volume has no macrocell ranges");
   return QueryStatus();

@@ -9,6 +9,7 @@
 #include "../ovr_hip_update.h"
 #pragma GCC visibility push(hidden)
 #include "commit_plan.hpp"
+#include "gradient_opacity_host.hpp"
 #include "policy.hpp"
 #include "slices_host.hpp"
 #pragma GCC visibility pop
@@ -238,6 +239,7 @@ struct ovr_hip_renderer {
   bool slices_skipped = false;     // the last slice frame ran the range-skipping kernel (ovr_hip_get_slices)
   Queued<ovrhip::host::SliceContextP> slice_context; // ovr_hip_set_slice_context; recorded under kShading like the slices.  Kept while no slice is committed: it takes effect when n > 0
   Queued<ovrhip::host::IsoContextP> isosurface_context; // ovr_hip_set_isosurface_context; recorded under kShading like the isovalues.  Kept while no isovalue is committed: it takes effect when n > 0 and no slice is committed
+  Queued<ovrhip::GradientOpacityState> gradient_opacity; // ovr_hip_set_gradient_opacity (host/gradient_opacity_host.hpp); recorded under kShading like the other frame kinds.  Kept, and not drawn, while gradient_opacity_frame says no
   Queued<ovrhip::host::PreintP> preintegration; // ovr_hip_set_preintegration; recorded under kShading like the other frame kinds.  Kept, and not drawn, while the committed frame is not the unshaded march
   // the integral node table of the committed transfer function (host/preintegration_host.hpp): built by the first pre-integrated frame (or tables getter) after a
   // transfer-function commit - it carries the generation of the tables it was built from and the subdivision the frame's LDS budget allowed
@@ -449,6 +451,10 @@ bool preintegrated_frame(const ovr_hip_renderer* r);
 // q.preintegrated / preint_m1 / preint_nodes for the frame q describes so far (its layout, tables and clip box are bound): the node table is rebuilt when the
 // transfer function was committed since, or the plan's subdivision changed.  A plan that is an error binds no table: the launch then fails as any error plan does
 int bind_preintegration(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
+// the next frame is a gradient-opacity march (host/gradient_opacity_host.hpp gradient_opacity_active over the committed state)
+bool gradient_opacity_frame(const ovr_hip_renderer* r);
+// q.gradient_opacity (on) and the committed thresholds
+void fill_gradient_opacity_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q, bool on);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

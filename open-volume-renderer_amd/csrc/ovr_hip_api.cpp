@@ -488,6 +488,32 @@ int ovr_hip_get_preintegration_tables(ovr_hip_renderer* r, float* nodes_host, si
   return 0;
 }
 
+static_assert(kGradientOpacityOff == OVR_HIP_GRADIENT_OPACITY_OFF && kGradientOpacityRamp == OVR_HIP_GRADIENT_OPACITY_RAMP, "host/gradient_opacity_host.hpp restates include/ovr_hip.h");
+int ovr_hip_set_gradient_opacity(ovr_hip_renderer* r, int32_t mode, float lo, float hi)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  GradientOpacityState g;
+  if (!gradient_opacity_commit(mode, lo, hi, &g))
+    return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_set_gradient_opacity: the mode is OFF or RAMP, the thresholds are finite and lo < hi");
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->gradient_opacity.set(g); }
+  GROUP_FORWARD(r, ovr_hip_set_gradient_opacity(m, mode, lo, hi));
+  return 0;
+}
+
+int ovr_hip_get_gradient_opacity(const ovr_hip_renderer* r, ovr_hip_gradient_opacity* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_gradient_opacity: null argument");
+  std::memset(out, 0, sizeof(*out));
+  const GradientOpacityState& g = r->gradient_opacity.current;
+  out->mode = g.mode;
+  out->active = gradient_opacity_frame(r) ? 1 : 0;
+  out->lo = g.lo;
+  out->hi = g.hi;
+  out->inv_ramp = g.inv_ramp;
+  return 0;
+}
+
 int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -841,6 +867,9 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (!same_bytes(a->slice_context.current, b->slice_context.current)) return false;
   if (!same_bytes(a->isosurface_context.current, b->isosurface_context.current)) return false;
   if (a->preintegration.current.mode != b->preintegration.current.mode) return false;
+  if (a->gradient_opacity.current.mode != b->gradient_opacity.current.mode || !(a->gradient_opacity.current.lo == b->gradient_opacity.current.lo) ||
+      !(a->gradient_opacity.current.hi == b->gradient_opacity.current.hi))
+    return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -952,6 +981,11 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
               sc.mode != r->slice_context.current.mode || !(sc.scale == r->slice_context.current.scale) ||
               ic.mode != r->isosurface_context.current.mode || !(ic.scale == r->isosurface_context.current.scale));
     if (set_pi) ch.note(kShading, true, ch.of[kShading].differs || pm != r->preintegration.current.mode); // ovr_hip_set_preintegration: the same row - a call sets it, a changed mode differs
+    {
+      const GradientOpacityState go = r->gradient_opacity.current;
+      if (r->gradient_opacity.update()) // ovr_hip_set_gradient_opacity: the same row - a call sets it, a changed mode or threshold differs
+        ch.note(kShading, true, ch.of[kShading].differs || go.mode != r->gradient_opacity.current.mode || !(go.lo == r->gradient_opacity.current.lo) || !(go.hi == r->gradient_opacity.current.hi));
+    }
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
   }
@@ -1527,6 +1561,7 @@ int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, f
   f.transfer_function = r->d_tf_color && r->d_tf_alpha;
   f.ranges = projection_ranges(r) != nullptr;
   f.preintegration = r->preintegration.current.mode == OVR_HIP_PREINTEGRATION_SEGMENTS;
+  f.gradient_opacity = r->gradient_opacity.current.mode == OVR_HIP_GRADIENT_OPACITY_RAMP;
   if (const QueryStatus s = ray_query_preconditions(d, f, c.range_skipping != 0); s.code) return fail(s.code, s.message);
   RayMarchParams q = r->P;
   fill_shadow_params(r, q); // the committed sampling rate and the general layout, as a frame sets them (the tables are read by the context kernels alone)
@@ -1541,6 +1576,11 @@ int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, f
     q.shading = 0; q.projection = 0; q.iso_n = 0; q.slice_n = 0; q.ao_samples = 0;
     q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
     if (int e = bind_preintegration(r, q)) return e;
+  }
+  if (d.needs_gradient_opacity) { // the march's plan under the asked shading, whatever frame kind and shading mode are committed
+    q.projection = 0; q.iso_n = 0; q.slice_n = 0; q.ao_samples = 0;
+    q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
+    fill_gradient_opacity_params(r, q, true);
   }
   HIP_TRY(launch_ray_query(id, q, c, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
@@ -1566,6 +1606,11 @@ int ovr_hip_slice_context_floats(ovr_hip_renderer* r, const float* org, const fl
 int ovr_hip_preintegrated_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n)
 {
   return ray_query(r, kQueryPreintegrated, org, dir, out, n);
+}
+
+int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t shade)
+{
+  return ray_query(r, kQueryGradientOpacity, org, dir, out, n, shade);
 }
 
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)

@@ -301,6 +301,12 @@ struct RayMarchParams {
   int preintegrated;
   int preint_m1;
   const float* preint_nodes;
+  // gradient opacity (ovr_hip_set_gradient_opacity; open-volume-renderer_amd/gradient_opacity.py is the arithmetic): gradient_opacity != 0 on the march under
+  // shading NONE or GRADIENT = the frame is gradient_opacity_kernel's.  gradop_lo = the ramp's lower threshold, gradop_inv_ramp = 1.f / (hi - lo) as the host
+  // rounded it (host/gradient_opacity_host.hpp).  Behind everything else: no other kernel reads them
+  int gradient_opacity;
+  float gradop_lo;
+  float gradop_inv_ramp;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -369,6 +375,8 @@ hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* bloc
 //                                                                   then (k, t*, the world normal, shadow, A after the event, O) per event
 //   kQueryPreintegrated (preintegrated_ray, ovr_hip_preintegration.h; p.preint_nodes / p.preint_m1, the transfer function as a frame binds it)
 //                                                                   segments taken, of them integral-branch segments, tx at exit, 0, then r, g, b, a of the pixel sample
+//   kQueryGradientOpacity (gradient_opacity_ray, ovr_hip_gradient_opacity.h; p.gradop_lo / p.gradop_inv_ramp, under shading c.mode = 0 (NONE) or 1 (GRADIENT), the
+//   perspective camera's view vector)                               steps taken, of them steps that fetched a gradient, tx at exit, steps with a > 0, then r, g, b, a of the pixel sample
 struct RayQueryCall; // host/ray_query.hpp
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream);
 

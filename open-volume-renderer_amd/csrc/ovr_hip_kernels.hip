@@ -19,6 +19,7 @@
 #include "ovr_hip_slices.h"
 #include "ovr_hip_slice_context.h"
 #include "ovr_hip_preintegration.h"
+#include "ovr_hip_gradient_opacity.h"
 #include "ovr_hip_isosurface_context.h"
 #include "ovr_hip_update.h"
 #include "host/ray_query.hpp"
@@ -1032,6 +1033,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.slice_context = p.slice_n > 0 && p.slice_context != 0;
   f.isosurface_context = p.iso_n > 0 && p.iso_context != 0;
   f.preintegrated = p.preintegrated != 0;
+  f.gradient_opacity = p.gradient_opacity != 0;
   return plan_launch(f, o);
 }
 
@@ -1091,7 +1093,8 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template SliceKernels slice_kernels_of<E>(const LaunchPlan&);               \
   extern template SliceContextKernels slice_context_kernels_of<E>(const LaunchPlan&); \
   extern template IsosurfaceContextKernels isosurface_context_kernels_of<E>(const LaunchPlan&); \
-  extern template PreintegratedKernels preintegrated_kernels_of<E>(const LaunchPlan&);
+  extern template PreintegratedKernels preintegrated_kernels_of<E>(const LaunchPlan&); \
+  extern template GradientOpacityKernels gradient_opacity_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
 OVR_VOXEL_TYPES(OVR_X_SLICES)
@@ -1136,6 +1139,7 @@ static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
     if (p.preint_nodes && p.preint_m1 == plan.preintegrated.nodes - 1) // (the kernels stage the node table the plan sized its LDS for: no table, no kernel)
       dispatch_voxel_type<true>(t, [&](auto vt) { k.take(preintegrated_kernels_of<decltype(vt)::value>(plan)); });
     break;
+  case FrameKind::GradientOpacityMarch: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(gradient_opacity_kernels_of<decltype(vt)::value>(plan)); }); break;
   case FrameKind::March: dispatch_voxel_type(t, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); }); break;
   }
   return k;
@@ -2095,6 +2099,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
   q.slice_context = 0;
   q.iso_context = 0; // (the context's own query puts it back)
   q.preintegrated = 0; // (likewise)
+  q.gradient_opacity = 0; // (likewise)
   q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
@@ -2154,7 +2159,7 @@ hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float
 // frame takes for it.  What the query does not ask about is scrubbed from the plan's facts, whatever is committed and whatever the last frame drew
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream)
 {
-  if (query < 0 || query >= kRayQueryIds) return hipErrorInvalidValue;
+  if (query < 0 || query >= kRayQueryRows) return hipErrorInvalidValue;
   const RayQuery& d = ray_query_row(query);
   if (c.n <= 0) return hipSuccess;
   const bool skip = d.takes_range_skipping && c.range_skipping != 0 && !(d.takes_mode && c.mode == kProjectMean); // (a mean needs every sample: it has no skipping twin)
@@ -2166,6 +2171,7 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   if (d.needs_ao && (p.ao_samples < 1 || p.ao_samples > kAoMaxSamples || !p.ao_dirs)) return hipErrorInvalidValue;
   if (d.needs_tf && (!p.tf_color || !p.tf_alpha)) return hipErrorInvalidValue;
   if (d.needs_preintegration && (!p.preint_nodes || p.preint_m1 < 1)) return hipErrorInvalidValue;
+  if (d.takes_shade && (c.mode < 0 || c.mode > 1)) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, skip);
   switch (d.kind) {
   case FrameKind::Projection: q.projection = c.mode; q.iso_n = 0; q.ao_samples = 0; break; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
@@ -2176,6 +2182,7 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   case FrameKind::IsosurfaceContext: q.iso_context = 1; q.shading = 2; q.ao_samples = 0; break; // (under full shading)
   case FrameKind::IsosurfaceAo: q.iso_translucent = 1; q.shading = 2; break;        // (with full shading, the committed samples)
   case FrameKind::PreintegratedMarch: q.preintegrated = 1; q.shading = 0; q.projection = 0; q.iso_n = 0; q.ao_samples = 0; break; // (the unshaded march's plan, whatever is committed)
+  case FrameKind::GradientOpacityMarch: q.gradient_opacity = 1; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0; break; // (the march's plan under the asked shading, whatever is committed)
   default: return hipErrorInvalidValue;
   }
   const LaunchPlan pl = plan_raymarch(q);

@@ -474,6 +474,30 @@ class DeviceHIP:
         o = self._ray_query("preintegrated_rays", "ovr_hip_preintegrated_floats", org, direction, 8)
         return o[:, 0].astype(np.int64), o[:, 1].astype(np.int64), o[:, 2].copy(), o[:, 4:8].copy()
 
+    # gradient opacity (include/ovr_hip.h ovr_hip_set_gradient_opacity; gradient_opacity.py is the arithmetic): the march with every sample's table opacity
+    # weighted by a ramp over the gradient's magnitude.  Queued, applied at commit; every call resets the accumulation; kept, and not drawn, under FULL shading,
+    # while slices, isovalues or a projection are committed, and behind an active pre-integration.
+    def set_gradient_opacity(self, mode, lo=0.0, hi=1.0):
+        """mode: GRADIENT_OPACITY_OFF (0) or GRADIENT_OPACITY_RAMP (1); lo < hi, finite: the ramp's thresholds in transfer-function ranges per world unit length
+        (gradient_opacity.magnitudes gives a volume's).  ValueError where the ABI says EINVAL"""
+        code = self._lib.ovr_hip_set_gradient_opacity(self._h, int(mode), float(lo), float(hi))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def get_gradient_opacity(self):
+        """ovr_hip_gradient_opacity, the COMMITTED state: mode, active (1: the next frame is a gradient-opacity frame), lo, hi, inv_ramp"""
+        c = L.GradientOpacity()
+        L.check(self._lib.ovr_hip_get_gradient_opacity(self._h, C.byref(c)))
+        return c
+
+    def gradient_opacity_rays(self, org, direction, shade=0):
+        """gradient-opacity rays as the kernel evaluates them (ovr_hip_gradient_opacity_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used
+        as given - under shading `shade` (0 NONE, 1 GRADIENT) -> steps taken (n,) int64, of them steps that fetched a gradient (n,) int64, tx at exit (n,) float32,
+        steps with a > 0 (n,) int64, rgba (n, 4) float32 of the pixel sample"""
+        o = self._ray_query("gradient_opacity_rays", "ovr_hip_gradient_opacity_floats", org, direction, 8, int(shade))
+        return o[:, 0].astype(np.int64), o[:, 1].astype(np.int64), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
+
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
     def set_isosurfaces(self, values=(), opacities=None):

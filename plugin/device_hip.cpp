@@ -16,6 +16,7 @@
 #include "slice_context_env.hpp"
 #include "iso_context_env.hpp"
 #include "../open-volume-renderer_amd/csrc/host/preintegration_host.hpp" // (HIP-free: parse_preintegration)
+#include "../open-volume-renderer_amd/csrc/host/gradient_opacity_host.hpp" // (HIP-free: parse_gradient_opacity)
 
 #include <chrono>
 #include <cmath>
@@ -269,6 +270,14 @@ public:
         if (!ovrhip::parse_preintegration(pv, &mode)) throw std::runtime_error("[hip] OVR_HIP_PREINTEGRATION expects 0 or 1");
         check(ovr_hip_set_preintegration(h, mode));
         if (!quiet && mode) std::fprintf(stderr, "[hip] pre-integrated classification: segments (drawn by unshaded march frames)\n");
+      }
+      // Gradient opacity (ovr_hip_set_gradient_opacity): OVR_HIP_GRADIENT_OPACITY=lo,hi weights every sample's table opacity by the ramp over the gradient's
+      // magnitude, in transfer-function ranges per world unit length.  Unset: nothing is called
+      if (const char* gv = std::getenv("OVR_HIP_GRADIENT_OPACITY")) {
+        float lo = 0.f, hi = 1.f;
+        if (!ovrhip::parse_gradient_opacity(gv, &lo, &hi)) throw std::runtime_error("[hip] OVR_HIP_GRADIENT_OPACITY expects lo,hi: two finite numbers with lo < hi");
+        check(ovr_hip_set_gradient_opacity(h, OVR_HIP_GRADIENT_OPACITY_RAMP, lo, hi));
+        if (!quiet) std::fprintf(stderr, "[hip] gradient opacity: ramp %g ... %g (drawn by march frames under shading NONE or GRADIENT)\n", (double)lo, (double)hi);
       }
     }
     commit();

@@ -748,6 +748,55 @@ typedef struct ovr_hip_gradient_opacity {
 } ovr_hip_gradient_opacity;
 int ovr_hip_get_gradient_opacity(const ovr_hip_renderer* r, ovr_hip_gradient_opacity* out);
 
+/* Depth limit (added within ABI v11: new entry points and one new struct only): the march that ends every ray of a pixel on a ray
+ * parameter the caller hands in - the distance of the opaque geometry (a mesh, an instrument, a bounding frame, another renderer's picture) the application drew
+ * at that pixel - so that the frame is what lies IN FRONT of that geometry and can be blended over the caller's picture (rgb * a + own * (1 - a)).  VTK and
+ * ParaView end rays at the depth buffer, OSPRay takes a map_maxDepth texture; the reference has no such control: like the clip box, the definition is this
+ * project's.  open-volume-renderer_amd/max_depth.py is the arithmetic in numpy, the normative text.
+ * depth: width * height float32 values in the frame's own pixel order - the order of ovr_hip_mapframe's rgba: the value of pixel (ix, iy) is at ix + iy * width.
+ * UNITS: the march's own t - WORLD LENGTH ALONG THE NORMALISED RAY DIRECTION FROM THE RAY'S ORIGIN.  Under the perspective camera that is the Euclidean distance
+ * from the camera position; it is not a planar z and not a z-buffer value (max_depth.ray_distance_from_planar converts an eye-space z).  Under the orthographic
+ * camera it is the distance from the image plane through `from`: the planar depth of section 18.
+ * The renderer keeps its own device copy: depth (host or device memory, mem_kind) is not referenced after the call returns.  depth == NULL switches the limit off
+ * (the other arguments are not read).
+ * Per pixel sample of pixel (ix, iy), with (t0, t1, hit) as the march forms them:
+ *   z = depth[ix + iy * width]        - every sample of a pixel (spp > 1, pixel jitter) takes the pixel's value
+ *   limited = z < +inf                - false for +inf and for NaN: no surface at this pixel
+ *   tc = limited ? fminf(t1, z) : t1
+ * and from there the loop is the march's with tc in t1's place, operation for operation: under shading NONE slice_context.py's step 3 with scale 1, under
+ * shading GRADIENT the gradient-shaded step of gradient_opacity.py with the opacity left unweighted.  The last step ends on tc: ty = fminf(tx + step, tc),
+ * dt = ty - tx goes through the opacity correction; a step of length 0 is not taken; z <= t0 (any negative value, -inf) takes no step.  Nothing is composited
+ * behind the cut: the pixel is the march's un-premultiplied (rgb, alpha) of what lies in front of the surface.  The gradient layer is zero under NONE and the
+ * march's under GRADIENT.  Counters: samples = steps taken, shaded_samples = steps with a > 0; shadow and skipped counters 0, layout 0, pipeline 1, tuning 0.
+ * Consequences: an image of +inf, of NaN or of values >= every t1 gives the same state's frame without the limit bit for bit, counters and gradient layer
+ * included; depth = the clipped march's t1 (0 where the clipped ray misses) under a clip box that removes only the far side gives the clipped frame.
+ * A frame is a depth-limited frame iff the committed frame is the march (no slices, isovalues or projection), an image is committed, the committed shading mode
+ * is OVR_HIP_SHADE_NONE or OVR_HIP_SHADE_GRADIENT, neither pre-integration nor gradient opacity is active (their own rules and `active` flags stay what they
+ * are), and the image's size equals the committed framebuffer size.  Otherwise the image is kept and not drawn.  Such a frame honours camera kind, clip box,
+ * sampling rate, transfer function, grid convention, samples per pixel, jitter, accumulation, sparse sampling, image shards and device groups (every member
+ * holds the whole image and indexes it by the full frame's pixel index).  It fetches every step, reads the general layout, ignores LDS staging and neither asks
+ * nor feeds the tuner.
+ * Queued, applied at commit, recorded with the other frame kinds: every call resets the accumulation and voids nothing else - every call with an image counts as
+ * a change, contents are not compared; until it is called with an image every frame, counter and kernel is what it was.  The frame in flight is resolved before
+ * the image is copied.  EINVAL, checked before anything changes (the state stays): a bad mem_kind, width or height < 1, width x height beyond 2^31 - 1 pixels.
+ * Not done: FULL shading and shadow rays that see the surface; the limit on projections, isosurfaces, slices, the two contexts, pre-integration and gradient
+ * opacity; compositing a colour inside the renderer; empty-space skipping, the tuner and the layout choice for the new kernel; a depth OUTPUT layer; the mode walk
+ * of tests/mode_walk.py over the new kind.
+ * Kernel: max_depth_kernel, one per general voxel type, addressing mode, shading mode (NONE, GRADIENT) and camera, on the clipped box test alone - four lanes
+ * per ray, rounds of 16 steps, one depth load per pixel, transfer function in LDS.  Measured: tools/max_depth_bench.py, DESIGN.md section 26. */
+#define OVR_HIP_MAX_DEPTH_OFF 0
+#define OVR_HIP_MAX_DEPTH_ON 1
+int ovr_hip_set_max_depth(ovr_hip_renderer* r, const float* depth, int mem_kind, int32_t width, int32_t height);
+typedef struct ovr_hip_max_depth {
+  int32_t mode;          /* COMMITTED: OVR_HIP_MAX_DEPTH_ON while an image is held */
+  int32_t active;        /* 1: the next frame is a depth-limited frame - see above */
+  int32_t width, height; /* of the committed image; 0 in mode OFF */
+} ovr_hip_max_depth;
+int ovr_hip_get_max_depth(const ovr_hip_renderer* r, ovr_hip_max_depth* out);
+/* the committed image, read back: width x height floats into depth_host (capacity_floats of them; EINVAL where that is too few); width and height are always
+ * written (0 in mode OFF, where nothing is copied); depth_host == NULL asks for the size alone */
+int ovr_hip_get_max_depth_values(ovr_hip_renderer* r, float* depth_host, size_t capacity_floats, int32_t* width, int32_t* height);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -943,6 +992,13 @@ int ovr_hip_preintegrated_floats(ovr_hip_renderer* r, const float* org_device, c
  * floats: steps taken, of them steps that fetched a gradient, tx at exit, steps with a > 0, r, g, b, a of the pixel sample.  ESTATE without a volume, while the
  * committed mode is OFF or without a committed transfer function; EINVAL: a null pointer, n < 0, shade outside {0, 1}. */
 int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, float* out_device, int64_t n, int32_t shade);
+/* a depth-limited ray as the kernel evaluates it (added with the depth limit): n world-space rays as for ovr_hip_slice_floats, ray i ending on depth_device[i]
+ * (the march's t, as for ovr_hip_set_max_depth), through the device function the depth-limited frame's kernel calls, with the COMMITTED transfer function,
+ * volume transform, sampling rate, clip box, light and material - whatever frame kind, shading mode and depth image are committed - under shading `shade`: 0
+ * (NONE) or 1 (GRADIENT; the view vector is the perspective camera's).  Per ray 8 floats: steps taken, the cut tc, tx at exit, steps with a > 0, r, g, b, a of
+ * the pixel sample (tc and tx 0 for a ray that misses the box).  ESTATE without a volume or without a committed transfer function; EINVAL: a null pointer,
+ * n < 0, shade outside {0, 1}. */
+int ovr_hip_max_depth_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, const float* depth_device, float* out_device, int64_t n, int32_t shade);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -232,6 +232,18 @@ class GradientOpacity(C.Structure):
     ]
 
 
+MAX_DEPTH_OFF, MAX_DEPTH_ON = 0, 1
+
+
+class MaxDepth(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("active", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -360,6 +372,10 @@ SYMBOLS = {
     "ovr_hip_set_gradient_opacity": (C.c_int, [_H, C.c_int32, C.c_float, C.c_float]),
     "ovr_hip_get_gradient_opacity": (C.c_int, [_H, C.POINTER(GradientOpacity)]),
     "ovr_hip_gradient_opacity_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_max_depth": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int32, C.c_int32]),
+    "ovr_hip_get_max_depth": (C.c_int, [_H, C.POINTER(MaxDepth)]),
+    "ovr_hip_get_max_depth_values": (C.c_int, [_H, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ovr_hip_max_depth_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "gradient_opacity_host.hpp"
+#include "max_depth_host.hpp"
 #include "preintegration_host.hpp"
 
 #include <algorithm>
@@ -135,6 +136,15 @@ constexpr bool gradient_opacity_variant_exists(int shade, int am, bool skip, boo
   return (shade == 0 || shade == 1) && clipped && !skip && am >= 0 && am <= 4;
 }
 
+// max_depth_kernel<VT, am, shade, orthographic> (open-volume-renderer_amd/max_depth.py is the arithmetic): the march that ends on a
+// per-pixel ray parameter the caller hands in - like the context kernels ON THE CLIPPED VARIANTS ALONE (a frame without a clip box runs it with the unit box),
+// for shading NONE and GRADIENT and both cameras, of the general layouts; it fetches every step: no skipping twin
+constexpr bool max_depth_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false)
+{
+  (void)orthographic; // both cameras
+  return (shade == 0 || shade == 1) && clipped && !skip && am >= 0 && am <= 4;
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -181,7 +191,7 @@ static_assert(committed_frame(1, 1, 1) == CommittedFrame::Slices && committed_fr
                 && committed_frame(0, 0, 0) == CommittedFrame::March,
               "slices over isovalues over projection over march");
 // one value per kernel family that can stand in the march's place (frame_kind below reads it off a plan)
-enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext, PreintegratedMarch, GradientOpacityMarch };
+enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext, PreintegratedMarch, GradientOpacityMarch, DepthLimitedMarch };
 
 // ---- facts -> plan
 struct LaunchFacts {
@@ -214,6 +224,7 @@ struct LaunchFacts {
   bool isosurface_context = false;    // the isosurface context is committed in mode VOLUME (ovr_hip_set_isosurface_context): an isosurface frame takes the context kernel - read only while isosurfaces > 0 (and slices == 0)
   bool preintegrated = false;         // pre-integration is committed in mode SEGMENTS (ovr_hip_set_preintegration): the unshaded march takes the pre-integrated kernel - read only while the committed frame is the march and shading == 0
   bool gradient_opacity = false;      // gradient opacity is committed in mode RAMP (ovr_hip_set_gradient_opacity): the march under shading NONE or GRADIENT takes the gradient-opacity kernel - read only while the committed frame is the march and the frame is not a pre-integrated one
+  bool max_depth = false;             // a depth image of the framebuffer's size is committed (ovr_hip_set_max_depth): the march under shading NONE or GRADIENT takes the depth-limited kernel - read only while the committed frame is the march and neither pre-integration nor gradient opacity draws it
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -248,6 +259,9 @@ struct LaunchPlan {
   // a gradient-opacity march (LaunchFacts::gradient_opacity on the march under shading NONE or GRADIENT): gradient_opacity_kernel in the march's place, nothing
   // else of the plan but `am` is read.  LDS: [axis tables][transfer function], the slice context's carve; shade: the GRADIENT-shaded kernel
   struct GradientOpacity { bool on = false, clipped = false, shade = false; size_t lds_bytes = 0; } gradient_opacity;
+  // a depth-limited march (LaunchFacts::max_depth on the march under shading NONE or GRADIENT): max_depth_kernel in the march's place, nothing else of the plan
+  // but `am` is read.  LDS: [axis tables][transfer function], the slice context's carve; shade: the GRADIENT-shaded kernel
+  struct MaxDepth { bool on = false, clipped = false, shade = false; size_t lds_bytes = 0; } max_depth;
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -384,6 +398,23 @@ inline LaunchPlan plan_gradient_opacity(const LaunchFacts& f, const LaunchOverri
   return pl;
 }
 
+// a depth-limited march: one kernel of the general layout on the clipped box test, the transfer function in LDS behind the axis tables.
+// error: the transfer function does not fit (tf_lds_bytes)
+inline LaunchPlan plan_max_depth(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  const Addressing a = plan_addressing(f, o);
+  const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+  if (a.error || tf == 0 || f.quad || !(f.shading == 0 || f.shading == 1)) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am, true);
+  pl.shading = f.shading;
+  pl.max_depth.on = true;
+  pl.max_depth.clipped = w.clipped;
+  pl.max_depth.shade = f.shading == 1;
+  pl.max_depth.lds_bytes = pl.march_lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, a.am)) + tf, (size_t)kWaves * kCounterWords * 4);
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
   switch (committed_frame(f.slices, f.isosurfaces, f.projection)) {
@@ -395,6 +426,8 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   if (f.preintegrated && f.shading == 0) return plan_preintegrated(f, o); // under GRADIENT or FULL shading the mode is kept and not drawn
   if (gradient_opacity_active(f.gradient_opacity ? kGradientOpacityRamp : kGradientOpacityOff, true, f.shading, false))
     return plan_gradient_opacity(f, o); // under FULL shading, and behind an active pre-integration, the mode is kept and not drawn
+  if (max_depth_active(f.max_depth, true, f.shading, false, false, true)) // (pre-integration and gradient opacity returned above; the host compared the sizes)
+    return plan_max_depth(f, o); // under FULL shading the image is kept and not drawn
   LaunchPlan pl;
   pl.shading = f.shading == 0 || f.shading == 1 ? f.shading : 2;
   pl.orthographic = f.orthographic;
@@ -445,6 +478,7 @@ inline FrameKind frame_kind(const LaunchPlan& pl)
 {
   if (pl.preintegrated.on) return FrameKind::PreintegratedMarch;
   if (pl.gradient_opacity.on) return FrameKind::GradientOpacityMarch;
+  if (pl.max_depth.on) return FrameKind::DepthLimitedMarch;
   if (pl.slices.on) return pl.slices.context ? FrameKind::SliceContext : pl.slices.walks ? FrameKind::SliceWalk : FrameKind::SlicePlane;
   if (pl.isosurface.on)
     return pl.isosurface.context ? FrameKind::IsosurfaceContext : pl.ambient_occlusion ? FrameKind::IsosurfaceAo
@@ -464,6 +498,7 @@ inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
   case FrameKind::Projection: return project_variant_exists(pl.project.mode, pl.am, pl.project.skip, pl.project.clipped, pl.orthographic);
   case FrameKind::PreintegratedMarch: return preintegrated_variant_exists(pl.am, pl.skip, pl.preintegrated.clipped, pl.orthographic);
   case FrameKind::GradientOpacityMarch: return gradient_opacity_variant_exists(pl.gradient_opacity.shade ? 1 : 0, pl.am, pl.skip, pl.gradient_opacity.clipped, pl.orthographic);
+  case FrameKind::DepthLimitedMarch: return max_depth_variant_exists(pl.max_depth.shade ? 1 : 0, pl.am, pl.skip, pl.max_depth.clipped, pl.orthographic);
   case FrameKind::March: break;
   }
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
@@ -500,6 +535,9 @@ static_assert(preintegrated_variant_exists(0, false, true) && preintegrated_vari
 static_assert(gradient_opacity_variant_exists(0, 0, false, true) && gradient_opacity_variant_exists(1, 4, false, true, true) && !gradient_opacity_variant_exists(2, 0, false, true)
                 && !gradient_opacity_variant_exists(0, 0, false, false) && !gradient_opacity_variant_exists(1, 0, true, true) && !gradient_opacity_variant_exists(0, 5, false, true),
               "the gradient-opacity kernel: shading NONE and GRADIENT, on the clipped variants alone, for both cameras, without a skipping twin");
+static_assert(max_depth_variant_exists(0, 0, false, true) && max_depth_variant_exists(1, 4, false, true, true) && !max_depth_variant_exists(2, 0, false, true)
+                && !max_depth_variant_exists(0, 0, false, false) && !max_depth_variant_exists(1, 0, true, true) && !max_depth_variant_exists(0, 5, false, true),
+              "the depth-limited kernel: shading NONE and GRADIENT, on the clipped variants alone, for both cameras, without a skipping twin");
 static_assert(kPreintegrationLdsBudget % 16 == 0 && 3 * kPreintegrationLdsBudget <= 160 * 1024 && 4 * kPreintegrationLdsBudget > 160 * 1024, "three workgroups per CU");
 
 } // namespace ovrhip

@@ -27,6 +27,7 @@ struct RayQuery {
   bool zeroed;                      // out is zeroed first: the kernel writes a ray's header and the events it met
   bool needs_preintegration = false; // pre-integration committed in mode SEGMENTS (trailing and defaulted: the seven rows below read as they did)
   bool needs_gradient_opacity = false, takes_shade = false; // gradient opacity committed in mode RAMP; `mode` is a shading mode, NONE (0) or GRADIENT (1) (likewise)
+  bool takes_depth = false;         // one ray parameter per ray, a device pointer beside org and dir (likewise)
 };
 enum RayQueryId { kQueryProject, kQuerySlice, kQuerySliceContext, kQueryIsosurface, kQueryIsosurfaceLayers, kQueryIsosurfaceContext, kQueryIsosurfaceAo, kRayQueryCount };
 constexpr RayQuery kRayQueries[kRayQueryCount] = {
@@ -50,9 +51,15 @@ constexpr int kQueryGradientOpacity = kRayQueryIds, kRayQueryRows = kRayQueryIds
 constexpr RayQuery kGradientOpacityQueries[1] = {
   { "ovr_hip_gradient_opacity_floats",   FrameKind::GradientOpacityMarch, QueryNeeds::Nothing, nullptr,                        false,  false, true,  false, false, false, false, 8, 0, false, false, true, true },
 };
+// the tenth, ovr_hip_max_depth_floats (added with the depth limit), likewise: a row of its own behind the gradient opacity's, whose ids stay what they were.  It
+// needs nothing committed but volume and transfer function: the depths are the caller's
+constexpr int kQueryMaxDepth = kRayQueryRows, kRayQueryAll = kRayQueryRows + 1;
+constexpr RayQuery kMaxDepthQueries[1] = {
+  { "ovr_hip_max_depth_floats",          FrameKind::DepthLimitedMarch, QueryNeeds::Nothing,   nullptr,                         false,  false, true,  false, false, false, false, 8, 0, false, false, false, true, true },
+};
 constexpr const RayQuery& ray_query_row(int id)
 {
-  return id >= kRayQueryIds ? kGradientOpacityQueries[id - kRayQueryIds] : id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id];
+  return id >= kRayQueryRows ? kMaxDepthQueries[id - kRayQueryRows] : id >= kRayQueryIds ? kGradientOpacityQueries[id - kRayQueryIds] : id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id];
 }
 // the plan a query asked for is the plan of its kernel (slices: the committed set decides between the two slice kernels, as it does for a frame)
 constexpr bool query_runs(const RayQuery& d, FrameKind k) { return k == d.kind || (d.kind == FrameKind::SliceWalk && k == FrameKind::SlicePlane); }
@@ -67,6 +74,7 @@ struct RayQueryCall {
   float* out = nullptr;
   long long n = 0;
   int mode = 0, max_events = 0, rotation = 0, range_skipping = 0;
+  const float* depth = nullptr; // (takes_depth)
 };
 // what the preconditions read of the committed state
 struct QueryFacts {
@@ -85,7 +93,7 @@ inline QueryStatus query_refusal(const RayQuery& d, int code, const std::string&
 // step one of an entry, in front of anything that touches the device
 inline QueryStatus ray_query_arguments(const RayQuery& d, bool renderer, const RayQueryCall& c)
 {
-  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean)) || (d.takes_shade && (c.mode < 0 || c.mode > 1))
+  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean)) || (d.takes_shade && (c.mode < 0 || c.mode > 1)) || (d.takes_depth && !c.depth)
                    || (d.takes_max_events && (c.max_events < 1 || c.max_events > kQueryMaxEvents)) || (d.takes_rotation && (c.rotation < 0 || c.rotation >= kQueryRotations));
   return bad ? query_refusal(d, kQueryEinval, "bad arguments") : QueryStatus();
 }

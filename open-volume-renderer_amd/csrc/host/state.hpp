@@ -10,6 +10,7 @@
 #pragma GCC visibility push(hidden)
 #include "commit_plan.hpp"
 #include "gradient_opacity_host.hpp"
+#include "max_depth_host.hpp"
 #include "policy.hpp"
 #include "slices_host.hpp"
 #pragma GCC visibility pop
@@ -240,6 +241,13 @@ struct ovr_hip_renderer {
   Queued<ovrhip::host::SliceContextP> slice_context; // ovr_hip_set_slice_context; recorded under kShading like the slices.  Kept while no slice is committed: it takes effect when n > 0
   Queued<ovrhip::host::IsoContextP> isosurface_context; // ovr_hip_set_isosurface_context; recorded under kShading like the isovalues.  Kept while no isovalue is committed: it takes effect when n > 0 and no slice is committed
   Queued<ovrhip::GradientOpacityState> gradient_opacity; // ovr_hip_set_gradient_opacity (host/gradient_opacity_host.hpp); recorded under kShading like the other frame kinds.  Kept, and not drawn, while gradient_opacity_frame says no
+  // ovr_hip_set_max_depth (host/max_depth_host.hpp); recorded under kShading like the other frame kinds: every call with an image counts as a change.  Kept, and
+  // not drawn, while max_depth_frame says no.  The images: the setter copies into d_max_depth_queued (it only ever grows), a commit that applies an image swaps the
+  // two buffers; d_max_depth holds max_depth.current.width x height floats while max_depth.current.on
+  Queued<ovrhip::MaxDepthState> max_depth;
+  float* d_max_depth = nullptr;
+  float* d_max_depth_queued = nullptr;
+  size_t max_depth_capacity = 0, max_depth_queued_capacity = 0; // floats the two buffers hold
   Queued<ovrhip::host::PreintP> preintegration; // ovr_hip_set_preintegration; recorded under kShading like the other frame kinds.  Kept, and not drawn, while the committed frame is not the unshaded march
   // the integral node table of the committed transfer function (host/preintegration_host.hpp): built by the first pre-integrated frame (or tables getter) after a
   // transfer-function commit - it carries the generation of the tables it was built from and the subdivision the frame's LDS budget allowed
@@ -455,6 +463,8 @@ int bind_preintegration(ovr_hip_renderer* r, ovrhip::RayMarchParams& q);
 bool gradient_opacity_frame(const ovr_hip_renderer* r);
 // q.gradient_opacity (on) and the committed thresholds
 void fill_gradient_opacity_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q, bool on);
+// the next frame is a depth-limited march (host/max_depth_host.hpp max_depth_active over the committed state and the committed framebuffer size)
+bool max_depth_frame(const ovr_hip_renderer* r);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -112,6 +112,8 @@ void ovr_hip_destroy(ovr_hip_renderer* r)
   if (r->d_mc_minmax) (void)hipFree(r->d_mc_minmax);
   if (r->d_ao_dirs) (void)hipFree(r->d_ao_dirs);
   if (r->d_preint_nodes) (void)hipFree(r->d_preint_nodes);
+  if (r->d_max_depth) (void)hipFree(r->d_max_depth);
+  if (r->d_max_depth_queued) (void)hipFree(r->d_max_depth_queued);
   if (r->d_mc_majorant) (void)hipFree(r->d_mc_majorant);
   if (r->d_mc_occupancy) (void)hipFree(r->d_mc_occupancy);
   if (r->d_mc_fine) (void)hipFree(r->d_mc_fine);
@@ -514,6 +516,87 @@ int ovr_hip_get_gradient_opacity(const ovr_hip_renderer* r, ovr_hip_gradient_opa
   return 0;
 }
 
+} // extern "C"
+namespace {
+// one renderer's copy of the caller's image, from host memory (null: the limit is switched off), into the QUEUED buffer, which only ever grows.  The frame in
+// flight is resolved first, as ovr_hip_set_volume does: after a commit has swapped the buffers the queued one is the image an earlier frame was drawn from, and
+// no frame may see it half written.  The copy is synchronous: `host` is not referenced after the call returns
+int set_max_depth_one(ovr_hip_renderer* r, const float* host, int width, int height)
+{
+  MaxDepthState m;
+  if (host) {
+    if (int e = set_device(r)) return e;
+    if (int e = finish_frame_one(r)) return e;
+    const size_t n = (size_t)width * (size_t)height;
+    if (r->max_depth_queued_capacity < n) {
+      float* d = nullptr;
+      if (hipMalloc((void**)&d, n * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OVR_HIP_EDEVICE, "[hip] ovr_hip_set_max_depth: the image of " + std::to_string(n) + " pixels could not be allocated");
+      }
+      if (r->d_max_depth_queued) HIP_TRY(hipFree(r->d_max_depth_queued));
+      r->d_max_depth_queued = d;
+      r->max_depth_queued_capacity = n;
+    }
+    if (hipMemcpy(r->d_max_depth_queued, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(OVR_HIP_EDEVICE, "[hip] ovr_hip_set_max_depth: the copy to the device failed");
+    }
+    m.on = true; m.width = width; m.height = height;
+  }
+  std::lock_guard<std::mutex> lk(r->mtx);
+  r->max_depth.set(m);
+  return 0;
+}
+} // namespace
+extern "C" {
+
+int ovr_hip_set_max_depth(ovr_hip_renderer* r, const float* depth, int mem_kind, int32_t width, int32_t height)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (const int rule = max_depth_check(depth, mem_kind, width, height)) return fail(OVR_HIP_EINVAL, std::string("[hip] ovr_hip_set_max_depth: ") + max_depth_rule_text(rule));
+  // validated once, on the handle the caller holds; every member of a device group then uploads the same host copy of the whole image
+  std::vector<float> stage;
+  const float* host = depth;
+  if (depth && mem_kind == OVR_HIP_MEM_DEVICE) {
+    if (int e = set_device(r)) return e;
+    stage.resize((size_t)width * (size_t)height);
+    HIP_TRY(hipMemcpy(stage.data(), depth, stage.size() * sizeof(float), hipMemcpyDeviceToHost));
+    host = stage.data();
+  }
+  if (r->group.members.size() <= 1) return set_max_depth_one(r, host, width, height);
+  if (int e = finish_frame(r)) return e;
+  GroupLock gl(r);
+  return group_call(r, [=](ovr_hip_renderer* m) { return set_max_depth_one(m, host, width, height); }, [&] { return set_max_depth_one(r, host, width, height); });
+}
+
+int ovr_hip_get_max_depth(const ovr_hip_renderer* r, ovr_hip_max_depth* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_max_depth: null argument");
+  std::memset(out, 0, sizeof(*out));
+  const MaxDepthState& m = r->max_depth.current;
+  out->mode = m.on ? OVR_HIP_MAX_DEPTH_ON : OVR_HIP_MAX_DEPTH_OFF;
+  out->active = max_depth_frame(r) ? 1 : 0;
+  out->width = m.on ? m.width : 0;
+  out->height = m.on ? m.height : 0;
+  return 0;
+}
+
+int ovr_hip_get_max_depth_values(ovr_hip_renderer* r, float* depth_host, size_t capacity_floats, int32_t* width, int32_t* height)
+{
+  if (!r || !width || !height) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_max_depth_values: null argument");
+  const MaxDepthState& m = r->max_depth.current;
+  *width = m.on ? m.width : 0;
+  *height = m.on ? m.height : 0;
+  if (!m.on || !depth_host) return 0;
+  const size_t n = (size_t)m.width * (size_t)m.height;
+  if (capacity_floats < n) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_max_depth_values: the buffer holds fewer than width x height floats");
+  if (!r->d_max_depth || r->max_depth_capacity < n) return fail(OVR_HIP_ESTATE, "[hip] ovr_hip_get_max_depth_values: no image is resident");
+  if (int e = set_device(r)) return e;
+  HIP_TRY(hipMemcpy(depth_host, r->d_max_depth, n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -870,6 +953,8 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
   if (a->gradient_opacity.current.mode != b->gradient_opacity.current.mode || !(a->gradient_opacity.current.lo == b->gradient_opacity.current.lo) ||
       !(a->gradient_opacity.current.hi == b->gradient_opacity.current.hi))
     return false;
+  if (a->max_depth.current.on != b->max_depth.current.on || a->max_depth.current.width != b->max_depth.current.width || a->max_depth.current.height != b->max_depth.current.height)
+    return false; // (the images are each member's copy of the same host image)
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -985,6 +1070,14 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
       const GradientOpacityState go = r->gradient_opacity.current;
       if (r->gradient_opacity.update()) // ovr_hip_set_gradient_opacity: the same row - a call sets it, a changed mode or threshold differs
         ch.note(kShading, true, ch.of[kShading].differs || go.mode != r->gradient_opacity.current.mode || !(go.lo == r->gradient_opacity.current.lo) || !(go.hi == r->gradient_opacity.current.hi));
+    }
+    if (r->max_depth.update()) { // ovr_hip_set_max_depth: the same row - a call sets it; with an image it counts as a change, contents are not compared
+      const MaxDepthState& m = r->max_depth.current;
+      if (m.on) { // the image the setter queued becomes the committed one (the commit has finished the frame: nothing reads either)
+        std::swap(r->d_max_depth, r->d_max_depth_queued);
+        std::swap(r->max_depth_capacity, r->max_depth_queued_capacity);
+      }
+      ch.note(kShading, true, true);
     }
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
@@ -1542,12 +1635,13 @@ static_assert(kQueryEinval == OVR_HIP_EINVAL && kQueryEstate == OVR_HIP_ESTATE &
                 && kProjectMean == OVR_HIP_PROJECT_MEAN,
               "host/ray_query.hpp restates include/ovr_hip.h");
 int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, float* out, int64_t n, int32_t mode = 0, int32_t max_events = 0, int32_t rotation = 0,
-              int32_t range_skipping = 0) // (0: what the entry does not take)
+              int32_t range_skipping = 0, const float* depth = nullptr) // (0: what the entry does not take)
 {
   const RayQuery& d = ray_query_row(id);
   RayQueryCall c;
   c.org = org; c.dir = dir; c.out = out; c.n = n;
   c.mode = mode; c.max_events = max_events; c.rotation = rotation; c.range_skipping = range_skipping;
+  c.depth = depth;
   if (const QueryStatus s = ray_query_arguments(d, r != nullptr, c); s.code) return fail(s.code, s.message);
   if (int e = set_device(r)) return e;
   if (int e = finish_frame(r)) return e;
@@ -1582,6 +1676,10 @@ int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, f
     q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
     fill_gradient_opacity_params(r, q, true);
   }
+  if (d.takes_depth) { // the march's plan under the asked shading, whatever frame kind and shading mode are committed
+    q.projection = 0; q.iso_n = 0; q.slice_n = 0; q.ao_samples = 0;
+    q.pool = PoolDesc{}; q.majorant = nullptr; q.sparse_xy = nullptr; q.schedule = nullptr; q.n_schedule = 0;
+  }
   HIP_TRY(launch_ray_query(id, q, c, r->stream()));
   HIP_TRY(hipStreamSynchronize(r->stream()));
   return 0;
@@ -1611,6 +1709,11 @@ int ovr_hip_preintegrated_floats(ovr_hip_renderer* r, const float* org, const fl
 int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t shade)
 {
   return ray_query(r, kQueryGradientOpacity, org, dir, out, n, shade);
+}
+
+int ovr_hip_max_depth_floats(ovr_hip_renderer* r, const float* org, const float* dir, const float* depth, float* out, int64_t n, int32_t shade)
+{
+  return ray_query(r, kQueryMaxDepth, org, dir, out, n, shade, 0, 0, 0, depth);
 }
 
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)

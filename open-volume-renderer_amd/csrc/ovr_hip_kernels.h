@@ -307,6 +307,10 @@ struct RayMarchParams {
   int gradient_opacity;
   float gradop_lo;
   float gradop_inv_ramp;
+  // the depth limit (ovr_hip_set_max_depth; open-volume-renderer_amd/max_depth.py is the arithmetic): max_depth != nullptr on the march under shading NONE or
+  // GRADIENT = the frame is max_depth_kernel's.  width x height ray parameters (device memory, the renderer's own copy), indexed by the FULL frame's pixel index
+  // ix + iy * width, in the march's t.  Behind everything else: no other kernel reads it
+  const float* max_depth;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -377,6 +381,8 @@ hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* bloc
 //                                                                   segments taken, of them integral-branch segments, tx at exit, 0, then r, g, b, a of the pixel sample
 //   kQueryGradientOpacity (gradient_opacity_ray, ovr_hip_gradient_opacity.h; p.gradop_lo / p.gradop_inv_ramp, under shading c.mode = 0 (NONE) or 1 (GRADIENT), the
 //   perspective camera's view vector)                               steps taken, of them steps that fetched a gradient, tx at exit, steps with a > 0, then r, g, b, a of the pixel sample
+//   kQueryMaxDepth (max_depth_ray, ovr_hip_max_depth.h; c.depth = one ray parameter per ray (device), under shading c.mode = 0 (NONE) or 1 (GRADIENT), the
+//   perspective camera's view vector)                               steps taken, the cut tc, tx at exit, steps with a > 0, then r, g, b, a of the pixel sample
 struct RayQueryCall; // host/ray_query.hpp
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream);
 

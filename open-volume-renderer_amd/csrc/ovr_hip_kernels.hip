@@ -20,6 +20,7 @@
 #include "ovr_hip_slice_context.h"
 #include "ovr_hip_preintegration.h"
 #include "ovr_hip_gradient_opacity.h"
+#include "ovr_hip_max_depth.h"
 #include "ovr_hip_isosurface_context.h"
 #include "ovr_hip_update.h"
 #include "host/ray_query.hpp"
@@ -1034,6 +1035,7 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.isosurface_context = p.iso_n > 0 && p.iso_context != 0;
   f.preintegrated = p.preintegrated != 0;
   f.gradient_opacity = p.gradient_opacity != 0;
+  f.max_depth = p.max_depth != nullptr;
   return plan_launch(f, o);
 }
 
@@ -1094,7 +1096,8 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template SliceContextKernels slice_context_kernels_of<E>(const LaunchPlan&); \
   extern template IsosurfaceContextKernels isosurface_context_kernels_of<E>(const LaunchPlan&); \
   extern template PreintegratedKernels preintegrated_kernels_of<E>(const LaunchPlan&); \
-  extern template GradientOpacityKernels gradient_opacity_kernels_of<E>(const LaunchPlan&);
+  extern template GradientOpacityKernels gradient_opacity_kernels_of<E>(const LaunchPlan&); \
+  extern template MaxDepthKernels max_depth_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
 OVR_VOXEL_TYPES(OVR_X_SLICES)
@@ -1108,14 +1111,17 @@ OVR_VOXEL_TYPES(OVR_X_SLICES)
 typedef void (*QueryKernel)(const RayMarchParams, const float*, const float*, float*, long long);
 typedef void (*QueryEventsKernel)(const RayMarchParams, const float*, const float*, float*, long long, int);        // + max_events
 typedef void (*QueryRotationKernel)(const RayMarchParams, const float*, const float*, float*, long long, int, int); // + max_events, rotation
+typedef void (*QueryDepthKernel)(const RayMarchParams, const float*, const float*, const float*, float*, long long); // + one ray parameter per ray, behind dir
 struct PlanKernels {
   FrameKernels frame;
   QueryKernel query = nullptr;
   QueryEventsKernel query_events = nullptr;
   QueryRotationKernel query_rotation = nullptr;
+  QueryDepthKernel query_depth = nullptr;
   void set(QueryKernel k) { query = k; }
   void set(QueryEventsKernel k) { query_events = k; }
   void set(QueryRotationKernel k) { query_rotation = k; }
+  void set(QueryDepthKernel k) { query_depth = k; }
   template <typename V> void take(const V& v) { frame.march = v.frame; set(v.floats); } // (the pair a *_kernels_of lookup returns)
 };
 static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
@@ -1140,6 +1146,10 @@ static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
       dispatch_voxel_type<true>(t, [&](auto vt) { k.take(preintegrated_kernels_of<decltype(vt)::value>(plan)); });
     break;
   case FrameKind::GradientOpacityMarch: dispatch_voxel_type<true>(t, [&](auto vt) { k.take(gradient_opacity_kernels_of<decltype(vt)::value>(plan)); }); break;
+  case FrameKind::DepthLimitedMarch:
+    if (p.max_depth) // (the kernel loads the pixel's depth: no image, no kernel)
+      dispatch_voxel_type<true>(t, [&](auto vt) { k.take(max_depth_kernels_of<decltype(vt)::value>(plan)); });
+    break;
   case FrameKind::March: dispatch_voxel_type(t, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); }); break;
   }
   return k;
@@ -2100,6 +2110,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
   q.iso_context = 0; // (the context's own query puts it back)
   q.preintegrated = 0; // (likewise)
   q.gradient_opacity = 0; // (likewise)
+  q.max_depth = nullptr; // (likewise)
   q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
@@ -2159,7 +2170,7 @@ hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float
 // frame takes for it.  What the query does not ask about is scrubbed from the plan's facts, whatever is committed and whatever the last frame drew
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream)
 {
-  if (query < 0 || query >= kRayQueryRows) return hipErrorInvalidValue;
+  if (query < 0 || query >= kRayQueryAll) return hipErrorInvalidValue;
   const RayQuery& d = ray_query_row(query);
   if (c.n <= 0) return hipSuccess;
   const bool skip = d.takes_range_skipping && c.range_skipping != 0 && !(d.takes_mode && c.mode == kProjectMean); // (a mean needs every sample: it has no skipping twin)
@@ -2172,6 +2183,7 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   if (d.needs_tf && (!p.tf_color || !p.tf_alpha)) return hipErrorInvalidValue;
   if (d.needs_preintegration && (!p.preint_nodes || p.preint_m1 < 1)) return hipErrorInvalidValue;
   if (d.takes_shade && (c.mode < 0 || c.mode > 1)) return hipErrorInvalidValue;
+  if (d.takes_depth && !c.depth) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, skip);
   switch (d.kind) {
   case FrameKind::Projection: q.projection = c.mode; q.iso_n = 0; q.ao_samples = 0; break; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
@@ -2183,12 +2195,16 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   case FrameKind::IsosurfaceAo: q.iso_translucent = 1; q.shading = 2; break;        // (with full shading, the committed samples)
   case FrameKind::PreintegratedMarch: q.preintegrated = 1; q.shading = 0; q.projection = 0; q.iso_n = 0; q.ao_samples = 0; break; // (the unshaded march's plan, whatever is committed)
   case FrameKind::GradientOpacityMarch: q.gradient_opacity = 1; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0; break; // (the march's plan under the asked shading, whatever is committed)
+  case FrameKind::DepthLimitedMarch: // (the march's plan under the asked shading, whatever is committed; the twin reads c.depth, one value per ray, never q.max_depth)
+    q.max_depth = c.depth; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0;
+    break;
   default: return hipErrorInvalidValue;
   }
   const LaunchPlan pl = plan_raymarch(q);
   if (pl.error || !query_runs(d, frame_kind(pl))) return hipErrorInvalidValue; // (the kernels are filed by signature: a plan of another kind must not lend its own)
   const PlanKernels k = plan_kernels(q, pl);
   const dim3 grid(quad_ray_blocks(c.n));
+  if (d.takes_depth) return grid.x && k.query_depth ? launch_variant(k.query_depth, grid, kBlock, pl.march_lds_bytes, stream, q, c.org, c.dir, c.depth, c.out, c.n) : hipErrorInvalidValue;
   if (!grid.x || !(d.takes_rotation ? k.query_rotation != nullptr : d.takes_max_events ? k.query_events != nullptr : k.query != nullptr)) return hipErrorInvalidValue;
   if (d.zeroed)
     if (hipError_t e = hipMemsetAsync(c.out, 0, (size_t)c.n * ray_query_record_floats(d, c.max_events) * sizeof(float), stream)) return e;

@@ -498,6 +498,67 @@ class DeviceHIP:
         o = self._ray_query("gradient_opacity_rays", "ovr_hip_gradient_opacity_floats", org, direction, 8, int(shade))
         return o[:, 0].astype(np.int64), o[:, 1].astype(np.int64), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
 
+    # the depth limit (include/ovr_hip.h ovr_hip_set_max_depth; max_depth.py is the arithmetic): the march that ends every ray of a pixel on a ray parameter the
+    # caller hands in, so that the frame is what lies in front of the caller's opaque geometry.  Queued, applied at commit; every call resets the accumulation;
+    # kept, and not drawn, under FULL shading, while slices, isovalues or a projection are committed, behind an active pre-integration or gradient opacity, and
+    # while the image's size is not the committed framebuffer's.
+    def set_max_depth(self, depth=None, size=None):
+        """depth: a (height, width) float32 array in the frame's pixel order - the order of mapframe's rgba - or a flat one with size = (width, height); None
+        switches the limit off.  UNITS: the march's t - world length along the normalised ray direction from the ray's origin: under the perspective camera the
+        Euclidean distance from the camera position (not a planar z, not a z-buffer value; max_depth.ray_distance_from_planar converts one), under the
+        orthographic camera the distance from the image plane through `from`.  +inf or NaN: no surface at that pixel.  Copied at once.  ValueError where the
+        ABI says EINVAL"""
+        if depth is None:
+            L.check(self._lib.ovr_hip_set_max_depth(self._h, None, L.MEM_HOST, 0, 0))
+            return
+        a = np.ascontiguousarray(depth, dtype=np.float32)
+        if size is None:
+            if a.ndim != 2:
+                raise RuntimeError("set_max_depth: the image is a (height, width) array, or a flat one with size = (width, height)")
+            w, h = a.shape[1], a.shape[0]
+        else:
+            w, h = int(size[0]), int(size[1])
+            if w >= 1 and h >= 1 and w * h <= 2 ** 31 - 1 and a.size != w * h:      # (a size the ABI refuses is refused there, before the image is read)
+                raise RuntimeError("set_max_depth: the image holds width * height values")
+        code = self._lib.ovr_hip_set_max_depth(self._h, a.ctypes.data, L.MEM_HOST, int(w), int(h))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def get_max_depth(self, values=False):
+        """ovr_hip_max_depth, the COMMITTED state: mode, active (1: the next frame is a depth-limited frame), width, height; values=True: (state, the committed
+        image as a (height, width) float32 array, None in mode OFF)"""
+        c = L.MaxDepth()
+        L.check(self._lib.ovr_hip_get_max_depth(self._h, C.byref(c)))
+        if not values:
+            return c
+        w, h = C.c_int32(0), C.c_int32(0)
+        L.check(self._lib.ovr_hip_get_max_depth_values(self._h, None, 0, C.byref(w), C.byref(h)))
+        if w.value < 1 or h.value < 1:
+            return c, None
+        out = np.empty((h.value, w.value), np.float32)
+        L.check(self._lib.ovr_hip_get_max_depth_values(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(w), C.byref(h)))
+        return c, out
+
+    def max_depth_rays(self, org, direction, depth, shade=0):
+        """depth-limited rays as the kernel evaluates them (ovr_hip_max_depth_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as
+        given - ray i ending on depth[i] (n,), under shading `shade` (0 NONE, 1 GRADIENT) -> steps taken (n,) int64, the cut tc (n,) float32, tx at exit (n,)
+        float32, steps with a > 0 (n,) int64, rgba (n, 4) float32 of the pixel sample"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in (org, direction, depth)]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n or t[2].numel() != n:
+            raise RuntimeError("max_depth_rays: org and direction hold three floats per ray, depth one")
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        code = self._lib.ovr_hip_max_depth_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), out.data_ptr(), n, int(shade))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+        o = out.cpu().numpy()
+        return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
+
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
     def set_isosurfaces(self, values=(), opacities=None):

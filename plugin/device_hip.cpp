@@ -17,6 +17,7 @@
 #include "iso_context_env.hpp"
 #include "../open-volume-renderer_amd/csrc/host/preintegration_host.hpp" // (HIP-free: parse_preintegration)
 #include "../open-volume-renderer_amd/csrc/host/gradient_opacity_host.hpp" // (HIP-free: parse_gradient_opacity)
+#include "../open-volume-renderer_amd/csrc/host/max_depth_host.hpp" // (HIP-free: max_depth_read_file)
 
 #include <chrono>
 #include <cmath>
@@ -288,7 +289,22 @@ public:
   // DeviceOptix7::Impl::commit (device_impl.cpp:113-197): forward every changed TransactionalValue
   void commit() override
   {
-    if (params.fbsize.update()) check(ovr_hip_set_fbsize(h, params.fbsize.ref().x, params.fbsize.ref().y));
+    if (params.fbsize.update()) {
+      check(ovr_hip_set_fbsize(h, params.fbsize.ref().x, params.fbsize.ref().y));
+      // The depth limit (ovr_hip_set_max_depth): OVR_HIP_MAX_DEPTH=<path> names a raw little-endian float32 file of width * height ray parameters in the frame's
+      // pixel order (pixel (ix, iy) at ix + iy * width), read whenever the framebuffer size is set.  UNITS: the march's t - world length along the normalised ray
+      // direction from the ray's origin: under the perspective camera the Euclidean distance from the camera position, not a planar z and not a z-buffer value;
+      // under the orthographic camera the distance from the image plane through `from`.  +inf or NaN: no surface at that pixel.  Unset: nothing is called
+      if (const char* dv = std::getenv("OVR_HIP_MAX_DEPTH")) {
+        const int w = params.fbsize.ref().x, ht = params.fbsize.ref().y;
+        std::vector<float> depth;
+        if (!ovrhip::max_depth_read_file(dv, w, ht, &depth))
+          throw std::runtime_error("[hip] OVR_HIP_MAX_DEPTH expects a raw little-endian float32 file of exactly width * height values (" + std::to_string(w) + " x " + std::to_string(ht) + ")");
+        check(ovr_hip_set_max_depth(h, depth.data(), OVR_HIP_MEM_HOST, w, ht));
+        const bool quiet = std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0';
+        if (!quiet) std::fprintf(stderr, "[hip] depth limit: %d x %d ray parameters from %s (drawn by march frames under shading NONE or GRADIENT)\n", w, ht, dv);
+      }
+    }
     if (params.camera.update()) {
       const ovr::scene::Camera& c = params.camera.ref();
       const float from[3] = { c.from.x, c.from.y, c.from.z }, at[3] = { c.at.x, c.at.y, c.at.z }, up[3] = { c.up.x, c.up.y, c.up.z };

@@ -797,6 +797,51 @@ int ovr_hip_get_max_depth(const ovr_hip_renderer* r, ovr_hip_max_depth* out);
  * written (0 in mode OFF, where nothing is copied); depth_host == NULL asks for the size alone */
 int ovr_hip_get_max_depth_values(ovr_hip_renderer* r, float* depth_host, size_t capacity_floats, int32_t* width, int32_t* height);
 
+/* Depth layer (added within ABI v11: new entry points and one new struct only): the counterpart of the depth limit - the march says
+ * WHERE along each ray its picture is, so that an application can write the volume into its z-buffer, pick the structure under the cursor, reproject a frame,
+ * or hand one volume's depth to a second renderer as that renderer's limit.  VTK, ParaView and OSPRay hand a depth out with the picture; the reference has no
+ * such output: like the clip box and the depth limit, the definition is this project's.  open-volume-renderer_amd/depth_output.py is the arithmetic in numpy,
+ * the normative text.
+ * Per pixel sample, with (t0, t1, hit), step and the cut tc exactly as the depth limit forms them (tc = t1 when no limit applies), the march's loop with four
+ * more values, S = 0, d = 0, reached = false, k = 0.  Every step that is taken forms tr = 1 - alpha and alpha = fma(tr, a, alpha) as before, and also
+ *   S = fma(tr * tm, a, S)                         - tm the step's midpoint: a colour channel whose colour is tm
+ *   if (!reached && a > 0 && alpha >= threshold)   - alpha AFTER the step
+ *     reached = true, d = ty, k = steps taken so far, this one included        - ty is the BACK end of the crossing step
+ * Nothing else of the loop changes: rgb, alpha, the termination test and the counters are the march's operation for operation.  The pixel sample's layer is
+ * (reached ? d : 0, S, reached ? 1 : 0); samples per pixel sum and are scaled by 1 / spp as the march's gradient layer is, and like that layer the one
+ * ovr_hip_mapframe hands out is the LAST frame's (the layer is not accumulated; rgba is).  From a frame:
+ *   threshold depth             = layer[0] / layer[2] where layer[2] > 0
+ *   alpha-weighted mean depth   = layer[1] / rgba[3]  where rgba[3] > 0      (rgba[3] is the sum of tr * a exactly; of the same frame: without accumulation)
+ *   layer[2]                    = the share of the pixel's samples that reached the threshold
+ * (depth_output.resolve; +inf - the depth limit's "no surface" - where a depth is undefined).  UNITS: every depth is the march's own t, exactly what
+ * ovr_hip_set_max_depth takes (depth_output.planar_from_ray_distance converts to an eye-space z).
+ * threshold: a float in (0, 0.9999f].  The smallest positive normal float gives the back end of the first step with opacity, 0.5 the "median" surface; above
+ * the march's early-termination literal a crossing could only happen by overshoot, and is refused.  ty is recorded and not tm: handed back as a depth limit,
+ * fminf(tx + step, d) == d on the crossing step, and the limited march takes exactly the same k steps with the same bits.
+ * A frame is a depth frame iff the committed frame is the march (no slices, isovalues or projection), the mode is ON, the committed shading mode is
+ * OVR_HIP_SHADE_NONE or OVR_HIP_SHADE_GRADIENT, and neither pre-integration nor gradient opacity is active (their own rules and `active` flags stay what they
+ * are).  Otherwise the setting is kept and not drawn.  A depth frame's rgba and counters are the march's bit for bit; the layer replaces the gradient layer,
+ * under GRADIENT too (as projections do).  A committed depth image of the framebuffer's size is applied by the depth frame - same tc, same load, one per pixel -
+ * and `limited` says so; without one the kernel takes z = +inf without a load.
+ * Queued, applied at commit, recorded with the other frame kinds: every call resets the accumulation and voids nothing else.  Until it is called with ON every
+ * frame, counter, kernel and getter is what it was.  EINVAL, with the state kept: an unknown mode; mode ON with threshold NaN, <= 0 or > 0.9999f.  A device
+ * group forwards the call.
+ * Not done: FULL shading; the layer on projections, isosurfaces, slices, the two contexts, pre-integration and gradient opacity (projection and isosurface
+ * frames carry a distance of their own); accumulating the layer over frames; empty-space skipping, the tuner and the layout choice for the new kernel; the mode
+ * walk of tests/mode_walk.py over the new kind.
+ * Kernel: depth_output_kernel, the depth-limited kernel's variants and frame shell with S, the step count and the crossing in the recurrence.  Measured:
+ * tools/depth_output_bench.py, DESIGN.md section 27. */
+#define OVR_HIP_DEPTH_OUTPUT_OFF 0
+#define OVR_HIP_DEPTH_OUTPUT_ON 1
+int ovr_hip_set_depth_output(ovr_hip_renderer* r, int32_t mode, float threshold);
+typedef struct ovr_hip_depth_output {
+  int32_t mode;      /* COMMITTED */
+  int32_t active;    /* 1: the next frame is a depth frame - see above */
+  int32_t limited;   /* 1: ... and it applies the committed depth image */
+  float threshold;   /* COMMITTED; 0 in mode OFF */
+} ovr_hip_depth_output;
+int ovr_hip_get_depth_output(const ovr_hip_renderer* r, ovr_hip_depth_output* out);
+
 /* Shadow cache (added within ABI v11 like the clip box: new entry points and one new struct only).  Full shading marches one shadow ray
  * per shaded sample towards ONE directional light; volume, transfer function and light are static while a camera orbits, so the shadow term is a
  * view-independent scalar field.  It can be computed once on a lattice and read back with one trilinear tap:
@@ -999,6 +1044,11 @@ int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org_device
  * the pixel sample (tc and tx 0 for a ray that misses the box).  ESTATE without a volume or without a committed transfer function; EINVAL: a null pointer,
  * n < 0, shade outside {0, 1}. */
 int ovr_hip_max_depth_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, const float* depth_device, float* out_device, int64_t n, int32_t shade);
+/* a depth-output ray as the kernel evaluates it (added with the depth layer): as ovr_hip_max_depth_floats, through the device function the depth frame's kernel
+ * calls, with crossing threshold `threshold`; depth_device == NULL means no limit on any ray.  Per ray 12 floats: the depth limit's eight, then reached (0 / 1),
+ * d, k, S.  Needs nothing committed but volume and transfer function (ESTATE without).  EINVAL: a null org, dir or out, n < 0, shade outside {0, 1}, a
+ * threshold ovr_hip_set_depth_output refuses. */
+int ovr_hip_depth_output_floats(ovr_hip_renderer* r, const float* org_device, const float* dir_device, const float* depth_device_or_null, float* out_device, int64_t n, int32_t shade, float threshold);
 /* the pixel rays as the kernels form them (added with the orthographic camera): the world origin and direction of sample `sample` (0 ... spp - 1) of frame
  * `frame_index` (1-based) for every pixel, width x height x 6 floats in image order (a device buffer of capacity_floats floats) - through the device function
  * every frame kernel calls, with the COMMITTED camera, framebuffer size, jitter mode, noise tile and samples per pixel.  Needs a committed framebuffer and no

@@ -6,7 +6,7 @@ one-process-per-GPU runs (tiles) and the synthetic inputs the reference does not
 from . import _lib
 from ._lib import (GRID_CELL_CENTRED, GRID_VERTEX_CENTRED, JITTER_BLUE_NOISE, JITTER_TEA, PROJECT_MAXIMUM, PROJECT_MEAN, PROJECT_MINIMUM, PROJECT_OFF, RECONSTRUCT_FILL, RECONSTRUCT_OFF, SHADOWS_CACHED, SHADOWS_MARCHED, SHADOWS_SUPPLIED, SHADE_FULL, SHADE_GRADIENT, SHADE_NONE)
 from .renderer import (Camera, CrossDeviceBuffer, DeviceHIP, FrameBufferData, Scene, TransferFunction, create_renderer)
-from . import camera, clipping, convergence, gradient_opacity, imageio, isosurface, isosurface_context, lighting, max_depth, preintegration, projection, reconstruction, shadow_cache, slice_context, slices, synth, tiles, vidi3d
+from . import camera, clipping, convergence, depth_output, gradient_opacity, imageio, isosurface, isosurface_context, lighting, max_depth, preintegration, projection, reconstruction, shadow_cache, slice_context, slices, synth, tiles, vidi3d
 
 __all__ = ["Camera", "CrossDeviceBuffer", "DeviceHIP", "FrameBufferData", "Scene", "TransferFunction", "create_renderer",
-           "camera", "clipping", "convergence", "gradient_opacity", "imageio", "isosurface", "isosurface_context", "lighting", "max_depth", "preintegration", "projection", "reconstruction", "shadow_cache", "slice_context", "slices", "synth", "tiles", "vidi3d", "JITTER_TEA", "JITTER_BLUE_NOISE", "SHADE_NONE", "SHADE_GRADIENT", "SHADE_FULL", "GRID_CELL_CENTRED", "GRID_VERTEX_CENTRED", "RECONSTRUCT_OFF", "RECONSTRUCT_FILL", "SHADOWS_MARCHED", "SHADOWS_CACHED", "SHADOWS_SUPPLIED", "PROJECT_OFF", "PROJECT_MAXIMUM", "PROJECT_MINIMUM", "PROJECT_MEAN"]
+           "camera", "clipping", "convergence", "depth_output", "gradient_opacity", "imageio", "isosurface", "isosurface_context", "lighting", "max_depth", "preintegration", "projection", "reconstruction", "shadow_cache", "slice_context", "slices", "synth", "tiles", "vidi3d", "JITTER_TEA", "JITTER_BLUE_NOISE", "SHADE_NONE", "SHADE_GRADIENT", "SHADE_FULL", "GRID_CELL_CENTRED", "GRID_VERTEX_CENTRED", "RECONSTRUCT_OFF", "RECONSTRUCT_FILL", "SHADOWS_MARCHED", "SHADOWS_CACHED", "SHADOWS_SUPPLIED", "PROJECT_OFF", "PROJECT_MAXIMUM", "PROJECT_MINIMUM", "PROJECT_MEAN"]

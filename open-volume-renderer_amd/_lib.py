@@ -244,6 +244,18 @@ class MaxDepth(C.Structure):
     ]
 
 
+DEPTH_OUTPUT_OFF, DEPTH_OUTPUT_ON = 0, 1
+
+
+class DepthOutput(C.Structure):
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("active", C.c_int32),
+        ("limited", C.c_int32),
+        ("threshold", C.c_float),
+    ]
+
+
 MAX_AO_SAMPLES, AO_ROTATIONS = 16, 16
 
 
@@ -376,6 +388,9 @@ SYMBOLS = {
     "ovr_hip_get_max_depth": (C.c_int, [_H, C.POINTER(MaxDepth)]),
     "ovr_hip_get_max_depth_values": (C.c_int, [_H, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ovr_hip_max_depth_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "ovr_hip_set_depth_output": (C.c_int, [_H, C.c_int32, C.c_float]),
+    "ovr_hip_get_depth_output": (C.c_int, [_H, C.POINTER(DepthOutput)]),
+    "ovr_hip_depth_output_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float]),
     "ovr_hip_set_isosurfaces": (C.c_int, [_H, C.POINTER(C.c_float), C.c_int32]),
     "ovr_hip_get_isosurfaces": (C.c_int, [_H, C.POINTER(Isosurfaces)]),
     "ovr_hip_isosurface_floats": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -99,7 +99,7 @@ constexpr Row kRows[] = {
   { kAccumulation, kOnSet, kChanged, kTunerChanged },
   { kSamplingRate, kOnSet, kChanged, kTunerChanged },
   { kSamplingRate, kOnDiffers, kLatticeStale, kTunerKeeps },
-  // (the frame kinds - ovr_hip_set_projection, ovr_hip_set_isosurfaces, ovr_hip_set_ambient_occlusion, ovr_hip_set_slices, ovr_hip_set_slice_context, ovr_hip_set_isosurface_context, ovr_hip_set_preintegration, ovr_hip_set_gradient_opacity, ovr_hip_set_max_depth - are recorded under kShading: any call
+  // (the frame kinds - ovr_hip_set_projection, ovr_hip_set_isosurfaces, ovr_hip_set_ambient_occlusion, ovr_hip_set_slices, ovr_hip_set_slice_context, ovr_hip_set_isosurface_context, ovr_hip_set_preintegration, ovr_hip_set_gradient_opacity, ovr_hip_set_max_depth, ovr_hip_set_depth_output - are recorded under kShading: any call
   // starts the accumulation over, and voids nothing else - no majorant, range, lattice, schedule or block list depends on which kernel draws the frame)
   { kShading, kOnSet, kChanged, kTunerChanged },
   { kJitter, kOnSet, kChanged | kResort, kTunerChanged },

@@ -343,6 +343,10 @@ bool max_depth_frame(const ovr_hip_renderer* r)
   return max_depth_active(m.on && r->d_max_depth != nullptr, committed_frame(r) == CommittedFrame::March, r->shading.current, preintegrated_frame(r), gradient_opacity_frame(r),
                           max_depth_size_matches(m, r->fbsize.current.w, r->fbsize.current.h));
 }
+bool depth_output_frame(const ovr_hip_renderer* r)
+{
+  return depth_output_active(r->depth_output.current.mode == kDepthOutputOn, committed_frame(r) == CommittedFrame::March, r->shading.current, preintegrated_frame(r), gradient_opacity_frame(r));
+}
 int bind_preintegration(ovr_hip_renderer* r, RayMarchParams& q)
 {
   q.preintegrated = 1;
@@ -373,10 +377,10 @@ int bind_preintegration(ovr_hip_renderer* r, RayMarchParams& q)
   q.preint_nodes = r->d_preint_nodes;
   return 0;
 }
-// a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces, the slices, the pre-integrated, the gradient-opacity or the depth-limited march
+// a frame drawn by one kernel in the march's place, from the general layout: a projection, the isosurfaces, the slices, the pre-integrated, the gradient-opacity, the depth-limited or the depth-output march
 static bool in_place_frame(const RayMarchParams& P)
 {
-  return ovrhip::committed_frame(P.slice_n, P.iso_n, P.projection) != CommittedFrame::March || P.preintegrated != 0 || P.gradient_opacity != 0 || P.max_depth != nullptr;
+  return ovrhip::committed_frame(P.slice_n, P.iso_n, P.projection) != CommittedFrame::March || P.preintegrated != 0 || P.gradient_opacity != 0 || P.max_depth != nullptr || P.depth_tau > 0.f;
 }
 
 // step 2, continued: tables, shard, jitter, counters
@@ -411,6 +415,7 @@ static int fill_table_params(ovr_hip_renderer* r)
   P.preint_nodes = nullptr;
   fill_gradient_opacity_params(r, P, gradient_opacity_frame(r));
   P.max_depth = max_depth_frame(r) ? r->d_max_depth : nullptr; // (the image of the committed framebuffer's size: the kernel indexes it as it indexes the frame)
+  P.depth_tau = depth_output_frame(r) ? r->depth_output.current.threshold : 0.f; // (> 0 in mode ON: the depth frame, which applies P.max_depth where it is bound)
   return 0;
 }
 
@@ -718,7 +723,7 @@ int enqueue_frame(ovr_hip_renderer* r)
     if (int e = ensure_reconstruction(r)) return e;
   if (int e = reset_accumulation(r, f)) return e;
   fill_target_params(r, f);
-  if (committed_frame(r) != CommittedFrame::March || preintegrated_frame(r) || gradient_opacity_frame(r) || max_depth_frame(r)) bind_general_layout(r);
+  if (committed_frame(r) != CommittedFrame::March || preintegrated_frame(r) || gradient_opacity_frame(r) || max_depth_frame(r) || depth_output_frame(r)) bind_general_layout(r);
   else choose_layout(r, st);
   if (int e = fill_table_params(r)) return e;
   if (int e = choose_skipping(r, f)) return e;
@@ -894,7 +899,7 @@ static int read_frame_stats(ovr_hip_renderer* r)
   // a frame of one kernel in the march's place: which twin ran (the adaptive-skipping probe had no say), kept for the kind's getter
   switch (frame_kind(r->plan)) {
   case FrameKind::March: break;
-  case FrameKind::PreintegratedMarch: case FrameKind::GradientOpacityMarch: case FrameKind::DepthLimitedMarch: r->stats.skipping_kernels = 0; break; // (they fetch every step)
+  case FrameKind::PreintegratedMarch: case FrameKind::GradientOpacityMarch: case FrameKind::DepthLimitedMarch: case FrameKind::DepthOutputMarch: r->stats.skipping_kernels = 0; break; // (they fetch every step)
   case FrameKind::Projection: r->stats.skipping_kernels = r->projection_skipped = r->plan.project.skip; break;
   case FrameKind::Isosurface: case FrameKind::IsosurfaceLayers: case FrameKind::IsosurfaceAo: case FrameKind::IsosurfaceContext:
     r->stats.skipping_kernels = r->isosurface_skipped = r->plan.isosurface.skip;

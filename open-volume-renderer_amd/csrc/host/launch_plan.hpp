@@ -7,6 +7,7 @@
 // committed_frame is the ONLY statement of which committed state is drawn, frame_kind the only reading of a plan's kind (tests/test_ray_query_table.py).
 #pragma once
 
+#include "depth_output_host.hpp"
 #include "gradient_opacity_host.hpp"
 #include "max_depth_host.hpp"
 #include "preintegration_host.hpp"
@@ -145,6 +146,14 @@ constexpr bool max_depth_variant_exists(int shade, int am, bool skip, bool clipp
   return (shade == 0 || shade == 1) && clipped && !skip && am >= 0 && am <= 4;
 }
 
+// depth_output_kernel<VT, am, shade, orthographic> (open-volume-renderer_amd/depth_output.py is the arithmetic): the march that also
+// writes where along each ray it became opaque - the depth-limited kernel's variants exactly: ON THE CLIPPED VARIANTS ALONE, for shading NONE and GRADIENT and
+// both cameras, of the general layouts; it fetches every step: no skipping twin
+constexpr bool depth_output_variant_exists(int shade, int am, bool skip, bool clipped, bool orthographic = false)
+{
+  return max_depth_variant_exists(shade, am, skip, clipped, orthographic);
+}
+
 // ---- LDS arithmetic
 // the transfer function always lives in LDS; 0 = does not fit next to the request queues (the frame is an error)
 // (+ 32: both tables carry one more entry, a copy of their last one - stage_tf)
@@ -191,7 +200,7 @@ static_assert(committed_frame(1, 1, 1) == CommittedFrame::Slices && committed_fr
                 && committed_frame(0, 0, 0) == CommittedFrame::March,
               "slices over isovalues over projection over march");
 // one value per kernel family that can stand in the march's place (frame_kind below reads it off a plan)
-enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext, PreintegratedMarch, GradientOpacityMarch, DepthLimitedMarch };
+enum class FrameKind { March, Projection, Isosurface, IsosurfaceLayers, IsosurfaceAo, IsosurfaceContext, SlicePlane, SliceWalk, SliceContext, PreintegratedMarch, GradientOpacityMarch, DepthLimitedMarch, DepthOutputMarch };
 
 // ---- facts -> plan
 struct LaunchFacts {
@@ -225,6 +234,8 @@ struct LaunchFacts {
   bool preintegrated = false;         // pre-integration is committed in mode SEGMENTS (ovr_hip_set_preintegration): the unshaded march takes the pre-integrated kernel - read only while the committed frame is the march and shading == 0
   bool gradient_opacity = false;      // gradient opacity is committed in mode RAMP (ovr_hip_set_gradient_opacity): the march under shading NONE or GRADIENT takes the gradient-opacity kernel - read only while the committed frame is the march and the frame is not a pre-integrated one
   bool max_depth = false;             // a depth image of the framebuffer's size is committed (ovr_hip_set_max_depth): the march under shading NONE or GRADIENT takes the depth-limited kernel - read only while the committed frame is the march and neither pre-integration nor gradient opacity draws it
+  bool depth_output = false;          // depth output is committed in mode ON (ovr_hip_set_depth_output): the march under shading NONE or GRADIENT takes the depth-output kernel, which applies the depth limit itself where max_depth is set - read only while the committed frame is the march and neither pre-integration nor gradient opacity draws it
+  float depth_threshold = 0.f;        // its tau (the kernel reads RayMarchParams::depth_tau; the plan carries it for the record)
 };
 // the environment switches OVR_HIP_ADDRESSING / OVR_HIP_DEEP / OVR_HIP_SHADE_BLOCKS as data (diagnostics and measurements)
 struct LaunchOverrides { int addressing = -1, deep = -1, shade_blocks = 0; };
@@ -262,6 +273,9 @@ struct LaunchPlan {
   // a depth-limited march (LaunchFacts::max_depth on the march under shading NONE or GRADIENT): max_depth_kernel in the march's place, nothing else of the plan
   // but `am` is read.  LDS: [axis tables][transfer function], the slice context's carve; shade: the GRADIENT-shaded kernel
   struct MaxDepth { bool on = false, clipped = false, shade = false; size_t lds_bytes = 0; } max_depth;
+  // a depth-output march (LaunchFacts::depth_output on the march under shading NONE or GRADIENT): depth_output_kernel in the march's place, nothing else of the
+  // plan but `am` is read.  LDS: the depth-limited march's carve; shade: the GRADIENT-shaded kernel; limited: a depth image is bound and the kernel loads it
+  struct DepthOutput { bool on = false, clipped = false, shade = false, limited = false; size_t lds_bytes = 0; } depth_output;
 };
 
 // the deep rounds' rule without the kernel's own conditions
@@ -415,6 +429,24 @@ inline LaunchPlan plan_max_depth(const LaunchFacts& f, const LaunchOverrides& o)
   return pl;
 }
 
+// a depth-output march: the depth-limited march's plan with the depth layer's kernel - one kernel of the general layout on the clipped box test, the transfer
+// function in LDS behind the axis tables.  error: the transfer function does not fit (tf_lds_bytes)
+inline LaunchPlan plan_depth_output(const LaunchFacts& f, const LaunchOverrides& o)
+{
+  LaunchPlan pl;
+  const Addressing a = plan_addressing(f, o);
+  const size_t tf = tf_lds_bytes(f.n_color, f.n_alpha);
+  if (a.error || tf == 0 || f.quad || !(f.shading == 0 || f.shading == 1)) { pl.error = true; return pl; }
+  const WalkFrame w = plan_walk_frame(pl, f, a.am, true);
+  pl.shading = f.shading;
+  pl.depth_output.on = true;
+  pl.depth_output.clipped = w.clipped;
+  pl.depth_output.shade = f.shading == 1;
+  pl.depth_output.limited = f.max_depth;
+  pl.depth_output.lds_bytes = pl.march_lds_bytes = std::max<size_t>(align16(axis_table_bytes(f.nx, f.ny, f.nz, a.am)) + tf, (size_t)kWaves * kCounterWords * 4);
+  return pl;
+}
+
 inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = LaunchOverrides())
 {
   switch (committed_frame(f.slices, f.isosurfaces, f.projection)) {
@@ -426,6 +458,8 @@ inline LaunchPlan plan_launch(const LaunchFacts& f, const LaunchOverrides& o = L
   if (f.preintegrated && f.shading == 0) return plan_preintegrated(f, o); // under GRADIENT or FULL shading the mode is kept and not drawn
   if (gradient_opacity_active(f.gradient_opacity ? kGradientOpacityRamp : kGradientOpacityOff, true, f.shading, false))
     return plan_gradient_opacity(f, o); // under FULL shading, and behind an active pre-integration, the mode is kept and not drawn
+  if (depth_output_active(f.depth_output, true, f.shading, false, false)) // (pre-integration and gradient opacity returned above)
+    return plan_depth_output(f, o); // under FULL shading the setting is kept and not drawn; a committed depth image is applied by this kernel (f.max_depth)
   if (max_depth_active(f.max_depth, true, f.shading, false, false, true)) // (pre-integration and gradient opacity returned above; the host compared the sizes)
     return plan_max_depth(f, o); // under FULL shading the image is kept and not drawn
   LaunchPlan pl;
@@ -479,6 +513,7 @@ inline FrameKind frame_kind(const LaunchPlan& pl)
   if (pl.preintegrated.on) return FrameKind::PreintegratedMarch;
   if (pl.gradient_opacity.on) return FrameKind::GradientOpacityMarch;
   if (pl.max_depth.on) return FrameKind::DepthLimitedMarch;
+  if (pl.depth_output.on) return FrameKind::DepthOutputMarch;
   if (pl.slices.on) return pl.slices.context ? FrameKind::SliceContext : pl.slices.walks ? FrameKind::SliceWalk : FrameKind::SlicePlane;
   if (pl.isosurface.on)
     return pl.isosurface.context ? FrameKind::IsosurfaceContext : pl.ambient_occlusion ? FrameKind::IsosurfaceAo
@@ -499,6 +534,7 @@ inline bool plan_variants_exist(const LaunchPlan& pl, bool f32_general)
   case FrameKind::PreintegratedMarch: return preintegrated_variant_exists(pl.am, pl.skip, pl.preintegrated.clipped, pl.orthographic);
   case FrameKind::GradientOpacityMarch: return gradient_opacity_variant_exists(pl.gradient_opacity.shade ? 1 : 0, pl.am, pl.skip, pl.gradient_opacity.clipped, pl.orthographic);
   case FrameKind::DepthLimitedMarch: return max_depth_variant_exists(pl.max_depth.shade ? 1 : 0, pl.am, pl.skip, pl.max_depth.clipped, pl.orthographic);
+  case FrameKind::DepthOutputMarch: return depth_output_variant_exists(pl.depth_output.shade ? 1 : 0, pl.am, pl.skip, pl.depth_output.clipped, pl.orthographic);
   case FrameKind::March: break;
   }
   return march_variant_exists(pl.shading, pl.am, pl.pooled, pl.skip, pl.march.lds_staged, pl.march.deep, pl.march.material, pl.march.clipped, f32_general,
@@ -538,6 +574,10 @@ static_assert(gradient_opacity_variant_exists(0, 0, false, true) && gradient_opa
 static_assert(max_depth_variant_exists(0, 0, false, true) && max_depth_variant_exists(1, 4, false, true, true) && !max_depth_variant_exists(2, 0, false, true)
                 && !max_depth_variant_exists(0, 0, false, false) && !max_depth_variant_exists(1, 0, true, true) && !max_depth_variant_exists(0, 5, false, true),
               "the depth-limited kernel: shading NONE and GRADIENT, on the clipped variants alone, for both cameras, without a skipping twin");
+static_assert(depth_output_variant_exists(0, 0, false, true) && depth_output_variant_exists(1, 4, false, true, true) && !depth_output_variant_exists(2, 0, false, true)
+                && !depth_output_variant_exists(0, 0, false, false) && !depth_output_variant_exists(1, 0, true, true) && !depth_output_variant_exists(0, 5, false, true),
+              "the depth-output kernel: the depth-limited kernel's variants");
+static_assert((int)FrameKind::DepthOutputMarch == (int)FrameKind::DepthLimitedMarch + 1, "new frame kinds are appended: the ids of the others stay");
 static_assert(kPreintegrationLdsBudget % 16 == 0 && 3 * kPreintegrationLdsBudget <= 160 * 1024 && 4 * kPreintegrationLdsBudget > 160 * 1024, "three workgroups per CU");
 
 } // namespace ovrhip

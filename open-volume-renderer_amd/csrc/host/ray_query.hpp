@@ -28,6 +28,7 @@ struct RayQuery {
   bool needs_preintegration = false; // pre-integration committed in mode SEGMENTS (trailing and defaulted: the seven rows below read as they did)
   bool needs_gradient_opacity = false, takes_shade = false; // gradient opacity committed in mode RAMP; `mode` is a shading mode, NONE (0) or GRADIENT (1) (likewise)
   bool takes_depth = false;         // one ray parameter per ray, a device pointer beside org and dir (likewise)
+  bool takes_threshold = false, depth_optional = false; // the depth layer's tau in (0, 0.9999]; a null depth pointer means no limit on any ray (likewise)
 };
 enum RayQueryId { kQueryProject, kQuerySlice, kQuerySliceContext, kQueryIsosurface, kQueryIsosurfaceLayers, kQueryIsosurfaceContext, kQueryIsosurfaceAo, kRayQueryCount };
 constexpr RayQuery kRayQueries[kRayQueryCount] = {
@@ -57,9 +58,15 @@ constexpr int kQueryMaxDepth = kRayQueryRows, kRayQueryAll = kRayQueryRows + 1;
 constexpr RayQuery kMaxDepthQueries[1] = {
   { "ovr_hip_max_depth_floats",          FrameKind::DepthLimitedMarch, QueryNeeds::Nothing,   nullptr,                         false,  false, true,  false, false, false, false, 8, 0, false, false, false, true, true },
 };
+// the eleventh, ovr_hip_depth_output_floats (added with the depth layer), likewise: a row of its own behind the depth limit's, whose ids stay what they were.
+// It needs nothing committed but volume and transfer function: depths (or none) and threshold are the caller's
+constexpr int kQueryDepthOutput = kRayQueryAll, kRayQueryTotal = kRayQueryAll + 1;
+constexpr RayQuery kDepthOutputQueries[1] = {
+  { "ovr_hip_depth_output_floats",       FrameKind::DepthOutputMarch,  QueryNeeds::Nothing,   nullptr,                         false,  false, true,  false, false, false, false, 12, 0, false, false, false, true, true, true, true },
+};
 constexpr const RayQuery& ray_query_row(int id)
 {
-  return id >= kRayQueryRows ? kMaxDepthQueries[id - kRayQueryRows] : id >= kRayQueryIds ? kGradientOpacityQueries[id - kRayQueryIds] : id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id];
+  return id >= kRayQueryAll ? kDepthOutputQueries[id - kRayQueryAll] : id >= kRayQueryRows ? kMaxDepthQueries[id - kRayQueryRows] : id >= kRayQueryIds ? kGradientOpacityQueries[id - kRayQueryIds] : id >= kRayQueryCount ? kPreintegrationQueries[id - kRayQueryCount] : kRayQueries[id];
 }
 // the plan a query asked for is the plan of its kernel (slices: the committed set decides between the two slice kernels, as it does for a frame)
 constexpr bool query_runs(const RayQuery& d, FrameKind k) { return k == d.kind || (d.kind == FrameKind::SliceWalk && k == FrameKind::SlicePlane); }
@@ -75,6 +82,7 @@ struct RayQueryCall {
   long long n = 0;
   int mode = 0, max_events = 0, rotation = 0, range_skipping = 0;
   const float* depth = nullptr; // (takes_depth)
+  float threshold = 0.f;        // (takes_threshold)
 };
 // what the preconditions read of the committed state
 struct QueryFacts {
@@ -93,7 +101,8 @@ inline QueryStatus query_refusal(const RayQuery& d, int code, const std::string&
 // step one of an entry, in front of anything that touches the device
 inline QueryStatus ray_query_arguments(const RayQuery& d, bool renderer, const RayQueryCall& c)
 {
-  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean)) || (d.takes_shade && (c.mode < 0 || c.mode > 1)) || (d.takes_depth && !c.depth)
+  const bool bad = !renderer || !c.org || !c.dir || !c.out || c.n < 0 || (d.takes_mode && (c.mode < kProjectMaximum || c.mode > kProjectMean)) || (d.takes_shade && (c.mode < 0 || c.mode > 1)) || (d.takes_depth && !d.depth_optional && !c.depth)
+                   || (d.takes_threshold && depth_output_check(kDepthOutputOn, c.threshold) != kDepthOutputOk)
                    || (d.takes_max_events && (c.max_events < 1 || c.max_events > kQueryMaxEvents)) || (d.takes_rotation && (c.rotation < 0 || c.rotation >= kQueryRotations));
   return bad ? query_refusal(d, kQueryEinval, "bad arguments") : QueryStatus();
 }

@@ -9,6 +9,7 @@
 #include "../ovr_hip_update.h"
 #pragma GCC visibility push(hidden)
 #include "commit_plan.hpp"
+#include "depth_output_host.hpp"
 #include "gradient_opacity_host.hpp"
 #include "max_depth_host.hpp"
 #include "policy.hpp"
@@ -248,6 +249,7 @@ struct ovr_hip_renderer {
   float* d_max_depth = nullptr;
   float* d_max_depth_queued = nullptr;
   size_t max_depth_capacity = 0, max_depth_queued_capacity = 0; // floats the two buffers hold
+  Queued<ovrhip::DepthOutputState> depth_output; // ovr_hip_set_depth_output (host/depth_output_host.hpp); recorded under kShading like the other frame kinds.  Kept, and not drawn, while depth_output_frame says no
   Queued<ovrhip::host::PreintP> preintegration; // ovr_hip_set_preintegration; recorded under kShading like the other frame kinds.  Kept, and not drawn, while the committed frame is not the unshaded march
   // the integral node table of the committed transfer function (host/preintegration_host.hpp): built by the first pre-integrated frame (or tables getter) after a
   // transfer-function commit - it carries the generation of the tables it was built from and the subdivision the frame's LDS budget allowed
@@ -465,6 +467,8 @@ bool gradient_opacity_frame(const ovr_hip_renderer* r);
 void fill_gradient_opacity_params(const ovr_hip_renderer* r, ovrhip::RayMarchParams& q, bool on);
 // the next frame is a depth-limited march (host/max_depth_host.hpp max_depth_active over the committed state and the committed framebuffer size)
 bool max_depth_frame(const ovr_hip_renderer* r);
+// the next frame is a depth frame (host/depth_output_host.hpp depth_output_active over the committed state); it applies the depth limit iff max_depth_frame
+bool depth_output_frame(const ovr_hip_renderer* r);
 int ensure_shadow_cache(ovr_hip_renderer* r, ovrhip::RayMarchParams& q, hipStream_t st);
 int shadow_lattice_dims(const ovr_hip_renderer* r, int cell, int dims[3]); // of the resident volume; EINVAL past 2^31 - 1 nodes
 int shadow_lattice_positions(ovr_hip_renderer* r, const int dims[3], float* d_pos, hipStream_t st);

@@ -597,6 +597,32 @@ int ovr_hip_get_max_depth_values(ovr_hip_renderer* r, float* depth_host, size_t 
   return 0;
 }
 
+static_assert(kDepthOutputOff == OVR_HIP_DEPTH_OUTPUT_OFF && kDepthOutputOn == OVR_HIP_DEPTH_OUTPUT_ON, "host/depth_output_host.hpp restates include/ovr_hip.h");
+int ovr_hip_set_depth_output(ovr_hip_renderer* r, int32_t mode, float threshold)
+{
+  if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
+  if (const int rule = depth_output_check(mode, threshold)) return fail(OVR_HIP_EINVAL, std::string("[hip] ovr_hip_set_depth_output: ") + depth_output_rule_text(rule));
+  DepthOutputState s;
+  s.mode = mode;
+  s.threshold = mode == kDepthOutputOn ? threshold : 0.f;
+  GroupLock gl(r);
+  { std::lock_guard<std::mutex> lk(r->mtx); r->depth_output.set(s); }
+  GROUP_FORWARD(r, ovr_hip_set_depth_output(m, mode, threshold));
+  return 0;
+}
+
+int ovr_hip_get_depth_output(const ovr_hip_renderer* r, ovr_hip_depth_output* out)
+{
+  if (!r || !out) return fail(OVR_HIP_EINVAL, "[hip] ovr_hip_get_depth_output: null argument");
+  std::memset(out, 0, sizeof(*out));
+  const DepthOutputState& s = r->depth_output.current;
+  out->mode = s.mode;
+  out->active = depth_output_frame(r) ? 1 : 0;
+  out->limited = depth_output_limited(depth_output_frame(r), true, max_depth_frame(r)) ? 1 : 0;
+  out->threshold = s.threshold;
+  return 0;
+}
+
 int ovr_hip_set_ambient_occlusion(ovr_hip_renderer* r, int32_t samples, float distance)
 {
   if (!r) return fail(OVR_HIP_EINVAL, "[hip] null renderer");
@@ -955,6 +981,7 @@ bool same_committed_state(const ovr_hip_renderer* a, const ovr_hip_renderer* b)
     return false;
   if (a->max_depth.current.on != b->max_depth.current.on || a->max_depth.current.width != b->max_depth.current.width || a->max_depth.current.height != b->max_depth.current.height)
     return false; // (the images are each member's copy of the same host image)
+  if (a->depth_output.current.mode != b->depth_output.current.mode || !(a->depth_output.current.threshold == b->depth_output.current.threshold)) return false;
   if (a->jitter.current != b->jitter.current) return false;
   if (a->convergence.current.mode != b->convergence.current.mode || !(a->convergence.current.threshold == b->convergence.current.threshold)) return false;
   // (reconstruction: not forwarded - a group of more than one device refuses every mode but OFF)
@@ -1078,6 +1105,11 @@ int consume_queued(ovr_hip_renderer* r, commit::Changes& ch)
         std::swap(r->max_depth_capacity, r->max_depth_queued_capacity);
       }
       ch.note(kShading, true, true);
+    }
+    {
+      const DepthOutputState dz = r->depth_output.current;
+      if (r->depth_output.update()) // ovr_hip_set_depth_output: the same row - a call sets it, a changed mode or threshold differs
+        ch.note(kShading, true, ch.of[kShading].differs || dz.mode != r->depth_output.current.mode || !(dz.threshold == r->depth_output.current.threshold));
     }
     if (ao.samples != r->ambient_occlusion.current.samples) // the table follows K
       if (int e = upload_ao_table(r, r->ambient_occlusion.current.samples)) return e;
@@ -1635,13 +1667,14 @@ static_assert(kQueryEinval == OVR_HIP_EINVAL && kQueryEstate == OVR_HIP_ESTATE &
                 && kProjectMean == OVR_HIP_PROJECT_MEAN,
               "host/ray_query.hpp restates include/ovr_hip.h");
 int ray_query(ovr_hip_renderer* r, int id, const float* org, const float* dir, float* out, int64_t n, int32_t mode = 0, int32_t max_events = 0, int32_t rotation = 0,
-              int32_t range_skipping = 0, const float* depth = nullptr) // (0: what the entry does not take)
+              int32_t range_skipping = 0, const float* depth = nullptr, float threshold = 0.f) // (0: what the entry does not take)
 {
   const RayQuery& d = ray_query_row(id);
   RayQueryCall c;
   c.org = org; c.dir = dir; c.out = out; c.n = n;
   c.mode = mode; c.max_events = max_events; c.rotation = rotation; c.range_skipping = range_skipping;
   c.depth = depth;
+  c.threshold = threshold;
   if (const QueryStatus s = ray_query_arguments(d, r != nullptr, c); s.code) return fail(s.code, s.message);
   if (int e = set_device(r)) return e;
   if (int e = finish_frame(r)) return e;
@@ -1714,6 +1747,11 @@ int ovr_hip_gradient_opacity_floats(ovr_hip_renderer* r, const float* org, const
 int ovr_hip_max_depth_floats(ovr_hip_renderer* r, const float* org, const float* dir, const float* depth, float* out, int64_t n, int32_t shade)
 {
   return ray_query(r, kQueryMaxDepth, org, dir, out, n, shade, 0, 0, 0, depth);
+}
+
+int ovr_hip_depth_output_floats(ovr_hip_renderer* r, const float* org, const float* dir, const float* depth_or_null, float* out, int64_t n, int32_t shade, float threshold)
+{
+  return ray_query(r, kQueryDepthOutput, org, dir, out, n, shade, 0, 0, 0, depth_or_null, threshold);
 }
 
 int ovr_hip_isosurface_floats(ovr_hip_renderer* r, const float* org, const float* dir, float* out, int64_t n, int32_t range_skipping)

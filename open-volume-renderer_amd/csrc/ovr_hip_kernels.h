@@ -311,6 +311,10 @@ struct RayMarchParams {
   // GRADIENT = the frame is max_depth_kernel's.  width x height ray parameters (device memory, the renderer's own copy), indexed by the FULL frame's pixel index
   // ix + iy * width, in the march's t.  Behind everything else: no other kernel reads it
   const float* max_depth;
+  // the depth layer (ovr_hip_set_depth_output; open-volume-renderer_amd/depth_output.py is the arithmetic): depth_tau > 0 on the march under shading NONE or
+  // GRADIENT = the frame is depth_output_kernel's, whose layer is (d, S, reached) with the crossing at alpha >= depth_tau; max_depth is then null (no limit, no
+  // load) or the committed image.  Behind everything else: no other kernel reads it
+  float depth_tau;
 };
 
 // the shadow cache's build, and the known-answer entry of the shadow march: out[i] = march_shadow - the device function shade_request calls, clipped by p's
@@ -383,6 +387,8 @@ hipError_t launch_clear_blocks(const RayMarchParams& p, const unsigned int* bloc
 //   perspective camera's view vector)                               steps taken, of them steps that fetched a gradient, tx at exit, steps with a > 0, then r, g, b, a of the pixel sample
 //   kQueryMaxDepth (max_depth_ray, ovr_hip_max_depth.h; c.depth = one ray parameter per ray (device), under shading c.mode = 0 (NONE) or 1 (GRADIENT), the
 //   perspective camera's view vector)                               steps taken, the cut tc, tx at exit, steps with a > 0, then r, g, b, a of the pixel sample
+//   kQueryDepthOutput (depth_output_ray, ovr_hip_depth_output.h; c.depth = one ray parameter per ray (device) or null = no limit, c.threshold = tau, shading as
+//   for kQueryMaxDepth)                                             kQueryMaxDepth's eight, then reached, d, k, S
 struct RayQueryCall; // host/ray_query.hpp
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream);
 

@@ -21,6 +21,7 @@
 #include "ovr_hip_preintegration.h"
 #include "ovr_hip_gradient_opacity.h"
 #include "ovr_hip_max_depth.h"
+#include "ovr_hip_depth_output.h"
 #include "ovr_hip_isosurface_context.h"
 #include "ovr_hip_update.h"
 #include "host/ray_query.hpp"
@@ -1036,6 +1037,8 @@ LaunchPlan plan_raymarch(const RayMarchParams& p)
   f.preintegrated = p.preintegrated != 0;
   f.gradient_opacity = p.gradient_opacity != 0;
   f.max_depth = p.max_depth != nullptr;
+  f.depth_output = p.depth_tau > 0.f;
+  f.depth_threshold = p.depth_tau;
   return plan_launch(f, o);
 }
 
@@ -1097,7 +1100,8 @@ static hipError_t launch_sequence(const RayMarchParams& p, const LaunchPlan& pla
   extern template IsosurfaceContextKernels isosurface_context_kernels_of<E>(const LaunchPlan&); \
   extern template PreintegratedKernels preintegrated_kernels_of<E>(const LaunchPlan&); \
   extern template GradientOpacityKernels gradient_opacity_kernels_of<E>(const LaunchPlan&); \
-  extern template MaxDepthKernels max_depth_kernels_of<E>(const LaunchPlan&);
+  extern template MaxDepthKernels max_depth_kernels_of<E>(const LaunchPlan&); \
+  extern template DepthOutputKernels depth_output_kernels_of<E>(const LaunchPlan&);
 OVR_VOXEL_TYPES(OVR_X)
 OVR_VOXEL_TYPES(OVR_X_AO)
 OVR_VOXEL_TYPES(OVR_X_SLICES)
@@ -1149,6 +1153,9 @@ static PlanKernels plan_kernels(const RayMarchParams& p, const LaunchPlan& plan)
   case FrameKind::DepthLimitedMarch:
     if (p.max_depth) // (the kernel loads the pixel's depth: no image, no kernel)
       dispatch_voxel_type<true>(t, [&](auto vt) { k.take(max_depth_kernels_of<decltype(vt)::value>(plan)); });
+    break;
+  case FrameKind::DepthOutputMarch: // (a null image is no limit: the kernel takes z = +inf without a load)
+    dispatch_voxel_type<true>(t, [&](auto vt) { k.take(depth_output_kernels_of<decltype(vt)::value>(plan)); });
     break;
   case FrameKind::March: dispatch_voxel_type(t, [&](auto vt) { k.frame = frame_kernels<decltype(vt)::value>(plan); }); break;
   }
@@ -2111,6 +2118,7 @@ static RayMarchParams query_params(const RayMarchParams& p, bool keep_ranges)
   q.preintegrated = 0; // (likewise)
   q.gradient_opacity = 0; // (likewise)
   q.max_depth = nullptr; // (likewise)
+  q.depth_tau = 0.f; // (likewise)
   q.slice_n = 0; // (committed slices take precedence in a FRAME's plan: the slices' own query puts them back)
   if (!keep_ranges) q.mc_ranges = nullptr;
   return q;
@@ -2170,7 +2178,7 @@ hipError_t launch_shadow_lookup(const RayMarchParams& p, const float* pos, float
 // frame takes for it.  What the query does not ask about is scrubbed from the plan's facts, whatever is committed and whatever the last frame drew
 hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCall& c, hipStream_t stream)
 {
-  if (query < 0 || query >= kRayQueryAll) return hipErrorInvalidValue;
+  if (query < 0 || query >= kRayQueryTotal) return hipErrorInvalidValue;
   const RayQuery& d = ray_query_row(query);
   if (c.n <= 0) return hipSuccess;
   const bool skip = d.takes_range_skipping && c.range_skipping != 0 && !(d.takes_mode && c.mode == kProjectMean); // (a mean needs every sample: it has no skipping twin)
@@ -2183,7 +2191,8 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   if (d.needs_tf && (!p.tf_color || !p.tf_alpha)) return hipErrorInvalidValue;
   if (d.needs_preintegration && (!p.preint_nodes || p.preint_m1 < 1)) return hipErrorInvalidValue;
   if (d.takes_shade && (c.mode < 0 || c.mode > 1)) return hipErrorInvalidValue;
-  if (d.takes_depth && !c.depth) return hipErrorInvalidValue;
+  if (d.takes_depth && !d.depth_optional && !c.depth) return hipErrorInvalidValue;
+  if (d.takes_threshold && depth_output_check(kDepthOutputOn, c.threshold) != kDepthOutputOk) return hipErrorInvalidValue;
   RayMarchParams q = query_params(p, skip);
   switch (d.kind) {
   case FrameKind::Projection: q.projection = c.mode; q.iso_n = 0; q.ao_samples = 0; break; // (p may be an isosurface frame's parameters: the plan asked here is the projection's)
@@ -2197,6 +2206,9 @@ hipError_t launch_ray_query(int query, const RayMarchParams& p, const RayQueryCa
   case FrameKind::GradientOpacityMarch: q.gradient_opacity = 1; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0; break; // (the march's plan under the asked shading, whatever is committed)
   case FrameKind::DepthLimitedMarch: // (the march's plan under the asked shading, whatever is committed; the twin reads c.depth, one value per ray, never q.max_depth)
     q.max_depth = c.depth; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0;
+    break;
+  case FrameKind::DepthOutputMarch: // (likewise; c.depth may be null: no limit on any ray.  The plan reads depth_tau, the twin c.depth)
+    q.depth_tau = c.threshold; q.max_depth = c.depth; q.shading = c.mode; q.projection = 0; q.iso_n = 0; q.ao_samples = 0;
     break;
   default: return hipErrorInvalidValue;
   }

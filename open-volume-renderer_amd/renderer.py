@@ -559,6 +559,49 @@ class DeviceHIP:
         o = out.cpu().numpy()
         return o[:, 0].astype(np.int64), o[:, 1].copy(), o[:, 2].copy(), o[:, 3].astype(np.int64), o[:, 4:8].copy()
 
+    # the depth layer (include/ovr_hip.h ovr_hip_set_depth_output; depth_output.py is the arithmetic): the march that also writes where along each ray it became
+    # opaque into the buffer mapframe hands out as `grad` - (d, S, reached); depth_output.resolve turns a frame into depths.  Queued, applied at commit; every
+    # call resets the accumulation; kept, and not drawn, under FULL shading, while slices, isovalues or a projection are committed, and behind an active
+    # pre-integration or gradient opacity.
+    def set_depth_output(self, threshold=None):
+        """threshold: tau in (0, 0.9999] - the accumulated opacity at which a ray counts as having reached its surface (the smallest positive normal float:
+        the first step with opacity; 0.5: the median surface); None switches the output off.  ValueError where the ABI says EINVAL"""
+        if threshold is None:
+            L.check(self._lib.ovr_hip_set_depth_output(self._h, L.DEPTH_OUTPUT_OFF, 0.0))
+            return
+        code = self._lib.ovr_hip_set_depth_output(self._h, L.DEPTH_OUTPUT_ON, float(threshold))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+
+    def get_depth_output(self):
+        """ovr_hip_depth_output, the COMMITTED state: mode, active (1: the next frame is a depth frame), limited (1: it applies the committed depth image),
+        threshold"""
+        c = L.DepthOutput()
+        L.check(self._lib.ovr_hip_get_depth_output(self._h, C.byref(c)))
+        return c
+
+    def depth_output_rays(self, org, direction, threshold, depth=None, shade=0):
+        """depth-output rays as the kernel evaluates them (ovr_hip_depth_output_floats; known-answer tests): world rays (n, 3), (n, 3) - the direction used as
+        given - ray i ending on depth[i] (n,) (None: no limit on any ray), under shading `shade` (0 NONE, 1 GRADIENT) -> dict(steps (n,) int64, tc, tx (n,)
+        float32, shaded (n,) int64, rgba (n, 4) float32, reached (n,) bool, d (n,) float32, k (n,) int64, S (n,) float32)"""
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        arrays = (org, direction) if depth is None else (org, direction, depth)
+        t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev) for a in arrays]
+        n = int(t[0].numel()) // 3
+        if t[0].numel() != 3 * n or t[1].numel() != 3 * n or (depth is not None and t[2].numel() != n):
+            raise RuntimeError("depth_output_rays: org and direction hold three floats per ray, depth one")
+        out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        code = self._lib.ovr_hip_depth_output_floats(self._h, t[0].data_ptr(), t[1].data_ptr(), None if depth is None else t[2].data_ptr(), out.data_ptr(), n, int(shade), float(threshold))
+        if code == -1:   # OVR_HIP_EINVAL
+            raise ValueError((self._lib.ovr_hip_last_error() or b"").decode("utf-8", "replace"))
+        L.check(code)
+        o = out.cpu().numpy()
+        return dict(steps=o[:, 0].astype(np.int64), tc=o[:, 1].copy(), tx=o[:, 2].copy(), shaded=o[:, 3].astype(np.int64), rgba=o[:, 4:8].copy(),
+                    reached=o[:, 8] != 0, d=o[:, 9].copy(), k=o[:, 10].astype(np.int64), S=o[:, 11].copy())
+
     # isosurfaces (include/ovr_hip.h ovr_hip_set_isosurfaces; isosurface.py is the arithmetic): opaque, shaded, hard-shadowed level sets in the march's place; the
     # buffer mapframe hands out as `grad` carries the layer (isovalue, t*, 1).  Queued, applied at commit; every call resets the accumulation.
     def set_isosurfaces(self, values=(), opacities=None):

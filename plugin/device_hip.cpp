@@ -18,6 +18,7 @@
 #include "../open-volume-renderer_amd/csrc/host/preintegration_host.hpp" // (HIP-free: parse_preintegration)
 #include "../open-volume-renderer_amd/csrc/host/gradient_opacity_host.hpp" // (HIP-free: parse_gradient_opacity)
 #include "../open-volume-renderer_amd/csrc/host/max_depth_host.hpp" // (HIP-free: max_depth_read_file)
+#include "../open-volume-renderer_amd/csrc/host/depth_output_host.hpp" // (HIP-free: parse_depth_output, depth_output_write_file)
 
 #include <chrono>
 #include <cmath>
@@ -77,6 +78,13 @@ public:
       ovr_hip_convergence c;
       if (ovr_hip_get_convergence(h, &c) == 0)
         std::fprintf(stderr, "[hip] convergence: error %g after %d frames, %d of %d blocks retired\n", (double)c.error, c.frames, c.retired_blocks, c.blocks);
+    }
+    // OVR_HIP_DEPTH_OUTPUT_FILE: the last mapped depth frame's resolved threshold depth (see mapframe)
+    if (const char* path = std::getenv("OVR_HIP_DEPTH_OUTPUT_FILE")) {
+      const bool quiet = std::getenv("OVR_HIP_QUIET") && std::getenv("OVR_HIP_QUIET")[0] != '0';
+      if (depth_layer.empty()) std::fprintf(stderr, "[hip] OVR_HIP_DEPTH_OUTPUT_FILE: the last mapped frame was no depth frame (OVR_HIP_DEPTH_OUTPUT, OVR_HIP_MAP_GRAD): nothing is written\n");
+      else if (!ovrhip::depth_output_write_file(path, depth_layer.data(), depth_w, depth_h)) std::fprintf(stderr, "[hip] OVR_HIP_DEPTH_OUTPUT_FILE: %s could not be written\n", path);
+      else if (!quiet) std::fprintf(stderr, "[hip] depth output: %d x %d threshold depths written to %s\n", depth_w, depth_h, path);
     }
     ovr_hip_destroy(h);
   }
@@ -280,6 +288,17 @@ public:
         check(ovr_hip_set_gradient_opacity(h, OVR_HIP_GRADIENT_OPACITY_RAMP, lo, hi));
         if (!quiet) std::fprintf(stderr, "[hip] gradient opacity: ramp %g ... %g (drawn by march frames under shading NONE or GRADIENT)\n", (double)lo, (double)hi);
       }
+      // The depth layer (ovr_hip_set_depth_output): OVR_HIP_DEPTH_OUTPUT=<threshold>, a number in (0, 0.9999] - the accumulated opacity at which a ray counts as
+      // having reached its surface.  The gradient layer of a march frame under shading NONE or GRADIENT then carries (d, S, reached), depths in the march's t: the
+      // unit OVR_HIP_MAX_DEPTH takes.  OVR_HIP_DEPTH_OUTPUT_FILE=<path>: when the renderer is destroyed the last mapped frame's resolved threshold depth is written
+      // there as raw little-endian float32 in the frame's pixel order, +inf where not reached - exactly the file OVR_HIP_MAX_DEPTH reads.  Unset: nothing is called
+      if (const char* zv = std::getenv("OVR_HIP_DEPTH_OUTPUT")) {
+        float tau = 0.f;
+        if (!ovrhip::parse_depth_output(zv, &tau))
+          throw std::runtime_error("[hip] OVR_HIP_DEPTH_OUTPUT expects a threshold in (0, 0.9999]");
+        check(ovr_hip_set_depth_output(h, OVR_HIP_DEPTH_OUTPUT_ON, tau));
+        if (!quiet) std::fprintf(stderr, "[hip] depth output: threshold %g (drawn by march frames under shading NONE or GRADIENT; the gradient layer carries the depth)\n", (double)tau);
+      }
     }
     commit();
   }
@@ -391,6 +410,17 @@ public:
     check(ovr_hip_mapframe(h, OVR_HIP_MEM_HOST, &rgba, &nb_rgba, want_grad ? &grad : nullptr, want_grad ? &nb_grad : nullptr));
     fb->rgba->set_data((void*)rgba, nb_rgba, ovr::CrossDeviceBuffer::DEVICE_CPU);
     if (want_grad) fb->grad->set_data((void*)grad, nb_grad, ovr::CrossDeviceBuffer::DEVICE_CPU);
+    // OVR_HIP_DEPTH_OUTPUT_FILE: keep the layer of the last mapped frame while it is a depth frame's (the destructor resolves and writes it)
+    static const bool want_depth_file = std::getenv("OVR_HIP_DEPTH_OUTPUT_FILE") != nullptr;
+    if (want_depth_file) {
+      ovr_hip_depth_output z;
+      const int w = params.fbsize.ref().x, ht = params.fbsize.ref().y;
+      depth_layer.clear();
+      if (want_grad && grad && ovr_hip_get_depth_output(h, &z) == 0 && z.active && w > 0 && ht > 0 && nb_grad == (size_t)w * (size_t)ht * 3 * sizeof(float)) {
+        depth_layer.assign(grad, grad + (size_t)w * (size_t)ht * 3);
+        depth_w = w; depth_h = ht;
+      }
+    }
   }
 
 private:
@@ -409,6 +439,8 @@ private:
   bool angles_set = false;
   ovr_hip_renderer* h = nullptr;
   bool have_noise = false;
+  std::vector<float> depth_layer; // OVR_HIP_DEPTH_OUTPUT_FILE: the layer (3 floats per pixel) of the last mapped frame, empty while that was no depth frame
+  int depth_w = 0, depth_h = 0;
   float said_height = 0.f; // OVR_HIP_ORTHOGRAPHIC: the height last reported on stderr (the camera is forwarded with every change; said once per value)
 
   int convergence_mode = OVR_HIP_CONVERGENCE_OFF;
